@@ -1,6 +1,7 @@
 """E4T pre-training throughput on MI355X (BASELINE.json metric) — driver contract in the task description.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full reference training step (pretrain_e4t.py:595-654) on a synthetic batch: VAE encode,
@@ -37,6 +38,27 @@ def build_models(dev, model, seed):
     """the benchmark's models: e4t.builders (the factory the CLIs use too), token table incl. the placeholder row"""
     from e4t.builders import build_models as _build
     return _build(dev, model, seed, vocab_size=49409)
+
+
+DUMP_SAMPLE = 1 << 21        # trainable-parameter elements dumped by --dump-outputs: 8 MB of values + 16 MB of float64 indices
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, losses, tr):
+    """--dump-outputs: what a caller of the timed step receives from its last call — the returned (loss, loss_diff, loss_reg) and the
+    trainable parameters the step updated in place (E4TTrainer.flat: weight offsets + E4T head, fp32).  The parameters are too large to
+    store whole (the head's stack alone is ~845 MB), so a fixed sample of them is written: DUMP_SAMPLE flat indices drawn from a CPU
+    generator seeded with DUMP_SEED, sorted, the same for every run of the same model."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    flat = tr.flat.data
+    idx = torch.randint(0, flat.numel(), (min(DUMP_SAMPLE, flat.numel()),), generator=torch.Generator().manual_seed(DUMP_SEED)).sort().values
+    arrays = dict(zip(("loss", "loss_diff", "loss_reg"), losses))
+    arrays["trainable_params_sample"] = flat[idx.to(flat.device)]
+    arrays["trainable_params_sample_index"] = idx.double()
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
 
 
 def cpu_baseline_and_parity(model, threads, dev):
@@ -174,7 +196,11 @@ def main():
     ap.add_argument("--materialise-head-grad", action="store_true", help="A/B: write the E4T head's 845 MB stacked weight gradient (batched GEMM + plain AdamW) instead of the factored update")
     ap.add_argument("--head-allreduce", action="store_true", help="N > 1: all-reduce the E4T head's 845 MB stacked weight gradient instead of gathering its factors (A/B)")
     ap.add_argument("--step-graph", action="store_true", help="A/B: the whole step replayed from one HIP graph (no next-batch prefetch: the two exclude each other)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step computed to DIR/<name>.npy "
+                                                         "(rank 0): its three losses and a fixed, seeded sample of the trainable parameters it updated")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -236,9 +262,12 @@ def main():
     t0 = time.perf_counter()
     for s in range(args.steps):
         tr.prefetch(pool[(args.warmup + s + 1) % len(pool)][0])
-        loss, _, _ = tr.train_step(*pool[(args.warmup + s) % len(pool)])
+        step_out = tr.train_step(*pool[(args.warmup + s) % len(pool)])
     sync()
     dt = time.perf_counter() - t0
+    loss = step_out[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, step_out, tr)     # before the instrumented steps below move the parameters on
     tmax = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)

@@ -1,6 +1,7 @@
 """Generates tests/golden/reference_*.pt by RUNNING THE REFERENCE'S OWN CODE (build container only: needs /root/reference).
 
     python tests/golden/make_golden_models.py [output_dir]
+    python tests/golden/make_golden_models.py --check     # regenerate into a temporary directory, compare with the committed files
 
 /root/reference/e4t/models/{cross_attention,attention,transformer_2d,unet_2d_blocks,unet_2d_condition}.py and
 /root/reference/e4t/encoder.py are imported unmodified; `diffusers`, `kornia`, `open_clip` resolve to the stand-ins under
@@ -443,7 +444,33 @@ def tuning_step_fixture(unet_blob):
                 loss_reg=ns["loss_reg"].detach(), total_norm=norms[0].detach(), grads=pack(grads), params_after=pack({n: named[n].detach().clone() for n in pick}))
 
 
+def check_against_committed(out_dir):
+    """--check: the freshly generated fixtures in out_dir equal the committed ones (flattened, rtol 1e-5 / atol 1e-6)"""
+    def flat(x, out):
+        if torch.is_tensor(x):
+            out.append(x.detach().reshape(-1).double())
+        elif isinstance(x, dict):
+            for k in sorted(x, key=str):
+                flat(x[k], out)
+        elif isinstance(x, (list, tuple)):
+            for v in x:
+                flat(v, out)
+        return out
+    for name in FIXTURES:
+        a = torch.cat(flat(torch.load(os.path.join(HERE, f"reference_{name}.pt")), []))
+        b = torch.cat(flat(torch.load(os.path.join(out_dir, f"reference_{name}.pt")), []))
+        assert a.shape == b.shape, (name, a.shape, b.shape)
+        torch.testing.assert_close(a, b, rtol=1e-5, atol=1e-6, msg=lambda m, name=name: f"{name}: {m}")
+    print("committed fixtures are what the reference produces")
+
+
+FIXTURES = ("unet", "unet_wide", "attention", "encoder", "encoder_wide", "pipeline", "pipeline_wide", "step", "tuning_step")
+
+
 if __name__ == "__main__":
+    import tempfile
+    check = sys.argv[1:] == ["--check"]
+    out_dir = tempfile.mkdtemp() if check else (sys.argv[1] if len(sys.argv) > 1 else HERE)
     import open_clip
     open_clip.TEST_ARCHS["ViT-golden-test"] = dict(image_size=224, patch_size=56, width=8, layers=2, heads=2, mlp_ratio=2.0)
     open_clip.TEST_ARCHS["ViT-golden-wide"] = dict(image_size=224, patch_size=56, width=64, layers=2, heads=2, mlp_ratio=2.0)
@@ -452,6 +479,8 @@ if __name__ == "__main__":
                      ("pipeline", lambda: pipeline_fixture(blobs["unet"]["sd1"])), ("pipeline_wide", pipeline_wide_fixture),
                      ("step", lambda: step_fixture(blobs["unet"]["sd1"])), ("tuning_step", lambda: tuning_step_fixture(blobs["unet"]["sd1"]))):
         blobs[name] = fn()
-        path = os.path.join(sys.argv[1] if len(sys.argv) > 1 else HERE, f"reference_{name}.pt")
+        path = os.path.join(out_dir, f"reference_{name}.pt")
         torch.save(blobs[name], path)
         print(f"{path}: {os.path.getsize(path) / 1e6:.2f} MB")
+    if check:
+        check_against_committed(out_dir)
