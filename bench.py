@@ -2,6 +2,7 @@
 
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR     # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full [--details FILE]  # + roofline, secondary configs, CPU baseline + parity
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" is one full reference training step (pretrain_e4t.py:595-654) on a synthetic batch: VAE encode,
@@ -9,6 +10,10 @@ noise, UNet encoder pass, E4T encoder (ViT-H-14 + head), embed injection, text e
 backward, gradient all-reduce (N > 1), fused AdamW.  Workload at N=1 = BASELINE.json configs[1]: SD-1.4 UNet
 config + ViT-H-14 E4T encoder, 512 px, bf16, per-GPU batch 16, random-init weights, synthetic images
 ("data": "synthetic").  Rank 0 prints ONE JSON line.
+
+A plain run only sets up, warms up, times the steps (and writes --dump-outputs) before it prints that line.  Everything else the
+benchmark measures or checks runs only with --full, after the timed steps: two instrumented steps for the per-kernel roofline (and the
+`comm` block at N > 1), the secondary configurations, the CPU baseline with its parity check.  Their keys are null in a plain run.
 """
 from __future__ import annotations
 
@@ -189,10 +194,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=16, help="per-GPU batch")
     ap.add_argument("--model", default="sd14", choices=["sd14", "sd21"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the kernel roofline, the secondary configurations and "
+                                                      "the CPU baseline with its parity check (the --no-* options below leave one out)")
+    ap.add_argument("--details", metavar="FILE", help="--full: also write the complete blocks (per-kernel tables, parity, secondary) as JSON "
+                                                     "to FILE; they always go to stderr")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and its parity check")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-kernel-roofline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the configs[3] / configs[4] block (tuning step, SD-2.x @768)")
+    ap.add_argument("--no-kernel-roofline", action="store_true", help="--full: skip the two instrumented steps")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the configs[3] / configs[4] block (tuning step, SD-2.x @768)")
     ap.add_argument("--materialise-head-grad", action="store_true", help="A/B: write the E4T head's 845 MB stacked weight gradient (batched GEMM + plain AdamW) instead of the factored update")
     ap.add_argument("--head-allreduce", action="store_true", help="N > 1: all-reduce the E4T head's 845 MB stacked weight gradient instead of gathering its factors (A/B)")
     ap.add_argument("--step-graph", action="store_true", help="A/B: the whole step replayed from one HIP graph (no next-batch prefetch: the two exclude each other)")
@@ -201,6 +210,11 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.details and not args.full:
+        ap.error("--details needs --full")
+    do_roof = args.full and not args.no_kernel_roofline
+    do_secondary = args.full and not args.no_secondary
+    do_cpu = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -275,7 +289,7 @@ def main():
     ips = B * world * args.steps / dt
 
     roof = roof_hbm = None
-    if not args.no_kernel_roofline:
+    if do_roof:
         # two extra, instrumented steps (outside the timed region): HIP events around every instrumented launch, recorded on the
         # stream the kernel is launched on.  EVERY rank runs them — a training step contains the gradient all-reduce, a collective
         # rank 0 must not enter alone — and rank 0 records and reports.
@@ -296,8 +310,8 @@ def main():
         torch.cuda.synchronize()
         tr.prefetch_mode = mode
         prof_alone, hip.prof = hip.prof, prof_steady
-    comm = tr.comm_report() if ((world > 1 or force_comm) and not args.no_kernel_roofline) else None
-    if rank == 0 and not args.no_kernel_roofline:
+    comm = tr.comm_report() if ((world > 1 or force_comm) and do_roof) else None
+    if rank == 0 and do_roof:
         def aggregate(prof):
             agg = {}
             for key, fl, nb, e0, e1 in prof:
@@ -402,18 +416,18 @@ def main():
         dist.barrier()
 
     cpu = parity = secondary = None
-    if rank == 0 and world == 1 and not (args.no_cpu_baseline and args.no_secondary):
+    if rank == 0 and world == 1 and (do_cpu or do_secondary):
         del tr, unet, enc, text, vae
         torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_secondary and args.model == "sd14":
+    if rank == 0 and world == 1 and do_secondary and args.model == "sd14":
         secondary = secondary_configs(dev)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and do_cpu:
         threads = args.cpu_threads or min(os.cpu_count() or 8, 128)
         cpu, parity = cpu_baseline_and_parity(args.model, threads, dev)
 
     if rank == 0:
         # The printed line is SHORT (the driver's record keeps the known keys and the last ~2 KB of stdout: the 16 KB line of rounds 2-4 lost
-        # its parity / secondary / per-kernel blocks there).  Everything else goes to gpurun_out/bench_details.json (+ stderr).
+        # its parity / secondary / per-kernel blocks there).  With --full everything else goes to stderr (+ the --details file).
         details = dict(roofline=roof, roofline_hbm=roof_hbm, parity=parity, secondary=secondary, comm=comm)
         r3 = lambda x: None if x is None else float(f"{x:.4g}")
         short_roof = short_hbm = None
@@ -451,14 +465,17 @@ def main():
                                per_gpu_batch=B, global_batch=B * world, parallelism=f"dp{world}", trainable="weight offsets + E4T head (ViT frozen)",
                                next_batch_prefetch=tr_prefetch, last_loss=float(loss)),
                    roofline=short_roof, roofline_hbm=short_hbm, cpu_baseline=cpu, parity=short_par,
-                   secondary_ms_per_step=sec_ms, secondary_images_per_s=sec_ips, comm=comm, details="gpurun_out/bench_details.json")
-        try:
-            os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-            with open(os.path.join(ROOT, "gpurun_out", "bench_details.json"), "w") as fh:
-                json.dump(dict(line=out, **details), fh, indent=1)
-        except OSError:
-            out["details"] = None
-        print(json.dumps(details), file=sys.stderr, flush=True)
+                   secondary_ms_per_step=sec_ms, secondary_images_per_s=sec_ips, comm=comm, details=args.details)
+        if args.details:
+            try:
+                os.makedirs(os.path.dirname(os.path.abspath(args.details)), exist_ok=True)
+                with open(args.details, "w") as fh:
+                    json.dump(dict(line=out, **details), fh, indent=1)
+            except OSError as e:
+                print(f"bench.py: cannot write --details {args.details}: {e}", file=sys.stderr)
+                out["details"] = None
+        if args.full:
+            print(json.dumps(details), file=sys.stderr, flush=True)
     if world > 1 or force_comm:
         dist.barrier()
         dist.destroy_process_group()

@@ -10,7 +10,7 @@ timeout 600 python -m pytest tests/test_kernels_gpu.py -q -x -k "attention" > gp
 for v in default a_old a_occ1 a_nofence; do
   if [ $v = default ]; then timeout 300 python tools/ab_attn.py default; else E4T_LIB=$V/libe4t_hip_$v.so timeout 300 python tools/ab_attn.py $v; fi
 done > gpurun_out/r06a_ab_attn.txt 2>&1; stamp "ab_attn"; cat gpurun_out/r06a_ab_attn.txt
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary"
 run() { name=$1; shift; env "$@" timeout 400 $B > gpurun_out/r06a_$name.json 2> gpurun_out/r06a_$name.err; python - "$name" <<'PY'
 import json, sys
 try:

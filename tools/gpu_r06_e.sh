@@ -3,7 +3,7 @@
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 timeout 600 python -m pytest tests/test_kernels_gpu.py -q -x -k "streaming" 2>&1 | grep -v amdgpu.ids | tail -8
-B="python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-secondary"
+B="python bench.py --steps 10 --warmup 3 --full --no-cpu-baseline --no-secondary"
 run() { name=$1; shift; timeout 400 $B "$@" > gpurun_out/r06e_$name.json 2> gpurun_out/r06e_$name.err; python - "$name" <<'PY'
 import json, sys
 try:
