@@ -420,6 +420,59 @@ extern "C" int e4t_guided_step(const float* pred, const float* sample, const flo
   E4T_CHECK_LAUNCH("guided_step_kernel");
   return 0;
 }
+// Guidance + one step of any linear sampler (DDIM, PLMS, LMS, Euler, Euler-ancestral, DPM-Solver++ 2M) in a single pass.
+// The row contract is the header's (e4t_sampler_step).  Every thread owns one element index across x, out, hist, saved
+// and x_in, so reading the old values before writing the new ones needs no synchronisation and x may alias out.
+// Terms whose coefficient is 0 are skipped (uniform branch on a row value), which keeps a DDIM row's arithmetic exactly
+// guided_step_kernel's: same expressions in the same order, so the same contraction.
+__global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restrict__ pred, const float* x, float* out, float* hist, float* saved,
+                                                           const float* __restrict__ noise, float* x_in, const float* __restrict__ row,
+                                                           int B, int C, int HW, int K, int cfg, int nhwc, int x_in_copies) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const long long n = (long long)B * C * HW;
+  if (i >= n) return;
+  const float g = row[0], a_e = row[1], a_x = row[2], c_x = row[3], c_s = row[4], c_m = row[5], c_n = row[6], k_in = row[7];
+  const int w = (int)row[8], save_x = row[9] != 0.f;
+  long long j = i;
+  if (nhwc) {
+    const int p = (int)(i % HW), c = (int)((i / HW) % C), b = (int)(i / ((long long)HW * C));
+    j = ((long long)b * HW + p) * C + c;
+  }
+  float e = pred[j];
+  if (cfg) {
+    const float t = pred[j + n];
+    e = e + g * (t - e);
+  }
+  const float xv = x[i];
+  float m = a_e * e;
+  if (a_x != 0.f) m = __fmaf_rn(a_x, xv, m);
+  float o = c_x * xv + c_m * m;
+  if (c_s != 0.f && saved) o = __fmaf_rn(c_s, saved[i], o);
+  for (int k = 0; k < K; ++k) {
+    const float ck = row[10 + k];
+    if (ck != 0.f) o = __fmaf_rn(ck, hist[k * n + i], o);
+  }
+  if (noise && c_n != 0.f) o += c_n * noise[i];
+  if (w >= 0 && w < K) hist[w * n + i] = m;
+  if (save_x && saved) saved[i] = xv;
+  out[i] = o;
+  if (x_in_copies > 0) {
+    const float v = k_in * o;
+    x_in[i] = v;
+    if (x_in_copies > 1) x_in[n + i] = v;
+  }
+}
+extern "C" int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
+                                const float* row, int B, int C, int HW, int K, int cfg, int pred_nhwc, int x_in_copies, e4t_stream s) {
+  E4T_REQUIRE(pred && x && out && row && B > 0 && C > 0 && HW > 0, "sampler_step: bad arguments");
+  E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
+  E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 2 && (x_in_copies == 0 || x_in), "sampler_step: x_in_copies = %d (0..2, x_in required when > 0)", x_in_copies);
+  const long long n = (long long)B * C * HW;
+  hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
+                     B, C, HW, K, cfg, pred_nhwc, x_in_copies);
+  E4T_CHECK_LAUNCH("sampler_step_kernel");
+  return 0;
+}
 extern "C" int e4t_transpose(const void* in, void* out, int batch, int R, int C, int ldi, int ldo, long long bsi, long long bso, e4t_stream s) {
   E4T_REQUIRE(in && out && batch > 0 && R > 0 && C > 0 && ldi >= C && ldo >= R, "transpose: bad arguments");
   hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(C, 64), cdiv(R, 64), batch), dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, R, C, ldi, ldo, bsi, bso);

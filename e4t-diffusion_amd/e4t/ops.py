@@ -503,6 +503,31 @@ class HipBackend:
                  "e4t_guided_step")
         return out
 
+    def sampler_step(self, pred, x, row, hist=None, saved=None, noise=None, x_in=None, cfg=True, pred_nhwc=False, out=None):
+        """guidance + one linear sampler update (the row contract of e4t_sampler_step in include/e4t_hip.h); row = device fp32
+        [16]; hist = [K, *x.shape] (K <= 4); x_in = [x.shape[0] or 2*x.shape[0], ...] receives k_in*out once or twice.
+        Returns out (x may be passed as out: in place)."""
+        B, Cn = x.shape[0], x.shape[1]
+        HW = x.numel() // (B * Cn)
+        assert pred.dtype == f32 and x.dtype == f32 and row.dtype == f32 and row.numel() == _C.SAMPLER_ROW and row.is_contiguous()
+        assert pred.is_contiguous() and x.is_contiguous() and pred.numel() == x.numel() * (2 if cfg else 1)
+        for t in (saved, noise):
+            assert t is None or (t.dtype == f32 and t.is_contiguous() and t.shape == x.shape)
+        K = 0
+        if hist is not None:
+            K = hist.shape[0]
+            assert hist.dtype == f32 and hist.is_contiguous() and tuple(hist.shape[1:]) == tuple(x.shape) and K <= _C.SAMPLER_MAX_HIST
+        copies = 0
+        if x_in is not None:
+            assert x_in.dtype == f32 and x_in.is_contiguous() and x_in.numel() % x.numel() == 0
+            copies = x_in.numel() // x.numel()
+        if out is None:
+            out = torch.empty_like(x)
+        assert out.dtype == f32 and out.is_contiguous() and out.shape == x.shape
+        _C.check(self.lib.e4t_sampler_step(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
+                                           B, Cn, HW, K, int(cfg), int(pred_nhwc), copies, _stream()), "e4t_sampler_step")
+        return out
+
     def image_prep(self, pool, table, B, S, out=None):
         """raw uint8 RGB images packed in `pool` + int64 [B,8] plan `table` (both on the device) -> fp32 [B,3,S,S]"""
         assert pool.dtype == torch.uint8 and table.dtype == torch.int64 and table.shape == (B, 8) and table.is_contiguous()

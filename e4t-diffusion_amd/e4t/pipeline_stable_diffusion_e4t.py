@@ -9,12 +9,18 @@ the MI355X:
   * everything that does not depend on the latents is evaluated once per call, not once per step: the CLIP-ViT features of
     the conditioning image (``E4TEncoder.encode_vision``), the ""-prompt context, the weight-offset ``W_eff`` (cached by
     the bank while the parameters do not change);
-  * guidance + the DDIM update are one kernel (``e4t_guided_step``) reading the UNet's NHWC output in place;
+  * guidance + the scheduler update are one kernel (``e4t_sampler_step``) reading the UNet's NHWC output in place, for every
+    sampler whose update is linear (``scheduler.fused_plan``: DDIM without clipping at any eta, PLMS, LMS, Euler,
+    Euler-ancestral, DPM-Solver++ 2M; epsilon or v prediction).  The coefficients of all steps are computed on the host once
+    per call; earlier per-step terms (eps / derivative / x0 history, PLMS's first sample) live in device buffers, and the
+    kernel also writes the next UNet input (``scale_model_input`` folded in) as the [x_in | x_in] CFG batch;
   * at 1-2 images a step is ~2000 short kernel launches; the whole step is captured once into a hipGraph
-    (``torch.cuda.CUDAGraph``) and replayed per timestep: the timestep and the update coefficients are read from small
-    device buffers that are refreshed between replays.  ``use_graph=None`` -> on for <= 2 images per call when the
-    scheduler update is linear and eta == 0 (measured: 13.6 -> 11.8 ms/step at one image, nothing from four images up,
-    where the step is GPU-bound); ``use_graph=False`` -> eager.
+    (``torch.cuda.CUDAGraph``) and replayed per timestep: the timestep and the coefficient row are read from small device
+    buffers that are refreshed between replays, and noise (Euler-ancestral, DDIM with eta > 0) is drawn outside the graph
+    into a fixed buffer by the same ``torch.randn`` call ``step`` makes.  ``use_graph=None`` -> on for <= 2 images per call
+    when the update is fused (measured with DDIM: 13.6 -> 11.8 ms/step at one image, nothing from four images up, where the
+    step is GPU-bound); ``use_graph=False`` -> eager.  Without ``e4t_sampler_step`` (the CPU op emulation) only DDIM with
+    eta == 0 is fused, through ``e4t_guided_step``; every other case takes the generic ``scale_model_input`` / ``step`` path.
 
 The tokenizer is whatever object the caller passes (``transformers.CLIPTokenizer`` in inference.py): it needs
 ``__call__(text, padding=, truncation=, max_length=, return_tensors="pt", add_special_tokens=)``, ``add_tokens``,
@@ -76,6 +82,7 @@ class StableDiffusionE4TPipeline:
         self.domain_embed_scale = cfg.domain_embed_scale
         self._progress = {}
         self._graph = None
+        self._fused_sampling = True          # False: every sampler takes the generic scale_model_input / step path
 
     # ---- housekeeping the reference inherits from DiffusionPipeline -------------------------------------------------
     @property
@@ -146,10 +153,16 @@ class StableDiffusionE4TPipeline:
         return [Image.fromarray(i) for i in (images * 255).round().astype("uint8")]
 
     # ---- one denoising step -----------------------------------------------------------------------------------------
-    def _model_step(self, latents, t, s):
-        """eps (or v) prediction for guidance: returns the UNet output tensor of the [uncond | cond] (or cond-only) batch"""
+    def _model_step(self, latents, t, s, x_in=None):
+        """eps (or v) prediction for guidance: returns the UNet output tensor of the [uncond | cond] (or cond-only) batch.
+        x_in: the scaled UNet input when the caller already has it, as the [x_in | x_in] batch under guidance (the fused
+        loop: e4t_sampler_step writes it); None -> scheduler.scale_model_input(latents, t)."""
         bsz = latents.shape[0]
-        x_in = self.scheduler.scale_model_input(latents, t)
+        x_cat = None
+        if x_in is None:
+            x_in = self.scheduler.scale_model_input(latents, t)
+        else:
+            x_cat, x_in = x_in, x_in[:bsz]
         ctx_e = s["ctx_e"].expand(bsz, -1, -1)
         enc = self.unet(x_in, t, ctx_e, return_encoder_outputs=True)                                   # :189
         if s["vision"] is not None:
@@ -161,7 +174,8 @@ class StableDiffusionE4TPipeline:
         emb[:, s["idx"], :] = domain.to(emb.dtype)                                                       # :195-196
         ctx = self.text_encoder(inputs_embeds=emb)[0].to(ctx_e.dtype)                                    # :198
         if s["cfg"]:
-            return self.unet(torch.cat([x_in] * 2), t, torch.cat([ctx_e, ctx])).sample                 # :199-206
+            x_cat = torch.cat([x_in] * 2) if x_cat is None else x_cat
+            return self.unet(x_cat, t, torch.cat([ctx_e, ctx])).sample                                     # :199-206
         return self.unet(x_in, t, ctx).sample
 
     def _fused_update(self, pred, latents, coef, cfg):
@@ -171,6 +185,16 @@ class StableDiffusionE4TPipeline:
             ops.backend().guided_step(nhwc, latents, coef, cfg=cfg, pred_nhwc=True, out=latents)
         else:
             ops.backend().guided_step(pred.contiguous(), latents, coef, cfg=cfg, pred_nhwc=False, out=latents)
+
+    def _sampler_update(self, pred, latents, row, bufs, cfg):
+        """guidance + any linear sampler update in one kernel (e4t_sampler_step), in place on `latents`; also writes the next
+        UNet input into bufs["x_in"]"""
+        nhwc = pred.permute(0, 2, 3, 1)
+        kw = dict(hist=bufs["hist"], saved=bufs["saved"], noise=bufs["noise"], x_in=bufs["x_in"], cfg=cfg, out=latents)
+        if nhwc.is_contiguous():                         # the native UNet hands out an NCHW view of NHWC storage
+            ops.backend().sampler_step(nhwc, latents, row, pred_nhwc=True, **kw)
+        else:
+            ops.backend().sampler_step(pred.contiguous(), latents, row, pred_nhwc=False, **kw)
 
     # ---- the call -------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -208,28 +232,52 @@ class StableDiffusionE4TPipeline:
                  pixels=pixels.expand(bsz, -1, -1, -1), vision=vision, scale=scale, cfg=cfg)
 
         sch = self.scheduler
-        fused = isinstance(sch, DDIMScheduler) and not sch.config["clip_sample"] and sch.config["prediction_type"] != "sample" and eta == 0.0
-        if use_graph is None:       # measured (SD-1.4, 512 px, 50 steps): 13.6 -> 11.8 ms/step at 1 image, no gain from 4 images up
-            use_graph = fused and device.type == "cuda" and bsz <= 2
-        if use_graph and not fused:
-            raise ValueError("graph replay needs the fused linear update (DDIMScheduler without sample clipping, eta == 0)")
+        native = device.type == "cuda" and hasattr(ops.backend(), "sampler_step")
+        plan = sch.fused_plan(guidance_scale, eta) if self._fused_sampling and hasattr(sch, "fused_plan") else None
+        if plan is not None and not native and not (isinstance(sch, DDIMScheduler) and eta == 0.0):
+            plan = None                  # without e4t_sampler_step only DDIM with eta == 0 is fused (through e4t_guided_step)
+        if use_graph is None:       # measured (SD-1.4, 512 px, 50 steps, DDIM): 13.6 -> 11.8 ms/step at 1 image, no gain from 4 images up
+            use_graph = plan is not None and device.type == "cuda" and bsz <= 2
+        if use_graph and plan is None:
+            raise ValueError("graph replay needs the fused linear update (a scheduler with a fused_plan: no sample clipping, "
+                             "epsilon / v prediction; on the CPU op emulation DDIM with eta == 0 only)")
 
-        if fused:
-            table = torch.tensor([[guidance_scale, *sch.coefficients(int(t), 0.0)] for t in timesteps.tolist()], dtype=torch.float32, device=device)
-            coef = torch.empty(4, dtype=torch.float32, device=device)
-            t_buf = torch.empty(1, dtype=torch.int64, device=device)
+        if plan is not None:
+            timesteps = plan.timesteps
+            table = plan.table.to(device=device, dtype=torch.float32)
+            t_buf = torch.empty(1, dtype=timesteps.dtype, device=device)
+            if native:
+                row = torch.empty(table.shape[1], dtype=torch.float32, device=device)
+                bufs = dict(hist=torch.zeros((plan.K,) + tuple(latents.shape), dtype=torch.float32, device=device) if plan.K else None,
+                            saved=torch.zeros_like(latents) if plan.saves_x else None,
+                            noise=torch.zeros_like(latents) if any(plan.noisy) else None,
+                            x_in=torch.empty(((2 if cfg else 1) * bsz,) + tuple(latents.shape[1:]), dtype=torch.float32, device=device))
+                x_in = bufs["x_in"]
+                torch.mul(latents, plan.k_in, out=x_in[:bsz])
+                if cfg:
+                    x_in[bsz:].copy_(x_in[:bsz])
+                state = [latents] + [bufs[k] for k in ("hist", "saved", "x_in") if bufs[k] is not None]
 
-            def one_step():
-                self._fused_update(self._model_step(latents, t_buf, s), latents, coef, cfg)
+                def one_step():
+                    self._sampler_update(self._model_step(latents, t_buf, s, x_in=x_in), latents, row, bufs, cfg)
+            else:                        # DDIM rows {g, 1, 0, c_sample, 0, c_pred, c_noise, ...} -> guided_step's {g, c_sample, c_pred, c_noise}
+                table = table[:, [0, 3, 5, 6]].contiguous()
+                row = torch.empty(4, dtype=torch.float32, device=device)
+                state = [latents]
+
+                def one_step():
+                    self._fused_update(self._model_step(latents, t_buf, s), latents, row, cfg)
 
             graph = None
             for i in range(len(timesteps)):
                 t_buf.copy_(timesteps[i:i + 1])
-                coef.copy_(table[i])
+                row.copy_(table[i])
+                if plan.noisy[i]:                # outside the graph, the same draw (generator, order) as the generic step()
+                    bufs["noise"].copy_(sch._step_noise(latents.shape, torch.float32, device, generator))
                 if not use_graph:
                     one_step()
                 elif graph is None:
-                    graph = self._capture(one_step, latents)
+                    graph = self._capture(one_step, *state)
                     graph.replay()
                 else:
                     graph.replay()
@@ -262,20 +310,24 @@ class StableDiffusionE4TPipeline:
             return (images, None)
         return StableDiffusionPipelineOutput(images=images, nsfw_content_detected=None)
 
-    def _capture(self, fn, latents):
+    def _capture(self, fn, latents, *state):
         """Warm the step up on a side stream (weight copies, workspaces and allocator pools reach their steady state), restore
-        the latents, then record the step into a graph on that stream."""
-        keep = latents.clone()
+        the latents and the other buffers the step updates (`state`: history, saved sample, next UNet input), then record the
+        step into a graph on that stream."""
+        bufs = (latents,) + state
+        keep = [b.clone() for b in bufs]
         coefs_stream = torch.cuda.Stream(device=latents.device)
         coefs_stream.wait_stream(torch.cuda.current_stream(latents.device))
         with torch.cuda.stream(coefs_stream):
             fn()
-            latents.copy_(keep)
+            for b, k in zip(bufs, keep):
+                b.copy_(k)
         torch.cuda.current_stream(latents.device).wait_stream(coefs_stream)
         graph = torch.cuda.CUDAGraph()
         with ops.capture_guard(), torch.cuda.graph(graph, stream=coefs_stream):
             fn()
-        latents.copy_(keep)               # capture does not execute: the first replay starts from the same state
+        for b, k in zip(bufs, keep):      # capture does not execute: the first replay starts from the same state
+            b.copy_(k)
         return graph
 
 

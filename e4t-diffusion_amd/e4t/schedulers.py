@@ -12,6 +12,12 @@ MI355X-first detail: without sample clipping a DDIM update is linear in (sample,
 for both epsilon and v prediction.  ``coefficients(i, eta)`` exposes the three numbers so the pipeline can run guidance
 and the update as ONE kernel (``e4t_guided_step``) whose coefficients live in device memory — a captured hipGraph of the
 whole denoising step is then replayed for every timestep.
+
+The other five samplers are linear too once configured as built here (no thresholding, s_churn = 0, DPM-Solver++ of order
+<= 2, PLMS without the Runge-Kutta warm-up).  Each class's ``fused_plan(guidance_scale, eta)`` restates its own ``step`` as
+one row of ``e4t_sampler_step`` coefficients per model call (the row contract is in include/e4t_hip.h), computed on the host
+in float64 from the same quantities ``step`` uses, without touching the scheduler's state; ``None`` where the update is not
+linear.  The pipeline then runs every sampler's step as one kernel that a captured graph replays.
 """
 from __future__ import annotations
 
@@ -19,11 +25,62 @@ import json
 import math
 import os
 from dataclasses import dataclass
-from typing import Optional
+from typing import List, Optional
 
 import torch
 
 from . import ops
+
+
+@dataclass
+class FusedPlan:
+    """One call of a linear sampler as rows of ``e4t_sampler_step`` (include/e4t_hip.h), one row per model call."""
+    timesteps: torch.Tensor          # the model calls' timesteps, in the scheduler's own dtype (PLMS: n + 1 of them)
+    table: torch.Tensor              # float64 [calls, ROW]
+    K: int                           # history slots the rows address
+    k_in: float                      # UNet-input scale of the first call (scale_model_input); later ones are in the rows
+    noisy: List[bool]                # rows that take a fresh noise tensor (drawn as ``step`` draws it)
+    saves_x: bool                    # some row keeps x in the saved-x slot
+
+
+ROW = 16                             # E4T_SAMPLER_ROW
+MAX_HIST = 4                         # E4T_SAMPLER_MAX_HIST
+
+
+def _row(g, a_e=1.0, a_x=0.0, c_x=0.0, c_s=0.0, c_m=0.0, c_n=0.0, k_in=1.0, w=-1, save_x=False, hist=()):
+    """{g, a_e, a_x, c_x, c_s, c_m, c_n, k_in, w, save_x, c_hist[0..3], 0, 0}"""
+    h = list(hist) + [0.0] * (MAX_HIST - len(hist))
+    return [g, a_e, a_x, c_x, c_s, c_m, c_n, k_in, float(w), float(save_x)] + h + [0.0, 0.0]
+
+
+class _Ring:
+    """Which history slot holds which earlier per-step term (keyed by the model call that produced it): slots are reused
+    oldest first, and the kernel reads every slot before it writes the current term."""
+
+    def __init__(self, K):
+        self.K, self.slot, self.next = K, {}, 0
+
+    def coefs(self, weights):
+        """{label: coefficient} of earlier terms -> the K c_hist entries"""
+        out = [0.0] * self.K
+        for label, c in weights.items():
+            out[self.slot[label]] += c
+        return out
+
+    def write(self, label):
+        if self.K == 0:
+            return -1
+        w = self.next
+        self.slot = {k: v for k, v in self.slot.items() if v != w}
+        self.slot[label] = w
+        self.next = (w + 1) % self.K
+        return w
+
+
+def _plan(timesteps, rows, K, k_in=1.0, noisy=None):
+    table = torch.tensor(rows, dtype=torch.float64).reshape(len(rows), ROW)
+    return FusedPlan(timesteps=timesteps, table=table, K=K, k_in=k_in, noisy=list(noisy or [False] * len(rows)),
+                     saves_x=bool((table[:, 9] != 0).any()))
 
 
 @dataclass
@@ -104,6 +161,21 @@ class DDIMScheduler:
             return sap / sa, d - sap * sb / sa, std
         return sap * sa + d * sb, d * sa - sap * sb, std
 
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0) -> Optional[FusedPlan]:
+        """step() of every timestep as e4t_sampler_step rows: x' = c_sample*x + c_pred*e (+ c_noise*noise when eta > 0)"""
+        if self.num_inference_steps is None or self.config["clip_sample"] or self.config["prediction_type"] == "sample":
+            return None
+        rows = []
+        for t in self.timesteps.tolist():
+            cs, cp, cn = self.coefficients(t, eta)
+            rows.append(_row(guidance_scale, c_x=cs, c_m=cp, c_n=cn if eta > 0 else 0.0))
+        return _plan(self.timesteps, rows, K=0, noisy=[eta > 0] * len(rows))
+
+    @staticmethod
+    def _step_noise(shape, dtype, device, generator):
+        """the variance noise step() draws when eta > 0"""
+        return torch.randn(shape, generator=generator, device=device, dtype=dtype)
+
     def step(self, model_output, timestep, sample, eta: float = 0.0, use_clipped_model_output: bool = False, generator=None,
              variance_noise=None, return_dict: bool = True):
         if self.num_inference_steps is None:
@@ -111,7 +183,7 @@ class DDIMScheduler:
         t = int(timestep)
         a_t, a_prev = self._alphas(t)
         if eta > 0 and variance_noise is None:
-            variance_noise = torch.randn(model_output.shape, generator=generator, device=model_output.device, dtype=model_output.dtype)
+            variance_noise = self._step_noise(model_output.shape, model_output.dtype, model_output.device, generator)
         linear = not self.config["clip_sample"] and self.config["prediction_type"] != "sample" and not use_clipped_model_output
         if linear and sample.dtype == torch.float32 and model_output.dtype == torch.float32:
             cs, cp, cn = self.coefficients(t, eta)
@@ -156,9 +228,9 @@ class DDIMScheduler:
 
 # ----------------------------------------------------------------------------------------------------------------------
 # The other five samplers of inference.py:60-67, restated from diffusers 0.14 (same defaults as the Stable Diffusion
-# scheduler configs).  They run through the pipeline's generic path (scale_model_input / step(...).prev_sample, elementwise
-# torch ops on the (B,4,h,w) latents — a few microseconds per step next to the UNet); only DDIM has the fused, graph-replayed
-# update.  Parity unpinned (diffusers is not installed): tests/test_schedulers.py checks each of them against the closed-form
+# scheduler configs).  ``step`` is the generic path (scale_model_input / step(...).prev_sample, elementwise torch ops on the
+# (B,4,h,w) latents: the CPU path and the reference of the fused loop); ``fused_plan`` restates it as e4t_sampler_step rows,
+# which the pipeline runs as one kernel per step inside the replayed graph.  Parity unpinned (diffusers is not installed): tests/test_schedulers.py checks each of them against the closed-form
 # probability-flow solution of a Gaussian toy problem.
 # ----------------------------------------------------------------------------------------------------------------------
 @dataclass
@@ -235,6 +307,31 @@ class _SigmaBase(_Base):
         s = float(self.sigmas[self._index(timestep)])
         return sample / ((s * s + 1) ** 0.5)
 
+    def _d_coefs(self, s):
+        """(a_e, a_x) of the derivative d = (sample - x0) / s that step() forms from _x0; None if not linear"""
+        pt = self.config["prediction_type"]
+        if pt == "epsilon":
+            return 1.0, 0.0
+        if pt == "v_prediction":
+            return 1.0 / (s * s + 1) ** 0.5, s / (s * s + 1)
+        return None
+
+    def _sigma_plan(self, guidance_scale, update, K=0, noisy=False):
+        """rows of a sigma sampler: update(i, s, s_next, ring) -> row keywords of call i (c_x, c_m, ...); the next call's
+        scale_model_input factor goes into every row, the first call's into the plan"""
+        if self.num_inference_steps is None or self._d_coefs(1.0) is None:
+            return None
+        sig = self.sigmas.tolist()
+        n = len(self.timesteps)
+        k_in = [1.0 / (sig[i] * sig[i] + 1) ** 0.5 for i in range(n)] + [1.0]
+        ring, rows = _Ring(K), []
+        for i in range(n):
+            s, s_next = sig[i], sig[i + 1]
+            a_e, a_x = self._d_coefs(s)
+            kw = update(i, s, s_next, ring)
+            rows.append(_row(guidance_scale, a_e=a_e, a_x=a_x, c_x=1.0, k_in=k_in[i + 1], w=ring.write(i), **kw))
+        return _plan(self.timesteps, rows, K=K, k_in=k_in[0], noisy=[noisy] * n)
+
     def _x0(self, model_output, sample, s):
         pt = self.config["prediction_type"]
         if pt == "epsilon":
@@ -245,6 +342,10 @@ class _SigmaBase(_Base):
 
 
 class EulerDiscreteScheduler(_SigmaBase):
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0) -> Optional[FusedPlan]:
+        """x' = x + (s_next - s) * d"""
+        return self._sigma_plan(guidance_scale, lambda i, s, s_next, ring: dict(c_m=s_next - s))
+
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         i = self._index(timestep)
         s, s_next = float(self.sigmas[i]), float(self.sigmas[i + 1])
@@ -254,15 +355,31 @@ class EulerDiscreteScheduler(_SigmaBase):
 
 
 class EulerAncestralDiscreteScheduler(_SigmaBase):
+    @staticmethod
+    def _sigmas_up_down(s, s_to):
+        s_up = (s_to ** 2 * (s ** 2 - s_to ** 2) / s ** 2) ** 0.5
+        return s_up, (s_to ** 2 - s_up ** 2) ** 0.5
+
+    @staticmethod
+    def _step_noise(shape, dtype, device, generator):
+        """the noise step() draws (on the generator's device)"""
+        gdev = generator.device if generator is not None else device
+        return torch.randn(shape, dtype=dtype, device=gdev, generator=generator).to(device)
+
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0) -> Optional[FusedPlan]:
+        """x' = x + (s_down - s) * d + s_up * noise"""
+        def update(i, s, s_to, ring):
+            s_up, s_down = self._sigmas_up_down(s, s_to)
+            return dict(c_m=s_down - s, c_n=s_up)
+        return self._sigma_plan(guidance_scale, update, noisy=True)
+
     def step(self, model_output, timestep, sample, generator=None, return_dict=True):
         i = self._index(timestep)
         s, s_to = float(self.sigmas[i]), float(self.sigmas[i + 1])
         x0 = self._x0(model_output, sample, s)
-        s_up = (s_to ** 2 * (s ** 2 - s_to ** 2) / s ** 2) ** 0.5
-        s_down = (s_to ** 2 - s_up ** 2) ** 0.5
+        s_up, s_down = self._sigmas_up_down(s, s_to)
         prev = sample + (sample - x0) / s * (s_down - s)
-        gdev = generator.device if generator is not None else model_output.device
-        noise = torch.randn(model_output.shape, dtype=model_output.dtype, device=gdev, generator=generator).to(model_output.device)
+        noise = self._step_noise(model_output.shape, model_output.dtype, model_output.device, generator)
         prev = prev + noise * s_up
         return SchedulerOutput(prev, x0) if return_dict else (prev,)
 
@@ -283,6 +400,16 @@ class LMSDiscreteScheduler(_SigmaBase):
                 prod *= (tau - sig[t - k]) / (sig[t - current_order] - sig[t - k])
             return prod
         return integrate.quad(lms_derivative, sig[t], sig[t + 1], epsrel=1e-4)[0]
+
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0, order: int = 4) -> Optional[FusedPlan]:
+        """x' = x + sum_j coeff_j * d_(i-j), j < min(i + 1, order): the current derivative and up to order - 1 earlier ones"""
+        def update(i, s, s_next, ring):
+            o = min(i + 1, order)
+            coeffs = [self.get_lms_coefficient(o, i, c) for c in range(o)]
+            return dict(c_m=coeffs[0], hist=ring.coefs({i - j: coeffs[j] for j in range(1, o)}))
+        if self.num_inference_steps is None:
+            return None
+        return self._sigma_plan(guidance_scale, update, K=min(order - 1, len(self.timesteps) - 1))
 
     def step(self, model_output, timestep, sample, order: int = 4, return_dict=True):
         i = self._index(timestep)
@@ -319,6 +446,45 @@ class PNDMScheduler(_Base):
         plms = (ts[:-1] + ts[-2:-1] + ts[-1:])[::-1]
         self.timesteps = torch.tensor(plms, dtype=torch.int64, device=device)
         self.ets, self.counter, self.cur_sample = [], 0, None
+
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0) -> Optional[FusedPlan]:
+        """step()'s bookkeeping replayed on labels: the eps history holds the outputs of every model call but the second; the
+        second call restarts from the saved first sample with the mean of its own and the first output"""
+        pt = self.config["prediction_type"]
+        if self.num_inference_steps is None or pt == "sample":
+            return None
+        ratio = self.config["num_train_timesteps"] // self.num_inference_steps
+        ts = self.timesteps.tolist()
+        ring, ets, rows = _Ring(min(3, len(ts) - 1)), [], []
+        for c, t in enumerate(ts):
+            prev_t = t - ratio
+            if c != 1:
+                ets = ets[-3:] + [c]
+            else:
+                prev_t, t = t, t + ratio
+            if len(ets) == 1 and c == 1:
+                wts = {"cur": 0.5, ets[-1]: 0.5}
+            elif len(ets) == 1:
+                wts = {ets[-1]: 1.0}
+            elif len(ets) == 2:
+                wts = {ets[-1]: 1.5, ets[-2]: -0.5}
+            elif len(ets) == 3:
+                wts = {ets[-1]: 23 / 12, ets[-2]: -16 / 12, ets[-3]: 5 / 12}
+            else:
+                wts = {ets[-1]: 55 / 24, ets[-2]: -59 / 24, ets[-3]: 37 / 24, ets[-4]: -9 / 24}
+            a_t = self._acp[t]
+            a_prev = self._acp[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+            b_t, b_prev = 1 - a_t, 1 - a_prev
+            denom = a_t * b_prev ** 0.5 + (a_t * b_t * a_prev) ** 0.5
+            c_smp, c_mo = (a_prev / a_t) ** 0.5, -(a_prev - a_t) / denom          # prev = c_smp * sample + c_mo * model_output
+            if pt == "v_prediction":                                             # model_output -> sqrt(a_t) mo + sqrt(b_t) sample
+                c_smp, c_mo = c_smp + c_mo * b_t ** 0.5, c_mo * a_t ** 0.5
+            cur = wts.pop("cur", 0.0) + wts.pop(c, 0.0)
+            kw = dict(c_s=c_smp) if c == 1 else dict(c_x=c_smp)                 # the second call steps from the saved sample
+            hist = ring.coefs({k: c_mo * v for k, v in wts.items()})
+            rows.append(_row(guidance_scale, c_m=c_mo * cur, hist=hist, save_x=(c == 0 and len(ts) > 1),
+                             w=ring.write(c) if c != 1 else -1, **kw))
+        return _plan(self.timesteps, rows, K=ring.K)
 
     def step(self, model_output, timestep, sample, return_dict=True):
         t = int(timestep)
@@ -371,6 +537,32 @@ class DPMSolverMultistepScheduler(_Base):
         ts = np.linspace(0, T - 1, num_inference_steps + 1).round()[::-1][:-1].copy().astype(np.int64)
         self.timesteps = torch.from_numpy(ts).to(device)
         self.model_outputs, self.lower_order_nums, self._prev_ts = [], 0, []
+
+    def fused_plan(self, guidance_scale: float = 1.0, eta: float = 0.0) -> Optional[FusedPlan]:
+        """m = x0 (data prediction); x' = (sigma_prev / sigma_t) x - c x0 [- c / (2 r0) (x0 - x0_prev) at second order]"""
+        pt = self.config["prediction_type"]
+        if self.num_inference_steps is None or pt == "sample":
+            return None
+        ts = self.timesteps.tolist()
+        if len(set(ts)) != len(ts):
+            return None
+        lam, al, sg = self.lambda_t, self.alpha_t, self.sigma_t
+        ring, rows, lower = _Ring(min(1, len(ts) - 1)), [], 0
+        for i, t in enumerate(ts):
+            prev_t = 0 if i == len(ts) - 1 else ts[i + 1]
+            final = i == len(ts) - 1 and self.config["lower_order_final"] and len(ts) < 15
+            a, s = float(al[t]), float(sg[t])
+            a_e, a_x = (-s / a, 1.0 / a) if pt == "epsilon" else (-s, a)
+            h = float(lam[prev_t] - lam[t])
+            c = float(al[prev_t]) * (math.exp(-h) - 1.0)
+            c_m, hist = -c, {}
+            if not (self.config["solver_order"] == 1 or lower < 1 or final):
+                k = 0.5 * c * (1.0 / (float(lam[t] - lam[ts[i - 1]]) / h))
+                c_m, hist = c_m - k, {i - 1: k}
+            rows.append(_row(guidance_scale, a_e=a_e, a_x=a_x, c_x=float(sg[prev_t] / sg[t]), c_m=c_m, hist=ring.coefs(hist),
+                             w=ring.write(i)))
+            lower = min(lower + 1, self.config["solver_order"])
+        return _plan(self.timesteps, rows, K=ring.K)
 
     def _x0(self, model_output, t, sample):
         a, s = float(self.alpha_t[t]), float(self.sigma_t[t])

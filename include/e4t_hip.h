@@ -267,6 +267,23 @@ int e4t_clip_preprocess(const float* pixels_nchw, void* patches /* bf16 [B*g*g][
  * pred_nhwc = 1: pred is [B(*2)][HW][C] (the UNet's native output); sample/noise/out are [B][C][HW] fp32. */
 int e4t_guided_step(const float* pred, const float* sample, const float* noise, float* out, const float* coef,
                     int B, int C, int HW, int cfg, int pred_nhwc, e4t_stream stream);
+/* Sampling loop glue for every linear sampler (pipeline_stable_diffusion_e4t.py:209-214: guidance + scheduler.step):
+ * DDIM, PLMS, LMS, Euler, Euler-ancestral and DPM-Solver++ 2M are, once configured, linear in the current latent, the
+ * guided model output, a few earlier per-step terms and one noise tensor.  With n = B*C*HW, per element:
+ *   e     = cfg ? u + g*(c - u) : p                 pred = [u | c] (cfg = 1) or p, NHWC ([B(*2)][HW][C]) when pred_nhwc
+ *   m     = a_e*e + a_x*x                           the sampler's own variable: eps, v, x0 or the k-diffusion derivative
+ *   out   = c_x*x + c_m*m + c_s*saved + sum_{k<K} c_hist[k]*hist[k] + c_n*noise
+ *   hist[w] = m   (0 <= w < K; w = -1: none)         saved = x when save_x    (both after all reads: out may alias x)
+ *   x_in  = k_in*out, written x_in_copies (0..2) times back to back ([x_in | x_in] = the UNet's CFG batch)
+ * row: DEVICE float[16] (so a captured graph replays with new values) =
+ *   {g, a_e, a_x, c_x, c_s, c_m, c_n, k_in, w, save_x, c_hist[0..3], 0, 0}.
+ * x, out, saved, noise, x_in and each of the K slots of hist ([K][n]) are [B][C][HW] fp32.  saved / noise may be NULL (their
+ * terms are dropped); terms whose coefficient is 0 are not read.  A DDIM row {g, 1, 0, c_sample, 0, c_pred, c_noise, ...}
+ * computes exactly what e4t_guided_step computes with {g, c_sample, c_pred, c_noise}, bit for bit. */
+#define E4T_SAMPLER_MAX_HIST 4
+#define E4T_SAMPLER_ROW 16
+int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
+                     const float* row, int B, int C, int HW, int K, int cfg, int pred_nhwc, int x_in_copies, e4t_stream stream);
 /* Data path (pretrain_e4t.py:137-144 make_transforms = SmallestMaxSize(interpolation=3: cv2.INTER_AREA) -> RandomCrop ->
  * HorizontalFlip, and :174-177 image/127.5-1, HWC->CHW): a batch of raw decoded uint8 RGB images in one device pool ->
  * out fp32 [B][3][S][S].  table: int64 [B][8] (device) = {byte offset of the image in pool, H, W, newH, newW (the

@@ -1,15 +1,23 @@
-"""Generation throughput of the E4T pipeline on one MI355X (SD-1.4 shapes, 512 px, DDIM, CFG 7.5): eager launch loop vs
-hipGraph replay of the denoising step, plus the VAE decode.  Random-init weights, word-level stand-in tokenizer."""
-import os, sys, time
+"""Generation throughput of the E4T pipeline on one MI355X (SD-1.4 shapes, 512 px, CFG 7.5): per sampler, the generic
+scale_model_input / step loop vs the fused e4t_sampler_step loop run eagerly vs its hipGraph replay, at 1 and 4 images per
+call, plus the VAE decode.  Random-init weights, word-level stand-in tokenizer.
+
+    python tools/bench_inference.py --scheduler ddim dpm_solver++ euler_ancestral plms      (STEPS=50 by default)"""
+import argparse, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (os.path.join(ROOT, "e4t-diffusion_amd"), ROOT, os.path.join(ROOT, "tests")):
     sys.path.insert(0, p)
 from bench import build_models
 from e4t.pipeline_stable_diffusion_e4t import StableDiffusionE4TPipeline
-from e4t.schedulers import DDIMScheduler
+from e4t.schedulers import SCHEDULER_MAPPING, DDIMScheduler
 from e4t.vae import VAEDecoder
 from word_tokenizer import WordTokenizer
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--scheduler", nargs="+", default=["ddim"], choices=sorted(SCHEDULER_MAPPING))
+ap.add_argument("--images", nargs="+", type=int, default=[1, 4])
+args = ap.parse_args()
 
 dev = torch.device("cuda:0")
 steps = int(os.environ.get("STEPS", "50"))
@@ -21,14 +29,20 @@ tok = WordTokenizer(base_size=49408, model_max_length=77)
 pipe = StableDiffusionE4TPipeline(vae=vae, text_encoder=text, tokenizer=tok, unet=unet, e4t_encoder=enc, scheduler=DDIMScheduler.stable_diffusion(),
                                   e4t_config=dict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1), already_added_placeholder_token=False)
 image = torch.rand(1, 3, 512, 512) * 2 - 1
-for n in (1, 4):
-    for graph in (False, True):
-        kw = dict(num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=n, image=image, output_type="np", use_graph=graph)
-        pipe("a painting of *s", **dict(kw, num_inference_steps=2))
-        torch.cuda.synchronize(); t0 = time.perf_counter()
-        out = pipe("a painting of *s", **kw).images
-        torch.cuda.synchronize(); dt = time.perf_counter() - t0
-        print(f"images/call={n} graph={graph}: {dt:.2f} s for {steps} steps ({dt/steps*1e3:.1f} ms/step incl. capture+decode) -> {n/dt:.2f} img/s; out {out.shape}", flush=True)
+for name in args.scheduler:
+    pipe.scheduler = SCHEDULER_MAPPING[name].stable_diffusion()
+    for n in args.images:
+        for leg, fused, graph in (("generic", False, False), ("fused eager", True, False), ("graph", True, True)):
+            pipe._fused_sampling = fused
+            kw = dict(num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=n, image=image, output_type="np", use_graph=graph)
+            pipe("a painting of *s", **dict(kw, num_inference_steps=2))
+            torch.cuda.synchronize(); t0 = time.perf_counter()
+            out = pipe("a painting of *s", **kw).images
+            torch.cuda.synchronize(); dt = time.perf_counter() - t0
+            calls = len(pipe.scheduler.timesteps)
+            print(f"{name} images/call={n} {leg}: {dt:.2f} s for {calls} model calls ({dt/calls*1e3:.1f} ms/step incl. capture+decode) "
+                  f"-> {n/dt:.2f} img/s; out {out.shape}", flush=True)
+    pipe._fused_sampling = True
 z = torch.randn(4, 4, 64, 64, device=dev) * 0.18215
 vae.decode_latents(z); torch.cuda.synchronize(); t0 = time.perf_counter()
 for _ in range(5):
