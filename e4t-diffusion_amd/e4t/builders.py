@@ -24,22 +24,33 @@ TEXT_CONFIGS["tiny-test"] = dict(vocab_size=100, hidden_size=64, num_layers=2, n
 RESOLUTION["tiny-test"] = 64
 
 
+def clip_arch(model):
+    """the E4T encoder's CLIP tower for `model`: the toy shape for tiny-test, the reference's ViT-H-14 otherwise"""
+    return "ViT-tiny-test" if model == "tiny-test" else "ViT-H-14"
+
+
 def build_models(dev, model="sd14", seed=0, vocab_size=None, freeze_clip_vision=True):
     """(unet, e4t_encoder, text_encoder, vae_encoder) of `model` on `dev`, random init from `seed`.  `vocab_size`: rows of the
     token-embedding table (the checkpoint's 49408 + the placeholder token the scripts add, pretrain_e4t.py:254-259)."""
+    tcfg = dict(TEXT_CONFIGS[model])
+    if vocab_size is not None:
+        tcfg["vocab_size"] = vocab_size
+    vcfg = dict(block_out_channels=(64, 64)) if model == "tiny-test" else {}
+    return build_from_configs(dev, UNET_CONFIGS[model], tcfg, vcfg, clip_arch(model), seed, freeze_clip_vision=freeze_clip_vision)
+
+
+def build_from_configs(dev, unet_cfg, text_cfg, vae_cfg, arch="ViT-H-14", seed=0, freeze_clip_vision=True):
+    """(unet, e4t_encoder, text_encoder, vae_encoder) on `dev` from explicit constructor kwargs (a checkpoint's configs,
+    e4t/checkpoints.py::pipeline_configs), random init from `seed`; `arch` is the E4T encoder's CLIP tower."""
     from .encoder import E4TEncoder
     from .models.unet_2d_condition import UNet2DConditionModel
     from .text import CLIPTextModel
     from .vae import VAEEncoder
     torch.manual_seed(seed)
-    ucfg, tcfg = UNET_CONFIGS[model], dict(TEXT_CONFIGS[model])
-    if vocab_size is not None:
-        tcfg["vocab_size"] = vocab_size
     with torch.device(dev):
-        unet = UNet2DConditionModel(**ucfg)
-        tiny = model == "tiny-test"
-        enc = E4TEncoder(word_embedding_dim=tcfg["hidden_size"], block_out_channels=ucfg["block_out_channels"],
-                         arch="ViT-tiny-test" if tiny else "ViT-H-14", freeze_clip_vision=freeze_clip_vision, **(dict(n_odd_layers=3) if tiny else {}))
-        text = CLIPTextModel(**tcfg).requires_grad_(False)      # fp32 master weights; bf16 compute copies are made once
-        vae = VAEEncoder(**(dict(block_out_channels=(64, 64)) if tiny else {})).requires_grad_(False)
+        unet = UNet2DConditionModel(**unet_cfg)
+        enc = E4TEncoder(word_embedding_dim=text_cfg["hidden_size"], block_out_channels=unet_cfg["block_out_channels"], arch=arch,
+                         freeze_clip_vision=freeze_clip_vision, **(dict(n_odd_layers=3) if arch == "ViT-tiny-test" else {}))
+        text = CLIPTextModel(**text_cfg).requires_grad_(False)      # fp32 master weights; bf16 compute copies are made once
+        vae = VAEEncoder(**vae_cfg).requires_grad_(False)
     return unet, enc, text, vae

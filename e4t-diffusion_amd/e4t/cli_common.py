@@ -4,16 +4,25 @@ templates, base-model loading — restated once so the three scripts condition t
 conditioned on tokenizer("") and the class token in training AND in sampling; getting one of them different in one script
 silently trains a model the pipeline cannot use).  No tensor arithmetic lives here.
 
-There is no network in this build: "pretrained_model_name_or_path" is a LOCAL directory laid out as
-    <dir>/unet.pt  vae.pt  text_encoder.pt        plain state dicts with the diffusers / transformers key names
-    <dir>/unet_config.json                        optional (defaults to the --unet_variant architecture)
+There is no network in this build: "pretrained_model_name_or_path" is a local directory, or a hub id (`org/name`,
+`--revision`) whose snapshot is in the local Hugging Face cache (e4t/checkpoints.py reads the cache's files; nothing is
+downloaded).  Two layouts:
+  the diffusers pipeline layout of published checkpoints (model_index.json; the components' config.json decide the architecture)
+    <dir>/unet/  vae/  text_encoder/              config.json + *.safetensors | *.bin (sharded or not, fp16 variant too)
     <dir>/tokenizer/                              CLIPTokenizer files
     <dir>/scheduler/scheduler_config.json         optional
+  the flat layout (the --unet_variant architecture)
+    <dir>/unet.pt  vae.pt  text_encoder.pt        plain state dicts with the diffusers / transformers key names
+    <dir>/tokenizer/                              CLIPTokenizer files
+    <dir>/scheduler/scheduler_config.json         optional
+The E4T encoder's CLIP tower comes from --clip_model_name_or_path 'arch::version' (an open_clip weight file, or a pretrained
+tag found in the local cache) unless an E4T run's encoder.pt is resumed; 'none' keeps it randomly initialised.
 """
 from __future__ import annotations
 
 import os
 import random
+import sys
 from typing import List, Optional, Sequence
 
 import torch
@@ -105,26 +114,95 @@ def tokenize_prompts(tokenizer, prompt_templates: Sequence[str], placeholder_tok
 def checked_load(module: torch.nn.Module, path: str, may_miss=lambda k: False, what: str = ""):
     """load_state_dict that fails loudly: unexpected keys always raise, missing keys raise unless `may_miss(key)` (the reference's
     load_e4t_unet / load_e4t_encoder contract, e4t/utils.py:119-124,150-154).  A shape mismatch raises inside torch."""
-    sd = torch.load(path, map_location="cpu")
+    return checked_load_state_dict(module, torch.load(path, map_location="cpu"), may_miss, what or path)
+
+
+def checked_load_state_dict(module: torch.nn.Module, sd: dict, may_miss=lambda k: False, what: str = ""):
+    """checked_load of a state dict already read (e4t/checkpoints.py).  The parameters are written in place; every prepared
+    compute copy of the modules (bf16 GEMM operands, fused q|k|v, the VAE's and the weight-offset banks' caches) is keyed on
+    the parameters' versions and is re-made at the next forward."""
     # transformers < 4.31 saved the (persistent, integer) buffer `*.embeddings.position_ids` with every CLIP state dict; it is an
     # arange, not a weight, and the module trees here do not carry it: drop it, keep the strict check for every other key
     sd = {k: v for k, v in sd.items() if not k.endswith(".position_ids")}
     missing, unexpected = module.load_state_dict(sd, strict=False)
     missing = [k for k in missing if not may_miss(k)]
     if missing or unexpected:
-        raise RuntimeError(f"{what or path}: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''} "
+        raise RuntimeError(f"{what}: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''} "
                            f"unexpected keys {list(unexpected)[:5]}{'...' if len(unexpected) > 5 else ''}")
     return module
 
 
+def resolve_base(base: Optional[str], revision: Optional[str] = None) -> Optional[str]:
+    """--pretrained_model_name_or_path -> a local directory: an existing path as it is, a hub id from the local Hugging Face
+    cache; None stays None.  Raises checkpoints.CheckpointNotFoundError (listing the paths tried) otherwise."""
+    from .checkpoints import resolve_model_dir
+    return resolve_model_dir(base, revision) if base else base
+
+
+def load_pipeline_weights(base_dir: str, unet=None, text=None, vae=None, vae_decoder=None):
+    """The components of a diffusers pipeline directory into built native modules, strictly (a stock UNet has no "wo" keys).
+    The VAE file holds both halves of the AutoencoderKL: `vae` takes the encoder half, `vae_decoder` the decoder half."""
+    from . import checkpoints as ck
+    for sub, mod, may_miss in (("unet", unet, lambda k: "wo" in k), ("text_encoder", text, lambda k: False)):
+        if mod is not None:
+            d = os.path.join(base_dir, sub)
+            checked_load_state_dict(mod, ck.read_state_dict(d), may_miss, what=d)
+    if vae is not None or vae_decoder is not None:
+        d = os.path.join(base_dir, "vae")
+        sd = ck.normalize_vae_keys(ck.read_state_dict(d))
+        for mod, prefixes in ((vae, ("encoder.", "quant_conv.")), (vae_decoder, ("decoder.", "post_quant_conv."))):
+            if mod is not None:
+                checked_load_state_dict(mod, {k: v for k, v in sd.items() if k.startswith(prefixes)}, what=d)
+
+
+def pipeline_vae_decoder(dev, base_dir: str):
+    """The AutoencoderKL decoder of a diffusers pipeline directory (its vae/config.json decides the shape), for sampling."""
+    from . import checkpoints as ck
+    from .vae import VAEDecoder
+    with torch.device(dev):
+        dec = VAEDecoder(**ck.pipeline_configs(base_dir)["vae"]).requires_grad_(False)
+    load_pipeline_weights(base_dir, vae_decoder=dec)
+    return dec
+
+
+def load_clip_tower(enc, clip_source: str) -> str:
+    """--clip_model_name_or_path 'arch::version' -> enc.clip_vision, strictly.  Returns the file read; raises
+    checkpoints.CheckpointNotFoundError when the source names nothing on this machine."""
+    from . import checkpoints as ck
+    arch, path = ck.resolve_clip_file(clip_source)
+    if arch != enc.config.arch:
+        raise ValueError(f"--clip_model_name_or_path {clip_source!r} is a {arch} tower; the E4T encoder was built with {enc.config.arch}")
+    sd = ck.read_openclip_visual(arch, path)
+    enc.clip_vision.load_state_dict({k[len("clip_vision."):]: v for k, v in sd.items()}, strict=True)
+    print(f"[e4t] CLIP tower {arch} loaded from {path}")
+    return path
+
+
 def build_models(dev, base_dir: Optional[str], variant: str, seed: int, freeze_clip_vision: bool = True, e4t_dir: Optional[str] = None,
-                 need_vae_encoder: bool = True):
+                 need_vae_encoder: bool = True, clip_source: Optional[str] = None, revision: Optional[str] = None):
     """(unet, e4t_encoder, text_encoder, vae_encoder) on `dev` (pretrain_e4t.py:233-251, tuning_e4t.py:97-118).
-    base_dir: local Stable Diffusion checkpoint directory (see the module docstring) or None = random init from `seed`.
+    base_dir: Stable Diffusion checkpoint in either layout of the module docstring (a hub id is looked up in the local cache at
+    `revision`) or None = random init from `seed`.  The pipeline layout's configs decide the architecture; otherwise `variant` does.
+    clip_source: --clip_model_name_or_path for the E4T encoder's CLIP tower; None = not requested, 'none' = random init.  It is
+    not read when e4t_dir holds an encoder.pt (that wins).  If it names nothing on this machine, a pipeline-layout base exits
+    listing the paths searched, a flat-layout base warns and keeps the random tower, and a random base keeps it.
     e4t_dir: directory with weight_offsets.pt | unet.pt and encoder.pt of an earlier E4T run, loaded on top (both strict)."""
     from . import builders
-    unet, enc, text, vae = builders.build_models(dev, variant, seed, freeze_clip_vision=freeze_clip_vision)
-    if base_dir:
+    from . import checkpoints as ck
+    if base_dir and not os.path.exists(base_dir):
+        base_dir = ck.resolve_model_dir(base_dir, revision)
+    pipeline = ck.is_pipeline_layout(base_dir)
+    want_clip = bool(clip_source) and clip_source.lower() != "none"
+    if pipeline:
+        cfgs = ck.pipeline_configs(base_dir)
+        arch = ck.parse_clip_source(clip_source)[0] if want_clip else builders.clip_arch(variant)
+        unet, enc, text, vae = builders.build_from_configs(dev, cfgs["unet"], cfgs["text"], cfgs["vae"], arch, seed,
+                                                           freeze_clip_vision=freeze_clip_vision)
+        print(f"[e4t] architecture from {base_dir}: {ck.describe(cfgs)}; CLIP tower {arch}")
+        load_pipeline_weights(base_dir, unet=unet, text=text, vae=vae)
+    else:
+        unet, enc, text, vae = builders.build_models(dev, variant, seed, freeze_clip_vision=freeze_clip_vision)
+    if base_dir and not pipeline:
         if not os.path.isdir(base_dir):
             raise FileNotFoundError(f"{base_dir}: only local checkpoint directories are supported (no hub access in this build)")
         found = 0
@@ -141,6 +219,17 @@ def build_models(dev, base_dir: Optional[str], variant: str, seed: int, freeze_c
                 found += 1
         if found == 0:
             raise FileNotFoundError(f"{base_dir} holds none of unet.pt / vae.pt / text_encoder.pt")
+    if want_clip and not (e4t_dir and os.path.exists(os.path.join(e4t_dir, "encoder.pt"))):
+        try:
+            load_clip_tower(enc, clip_source)
+        except ck.CheckpointNotFoundError as ex:
+            if pipeline:
+                raise SystemExit(f"{ex}\nThe E4T encoder's CLIP tower needs these weights next to a pretrained base model; "
+                                 f"--clip_model_name_or_path none starts it from random init instead.")
+            if base_dir:
+                print(f"[e4t] WARNING: {ex}: the E4T encoder's CLIP tower stays randomly initialised", file=sys.stderr)
+            else:
+                print(f"[e4t] {ex}: randomly initialised CLIP tower (random base model)")
     if e4t_dir:
         for fn in ("weight_offsets.pt", "unet.pt"):
             f = os.path.join(e4t_dir, fn)

@@ -182,7 +182,8 @@ class UNet2DConditionModel(nn.Module):
         lins = [r.time_emb_proj for r in self._resblocks]
         if any(l is None or l.weight.requires_grad or l.bias is None or l.bias.requires_grad for l in lins):
             return None
-        key = (tuple(l.weight.data_ptr() for l in lins), temb_act.dtype, temb_act.device)
+        # the versions: a checkpoint load writes the frozen weights in place (same storage), and the concatenation must follow
+        key = (tuple((l.weight.data_ptr(), l.weight._version, l.bias._version) for l in lins), temb_act.dtype, temb_act.device)
         if self._temb_cat is None or self._temb_cat[0] != key:
             w = torch.cat([l.weight.detach() for l in lins], dim=0).to(temb_act.dtype).contiguous()      # [sum Cout, temb]
             b = torch.cat([l.bias.detach().float() for l in lins], dim=0).contiguous()

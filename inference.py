@@ -2,9 +2,10 @@
 
     python inference.py --pretrained_model_name_or_path <dir> --image_path_or_url in.png --prompt "a photo of *s"
 
-<dir> is a directory written by pretrain_e4t.py / tuning_e4t.py (config.json, weight_offsets.pt | unet.pt, encoder.pt,
-optionally text_encoder.pt); the base Stable Diffusion weights are read from the directory named in its config
-(state dicts unet.pt / vae.pt / text_encoder.pt and a tokenizer/ folder) — there is no hub access here.  With
+<dir> is a directory written by pretrain_e4t.py / tuning_e4t.py or the reference's scripts (config.json, weight_offsets.pt |
+unet.pt, encoder.pt, optionally text_encoder.pt); the base Stable Diffusion weights are read from the checkpoint named in its
+config: a local directory or a hub id whose snapshot is in the local Hugging Face cache, in the diffusers pipeline layout or as
+state dicts unet.pt / vae.pt / text_encoder.pt, with a tokenizer/ folder (e4t/cli_common.py) — there is no hub access here.  With
 --random_init everything is randomly initialised and an offline whitespace tokenizer is used (smoke runs, benchmarks).
 All six samplers of the reference are available; DDIM additionally has the fused, graph-replayed update.
 """
@@ -48,21 +49,20 @@ def parse_args():
     return p.parse_args()
 
 
-def main():
-    args = parse_args()
-    from e4t.builders import build_models
+def setup(args, dev):
+    """Everything between the argument parser and the sampling loop (inference.py:52-101): models, base and E4T weights,
+    tokenizer, scheduler, pipeline."""
+    from e4t import builders
+    from e4t import checkpoints as ck
+    from e4t import cli_common as cc
     from e4t.cli_common import checked_load
     from e4t.pipeline_stable_diffusion_e4t import StableDiffusionE4TPipeline
     from e4t.schedulers import SCHEDULER_MAPPING
     from e4t.utils import AttributeDict, WhitespaceTokenizer, load_weight_offsets
     from e4t.vae import VAEDecoder
-    dev = torch.device("cuda:0")
-    print(f"device: {dev}")
-    unet, enc, text, _ = build_models(dev, args.unet_variant, seed=args.seed or 0)       # 49408-row token table; the pipeline adds the placeholder row
-    with torch.device(dev):
-        vae = VAEDecoder().requires_grad_(False)
     cfg = AttributeDict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1)
     tok, sched = None, SCHEDULER_MAPPING[args.scheduler_type].stable_diffusion("epsilon" if args.unet_variant == "sd14" else "v_prediction")
+    pipeline_cfgs = None
     if not args.random_init:
         d = args.pretrained_model_name_or_path
         with open(os.path.join(d, "config.json")) as f:
@@ -70,16 +70,35 @@ def main():
         e4t = AttributeDict(config.pretrained_args) if config.pretrained_args is not None else config          # inference.py:56-57
         cfg = AttributeDict(placeholder_token=e4t.placeholder_token, domain_class_token=e4t.domain_class_token,
                             domain_embed_scale=float(e4t.domain_embed_scale))
-        base = e4t.pretrained_model_name_or_path
+        base, searched = e4t.pretrained_model_name_or_path, ""
+        try:
+            base = cc.resolve_base(base, e4t.revision)          # a hub id: its snapshot in the local cache
+        except ck.CheckpointNotFoundError as ex:
+            searched = f" ({ex})"
         if not base or not os.path.isdir(base):
-            raise SystemExit(f"{d}/config.json names the base model {base!r}: a local directory with unet.pt / vae.pt / text_encoder.pt / tokenizer/ is needed")
-        # every load is strict: a misnamed key must not leave random weights behind (e4t/utils.py:119-124)
-        checked_load(unet, os.path.join(base, "unet.pt"), lambda k: "wo" in k)
-        checked_load(text, os.path.join(base, "text_encoder.pt"))
-        sd = {k: v for k, v in torch.load(os.path.join(base, "vae.pt"), map_location="cpu").items() if k.startswith(("decoder.", "post_quant_conv."))}
-        missing, unexpected = vae.load_state_dict(sd, strict=False)
-        if missing or unexpected:
-            raise RuntimeError(f"{base}/vae.pt: missing {missing[:5]} unexpected {list(unexpected)[:5]}")
+            raise SystemExit(f"{d}/config.json names the base model {base!r}: a local directory with unet.pt / vae.pt / text_encoder.pt / tokenizer/ "
+                             f"is needed{searched}")
+        if ck.is_pipeline_layout(base):
+            pipeline_cfgs = ck.pipeline_configs(base)
+    if pipeline_cfgs is not None:       # the checkpoint's configs decide the architecture; the pipeline adds the placeholder row
+        unet, enc, text, _ = builders.build_from_configs(dev, pipeline_cfgs["unet"], pipeline_cfgs["text"], pipeline_cfgs["vae"],
+                                                         builders.clip_arch(args.unet_variant), seed=args.seed or 0)
+        print(f"[e4t] architecture from {base}: {ck.describe(pipeline_cfgs)}")
+        vae = cc.pipeline_vae_decoder(dev, base)
+        cc.load_pipeline_weights(base, unet=unet, text=text)
+    else:
+        unet, enc, text, _ = builders.build_models(dev, args.unet_variant, seed=args.seed or 0)    # 49408-row token table; the pipeline adds the placeholder row
+        with torch.device(dev):
+            vae = VAEDecoder().requires_grad_(False)
+    if not args.random_init:
+        if pipeline_cfgs is None:
+            # every load is strict: a misnamed key must not leave random weights behind (e4t/utils.py:119-124)
+            checked_load(unet, os.path.join(base, "unet.pt"), lambda k: "wo" in k)
+            checked_load(text, os.path.join(base, "text_encoder.pt"))
+            sd = {k: v for k, v in torch.load(os.path.join(base, "vae.pt"), map_location="cpu").items() if k.startswith(("decoder.", "post_quant_conv."))}
+            missing, unexpected = vae.load_state_dict(sd, strict=False)
+            if missing or unexpected:
+                raise RuntimeError(f"{base}/vae.pt: missing {missing[:5]} unexpected {list(unexpected)[:5]}")
         if os.path.exists(os.path.join(d, "unet.pt")):
             checked_load(unet, os.path.join(d, "unet.pt"))
         else:
@@ -101,6 +120,14 @@ def main():
     enc.requires_grad_(False)
     if args.enable_xformers_memory_efficient_attention:
         pipe.enable_xformers_memory_efficient_attention()
+    return dict(pipe=pipe, unet=unet, enc=enc, text=text, vae=vae, tokenizer=tok, scheduler=sched, base_dir=base if not args.random_init else None)
+
+
+def main():
+    args = parse_args()
+    dev = torch.device("cuda:0")
+    print(f"device: {dev}")
+    pipe = setup(args, dev)["pipe"]
     print("loaded pipeline")
     if args.image_path_or_url:
         image = Image.open(args.image_path_or_url).convert("RGB").resize((512, 512))                           # e4t/utils.py load_image

@@ -5,9 +5,10 @@ native modules (e4t-diffusion_amd/e4t) and trainer.  One process per GPU:
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 pretrain_e4t.py --synthetic_data ...
     accelerate launch pretrain_e4t.py ...        # LOCAL_RANK / WORLD_SIZE from the launcher are honoured
 
-Without network access `--pretrained_model_name_or_path` is a LOCAL directory (e4t/cli_common.py: unet.pt / vae.pt /
-text_encoder.pt state dicts with the diffusers / transformers key names, tokenizer/); without it the weights are randomly
-initialised and an offline tokenizer stands in (--synthetic_data).  The set-up is the reference's: the placeholder token is
+Without network access `--pretrained_model_name_or_path` is a local checkpoint directory or a hub id whose snapshot is in the
+local Hugging Face cache (e4t/cli_common.py: the diffusers pipeline layout, or unet.pt / vae.pt / text_encoder.pt state dicts
+and tokenizer/), and `--clip_model_name_or_path` names the open_clip weights of the E4T encoder's CLIP tower; without a base
+model the weights are randomly initialised and an offline tokenizer stands in (--synthetic_data).  The set-up is the reference's: the placeholder token is
 added to the tokenizer and the embedding table grown by it (:253-259), the class token id comes from --domain_class_token and
 the E4T encoder pass is conditioned on tokenizer("") (:561-583), prompts are drawn from the reference's template lists.
 Artefacts keep the reference's names: `{output_dir}/{step}/config.json`, `weight_offsets.pt`, `encoder.pt` (:515-528).
@@ -29,7 +30,9 @@ import torch.distributed as dist  # noqa: E402
 def parse_args():
     p = argparse.ArgumentParser(description="E4T pre-training (MI355X-native)")
     p.add_argument("--pretrained_model_name_or_path", type=str, default=None)
-    p.add_argument("--clip_model_name_or_path", type=str, default="ViT-H-14::laion2b_s32b_b79k")
+    p.add_argument("--clip_model_name_or_path", type=str, default="ViT-H-14::laion2b_s32b_b79k",
+                   help="the E4T encoder's CLIP tower: 'arch::version', version an open_clip weight file or a pretrained tag in the "
+                        "local Hugging Face cache; 'none' = random init")
     p.add_argument("--domain_class_token", type=str, default="art")
     p.add_argument("--domain_embed_scale", type=float, default=0.1)
     p.add_argument("--placeholder_token", type=str, default="*s")
@@ -52,7 +55,8 @@ def parse_args():
     p.add_argument("--dataloader_num_workers", type=int, default=0)
     p.add_argument("--output_dir", type=str, default="e4t-model")
     p.add_argument("--seed", type=int, default=42)
-    p.add_argument("--revision", type=str, default=None, help="accepted for command-line compatibility (no hub access here)")
+    p.add_argument("--revision", type=str, default=None,
+                   help="branch, tag or commit of a hub-id --pretrained_model_name_or_path in the local Hugging Face cache (default main)")
     p.add_argument("--use_8bit_adam", action="store_true")
     p.add_argument("--mixed_precision", type=str, default="bf16", choices=["no", "fp16", "bf16"])
     p.add_argument("--enable_xformers_memory_efficient_attention", action="store_true")
@@ -119,11 +123,11 @@ def setup(args, dev, world=1, rank=0):
     with the placeholder token, class-token / empty-prompt conditioning, prompt templates, learning rate, trainer."""
     from e4t import cli_common as cc
     from e4t.trainer import E4TTrainer
-    base = args.pretrained_model_name_or_path
+    base = cc.resolve_base(args.pretrained_model_name_or_path, getattr(args, "revision", None))         # a hub id: its local snapshot
     e4t_dir = base if (base and os.path.exists(os.path.join(base, "weight_offsets.pt"))) else None      # :238-249
     # weights: a common seed on every rank (replicas must start identical: there is no DDP broadcast)
     unet, enc, text, vae = cc.build_models(dev, base, args.unet_variant, seed=args.seed or 0, freeze_clip_vision=not args.unfreeze_clip_vision,
-                                           e4t_dir=e4t_dir)
+                                           e4t_dir=e4t_dir, clip_source=getattr(args, "clip_model_name_or_path", None))
     tokenizer = cc.load_tokenizer(base, allow_offline_standin=args.synthetic_data or base is None,
                                   vocab_size=text.get_input_embeddings().weight.shape[0], max_len=text.config["max_len"])
     placeholder_token_id = cc.add_placeholder_token(tokenizer, text, args.placeholder_token)              # :253-259
@@ -144,7 +148,7 @@ def setup(args, dev, world=1, rank=0):
     def prompts(bsz):                                                                                      # :607-615
         ids, idx = cc.tokenize_prompts(tokenizer, prompt_templates, args.placeholder_token, placeholder_token_id, bsz, rng)
         return ids.to(dev), idx.to(dev)
-    return dict(unet=unet, enc=enc, text=text, vae=vae, tokenizer=tokenizer, placeholder_token_id=placeholder_token_id,
+    return dict(unet=unet, enc=enc, text=text, vae=vae, tokenizer=tokenizer, placeholder_token_id=placeholder_token_id, base_dir=base,
                 class_token_id=class_token_id, empty_ids=empty_ids, prompt_templates=prompt_templates, trainer=tr, lr=lr, prompts=prompts)
 
 
@@ -227,10 +231,15 @@ def main():
         """qualitative logging (reference pretrain_e4t.py:452-513): for every prompt x a few training images, run the E4T
         pipeline and write input-<step>.png / sample-<step>.png grids under <output_dir>/samples"""
         from PIL import Image
+        from e4t import cli_common as cc
+        from e4t.checkpoints import is_pipeline_layout
         from e4t.pipeline_stable_diffusion_e4t import StableDiffusionE4TPipeline
         from e4t.schedulers import DDIMScheduler
         from e4t.vae import VAEDecoder
         from inference import image_grid
+        if not pipe_parts and is_pipeline_layout(st["base_dir"]):
+            pipe_parts.update(tok=st["tokenizer"], dec=cc.pipeline_vae_decoder(dev, st["base_dir"]),
+                              sched=DDIMScheduler.stable_diffusion(args.prediction_type))
         if not pipe_parts:
             with torch.device(dev):
                 dec = VAEDecoder().requires_grad_(False)

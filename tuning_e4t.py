@@ -5,8 +5,8 @@ weight offsets and the E4T encoder head train (:139-147), one image expanded to 
     python tuning_e4t.py --pretrained_model_name_or_path <pretrain output dir> --train_image_path img.png --output_dir out
     python tuning_e4t.py --synthetic_data --train_batch_size 16 --max_train_steps 30 --output_dir out      # random weights
 
---pretrained_model_name_or_path is a directory written by pretrain_e4t.py: its config.json names the base Stable Diffusion
-directory, the placeholder token, the class token and the prompt template (:97,249-253); its weight_offsets.pt / encoder.pt are
+--pretrained_model_name_or_path is a directory written by pretrain_e4t.py (or the reference's): its config.json names the base
+Stable Diffusion checkpoint (a local directory, or a hub id whose snapshot is in the local Hugging Face cache), the placeholder token, the class token and the prompt template (:97,249-253); its weight_offsets.pt / encoder.pt are
 loaded strictly on top of the base weights.  The saved config carries `pretrained_args` so inference.py finds the base model.
 """
 from __future__ import annotations
@@ -81,6 +81,8 @@ def setup(args, dev):
         base = None
     else:
         raise SystemExit("--pretrained_model_name_or_path <dir written by pretrain_e4t.py> is required (or --synthetic_data)")
+    # a base named by hub id (a run directory written by the reference): its snapshot in the local cache
+    base = cc.resolve_base(base, getattr(args, "revision", None) or pretrained_args.revision)
     unet, enc, text, vae = cc.build_models(dev, base, args.unet_variant, seed=args.seed or 0, freeze_clip_vision=not args.unfreeze_clip_vision,
                                            e4t_dir=src)                                             # :99-118
     tokenizer = cc.load_tokenizer(base, allow_offline_standin=args.synthetic_data or base is None,
