@@ -20,6 +20,10 @@
 // (used for the K=11520..23040, M=1024 convs at the 8x8 level and for weight-gradient GEMMs whose
 // reduction runs over B*H*W).
 //
+// Host half (end of this file): one table, kVariants, has a row per kernel variant — tile code, tile shape, capabilities, entry points
+// and their symbol text.  plan_gemm() (hint -> automatic choice -> capability fallback -> split-K) picks a row, launch_gemm() launches
+// the row's entry and logs the row's text; e4t_gemm_plan / e4t_conv3x3_plan export the same plan.
+//
 // Reference call sites this replaces: every F.linear / nn.Linear / nn.Conv2d on the hot path —
 // e4t/models/cross_attention.py:506,516,518,534 ; e4t/models/attention.py:376,419-430 ;
 // e4t/models/transformer_2d.py:153,205,258-261 ; [3P diffusers] ResnetBlock2D/Downsample2D/Upsample2D
@@ -1249,7 +1253,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
   write_tile<64, 64, 2, 2, GENERAL>(p, *(f32x16(*)[2][2])(acc + 2), wave_stage<64, 64>(smem, wave), lane, m0 + wr * 128 + 64, n0 + wc * 64);
 }
 // may a 256 x 256 ping-pong conv launch go to gemm_pps_kernel?
-static bool conv_pps_ok(const GemmArgs& p, int batch) {
+static bool conv_pps_ok(const GemmArgs& p, int /*splitk*/, int batch) {
   static const bool on = CONV_STRIP && getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
   const bool rows = p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0);
   return on && p.mode == E4T_CONV_S1 && p.chan_major && batch == 1 && rows && p.Wout == p.Win && p.Hout == p.Hin && p.Cin % 64 == 0 &&
@@ -2017,33 +2021,143 @@ __global__ __launch_bounds__(256) void splitk_reduce4f_kernel(GemmArgs p, int nz
   }
 }
 
-// What launch_gemm() will run for a problem: the ONE place where tiles and split-K are chosen (e4t_gemm_plan / e4t_conv3x3_plan
-// export it, so that callers size workspaces and label timings from the launcher's own decision instead of mirroring it).
-struct GemmPlan {
-  int tile;        // 64 | 128 | 160 (128x160) | 256 (256x128 DMA) | 512 (256x256 ping-pong) | 640 (512x128 ping-pong) | 1128 / 1160 (persistent 256x128 / 256x160)
-  int stages;      // LDS stages of the 64 / 128 / 160 DMA kernels
-  bool kt32;       // 32-wide K-tiles (experimental codes 5064 / 5128 / 5256)
-  bool general_epi;
-  bool buf_ok;     // operands addressable through buffer resources (< 4 GB)
-  int tm, tn, gx, gy;
-  int splitk, ktiles_per_split;
-  unsigned a_bytes, a2_bytes, b_bytes;
-};
-
+// ---- host half: ONE variant table drives tile choice (plan_gemm), launch and launch log (launch_gemm) -------------------------------------
 int device_cu_count() {
-  static int ncu = [] {
+  static const int ncu = [] {
     int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-    return n;
+    return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
   }();
   return ncu;
 }
 
+bool dma_allowed() { static const bool on = getenv("E4T_GEMM_REGSTAGE") == nullptr; return on; }      // A/B switch: register-staged reference kernel
+// A kernel entry point and the symbol text rocprofv3 prints for it, from ONE macro invocation so that the launch log cannot name another
+// kernel than the one launched: KERNEL(512, gemm_pp_kernel, 1, false, true) is {&gemm_pp_kernel<1, false, true>, "gemm_pp_kernel<1, false, true>", 512 threads}.
+struct KernelEntry { void (*fn)(GemmArgs); const char* text; int threads; };      // text == nullptr: not instantiated
+#define KERNEL(threads, name, ...) {&name<__VA_ARGS__>, #name "<" #__VA_ARGS__ ">", threads}
+#define NO_KERNEL {nullptr, nullptr, 0}
+enum : unsigned {
+  CAP_STAGED = 1u << 0,      // the LDS depth is a template argument: hints 3xxx / 4xxx and the cost model choose among this tile's rows
+  CAP_BUF = 1u << 1,         // LDS-DMA through buffer resources (32-bit byte offsets): operands below 4 GB, not under E4T_GEMM_REGSTAGE
+  CAP_COLSTATS = 1u << 2,    // its bf16 single-pass epilogue produces column statistics
+  CAP_SPLITK = 1u << 3,      // accepts split-K (grid.z)
+  CAP_WHOLE_K = 1u << 4,     // needs whole 64-wide K-tiles (of each source of a two-source A)
+  CAP_ONE_A = 1u << 5,       // no two-source A
+  CAP_WHOLE_N = 1u << 6,     // needs N % tn == 0 (ragged N is only exercised for the narrower tiles)
+  CAP_TAIL = 1u << 7,        // carries gemm_tail() (plan_gemm_tail)
+  CAP_PANELS = 1u << 8,      // carries row panels
+  CAP_ONE_PER_CU = 1u << 9,  // one 512-thread workgroup per CU: the "ping-pong" split-K rule
+  CAP_PERSISTENT = 1u << 10, // launched through e4t_launch_gemm_ps (gemm_ps.hip): at most one workgroup per CU walks all tiles
+  CAP_DMA = CAP_BUF | CAP_COLSTATS | CAP_SPLITK,
+};
+// A conv launch of the row goes to a strip-staged kernel instead when ok(p, splitk, batch) holds at launch time.
+struct StripAlt { bool (*ok)(const GemmArgs&, int, int); KernelEntry k[2]; };      // k[GENERAL]
+struct Variant {
+  int tile, kt, stages, tm, tn;      // the public tile code is `tile`, 1000 * stages + tile for 3 / 4 stages of a CAP_STAGED tile, 5000 + tile for kt == 32
+  unsigned caps;
+  KernelEntry gemm[2], conv[2], conv_cm[2];      // [GENERAL]; conv_cm: channel-major K order as a template argument (else a run-time flag)
+  StripAlt alt[2];
+};
+
+// ---- hooks of the measured-and-rejected variants (csrc/build.sh: E4T_EXPERIMENTAL=1); the product build answers "no" -----------------
+#ifdef E4T_EXPERIMENTAL
+#define XKERNEL(...) KERNEL(__VA_ARGS__)
+bool auto_256() { static const bool on = getenv("E4T_GEMM_AUTO256") != nullptr; return on; }      // measured: 128x128/2-stage >= 256x128/3-stage on every E4T shape
+bool auto_pt() { static const bool on = getenv("E4T_GEMM_PT") != nullptr; return on; }
+int auto_ps() { static const int on = getenv("E4T_GEMM_PS") ? atoi(getenv("E4T_GEMM_PS")) : E4T_GEMM_PS_DEFAULT; return on; }
+// measured and rejected (round 6): the 16-wave 256 x 256 strip kernel EQUALS the ping-pong kernel on every conv shape of the step (1072 / 1007 /
+// 526 / 254 / 126 us against 1046-1082 / 995-1011 / 515-531 / 253 / 125-128) although it fills a third of the A bytes — with 64 x 64 wave tiles
+// it needs one fragment ds_read per MFMA, 125 B/clk/CU of LDS reads at the MFMA peak against the LDS's 128
+bool strip256_ok(const GemmArgs& p, int splitk, int batch) {
+  static const bool on = getenv("E4T_CONV_STRIP256") != nullptr && atoi(getenv("E4T_CONV_STRIP256")) != 0;
+  return on && conv_strip_ok(p, splitk, batch);
+}
+int launch_persistent(GemmArgs& p, const Variant& v, bool conv, bool general, hipStream_t st) {
+  static const bool ps_pre = getenv("E4T_PS_PRE") == nullptr || atoi(getenv("E4T_PS_PRE")) != 0;      // A/B switch
+  p.ps_pre = ps_pre && p.fast_epi && cdiv(p.K, BK) >= 2 && (!p.rowbias || p.rows_per_batch % 256 == 0);
+  return e4t_launch_gemm_ps(&p, conv ? 1 : 0, v.tn, general ? 1 : 0, device_cu_count(), st);
+}
+#else
+#define XKERNEL(...) NO_KERNEL
+bool auto_256() { return false; }
+bool auto_pt() { return false; }
+int auto_ps() { return 0; }
+bool strip256_ok(const GemmArgs&, int, int) { return false; }
+int launch_persistent(GemmArgs&, const Variant&, bool, bool, hipStream_t) { E4T_FAIL(-22, "gemm: the persistent kernels are not built"); }
+#endif
+
+// ---- the variant table.  How to add a variant: (1) write its kernel above, signature void(GemmArgs); (2) add ONE row here — tile code, tile shape, what it can
+// do, its instantiations; (3) add the rule that chooses it to choose_tile() with the measurement that justifies it.  Everything else
+// (hints, capability fallback, split-K, launch, launch log, e4t_gemm_plan) follows from the row.
+#define DMA_FN(nt, bm, bn, wgm, wgn, st, kt) {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 0, st, false, kt), NO_KERNEL}, \
+                                             {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 1, st, false, kt), NO_KERNEL}
+#define DMA_FN_GENERAL(nt, bm, bn, wgm, wgn, st)                                                                                  \
+  {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 0, st, false, 64), KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 0, st, true, 64)}, \
+  {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 1, st, false, 64), KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 1, st, true, 64)}
+#define PS_TEXT(mode, bn, general) {nullptr, "gemm_ps_kernel<" #mode ", " #bn ", " #general ">", 512}
+#define PS_FN(bn) {PS_TEXT(0, bn, false), PS_TEXT(0, bn, true)}, {PS_TEXT(1, bn, false), PS_TEXT(1, bn, true)}
+#define REG_FN(bm, bn, mode) {{&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}, {&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}}
+static const Variant kVariants[] = {
+    // 64 / 128 / 160 tiles: 2 LDS stages and 2 workgroups per CU by default; 3 or 4 stages (one workgroup per CU, 2-3 K-tiles in flight)
+    // when the grid cannot give a CU two workgroups anyway (small_grid_plan).  GENERAL: the 2-stage tiles and the 3-stage 64 tile.
+    {64, 64, 2, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(256, 64, 64, 2, 2, 2)},
+    {64, 64, 3, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(256, 64, 64, 2, 2, 3)},
+    {64, 64, 4, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN(256, 64, 64, 2, 2, 4, 64)},
+    // 128x128: 8 waves (wave tile 32x64): ~4 waves/SIMD at 2 workgroups/CU hide the DMA/LDS latency that the 4-wave
+    // version of the same tile exposed (measured +5..18 % on every E4T shape, 8192^3: 956 -> 980 TF)
+    {128, 64, 2, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(512, 128, 128, 4, 2, 2)},
+    {128, 64, 3, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN(512, 128, 128, 4, 2, 3, 64)},
+    {128, 64, 4, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN(512, 128, 128, 4, 2, 4, 64)},
+    {160, 64, 2, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN_GENERAL(256, 128, 160, 4, 1, 2)},
+    {160, 64, 3, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN(256, 128, 160, 4, 1, 3, 64)},
+    {160, 64, 4, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN(256, 128, 160, 4, 1, 4, 64)},
+    // 5256: 256 x 128 with 32-wide K-tiles, 3 x 24 KiB stages = two workgroups per CU; stride-1 convs on conv_strip_kernel where it applies
+    {256, 32, 3, 256, 128, CAP_DMA, DMA_FN(512, 256, 128, 4, 2, 3, 32), {}, {{conv_strip_ok, {KERNEL(512, conv_strip_kernel, 2), NO_KERNEL}}}},
+    // 512: 256 x 256 ping-pong; stride-1 convs on gemm_pps_kernel where it applies
+    {512, 64, 2, 256, 256, CAP_DMA | CAP_WHOLE_K | CAP_TAIL | CAP_ONE_PER_CU,
+     {KERNEL(512, gemm_pp_kernel, 0, false, false), KERNEL(512, gemm_pp_kernel, 0, true, false)},
+     {KERNEL(512, gemm_pp_kernel, 1, false, false), KERNEL(512, gemm_pp_kernel, 1, true, false)},
+     {KERNEL(512, gemm_pp_kernel, 1, false, true), KERNEL(512, gemm_pp_kernel, 1, true, true)},
+     {{conv_pps_ok, {KERNEL(512, gemm_pps_kernel, false), KERNEL(512, gemm_pps_kernel, true)}},
+      {strip256_ok, {XKERNEL(1024, conv_strip_kernel, 4), NO_KERNEL}}}},
+    // 2320: 256 x 320 ping-pong (the GENERAL instantiation exists for GEMMs only)
+    {2320, 64, 2, 256, 320, CAP_DMA | CAP_WHOLE_K | CAP_WHOLE_N | CAP_TAIL | CAP_PANELS | CAP_ONE_PER_CU,
+     {KERNEL(512, gemm_pq_kernel, 0, 320, false), KERNEL(512, gemm_pq_kernel, 0, 320, true)}, {KERNEL(512, gemm_pq_kernel, 1, 320, false), NO_KERNEL}},
+    // the register-staged fallback (operands beyond 4 GB, E4T_GEMM_REGSTAGE), logged as bare "gemm_kernel", GENERAL at run time
+    {128, 64, 2, 128, 128, CAP_SPLITK, REG_FN(128, 128, 0), REG_FN(128, 128, 1)},
+    {64, 64, 2, 64, 64, CAP_SPLITK, REG_FN(64, 64, 0), REG_FN(64, 64, 1)},
+#ifdef E4T_EXPERIMENTAL
+    // measured and rejected: 32-wide K-tiles on the 64 / 128 tiles (5064 / 5128), the 64-wide 256 x 128 tile (256), the 512 x 128 ping-pong
+    // tile (640), the persistent streaming kernels (1128 / 1160).  Those are instantiated in gemm_ps.hip, out of KERNEL()'s reach: their
+    // entries have no pointer, launch_persistent() hands e4t_launch_gemm_ps the (mode, tn, GENERAL) triple that PS_FN spells into the text.
+    {64, 32, 4, 64, 64, CAP_DMA, DMA_FN(256, 64, 64, 2, 2, 4, 32)},
+    {128, 32, 4, 128, 128, CAP_DMA, DMA_FN(512, 128, 128, 4, 2, 4, 32)},
+    {256, 64, 2, 256, 128, CAP_DMA, DMA_FN(512, 256, 128, 4, 2, 3, 64)},
+    {640, 64, 2, 512, 128, CAP_DMA | CAP_WHOLE_K | CAP_ONE_A, {KERNEL(512, gemm_pt_kernel, 0), NO_KERNEL}, {KERNEL(512, gemm_pt_kernel, 1), NO_KERNEL}},
+    {1128, 64, 2, 256, 128, CAP_BUF | CAP_COLSTATS | CAP_WHOLE_K | CAP_PERSISTENT, PS_FN(128)},
+    {1160, 64, 2, 256, 160, CAP_BUF | CAP_COLSTATS | CAP_WHOLE_K | CAP_PERSISTENT, PS_FN(160)},
+#endif
+};
+// The row of (tile, K-tile width, stages) — stages select only among CAP_STAGED rows — among the LDS-DMA rows or (!dma) the register-staged
+// ones; nullptr if this build carries none.
+const Variant* find_variant(int tile, bool kt32, int stages, bool dma = true) {
+  for (const Variant& v : kVariants)
+    if (!(v.caps & CAP_BUF) == !dma && v.tile == tile && v.kt == (kt32 ? 32 : 64) && (!(v.caps & CAP_STAGED) || v.stages == stages)) return &v;
+  return nullptr;
+}
+const KernelEntry& kernel_of(const Variant& v, bool conv, bool general) { return (conv ? v.conv : v.gemm)[general]; }
+// The ONE place that turns a planned row into a kernel entry: launch and launch log both ask it.
+const KernelEntry& select_entry(const Variant& v, const GemmArgs& p, bool conv, bool general, int splitk, int batch) {
+  if (conv)
+    for (const StripAlt& a : v.alt)
+      if (a.ok && a.k[general].text && a.ok(p, splitk, batch)) return a.k[general];
+  if (conv && p.chan_major && v.conv_cm[general].text) return v.conv_cm[general];
+  return kernel_of(v, conv, general);
+}
+
 // The persistent 256 x BN kernel (gemm_ps.hip) pays when its one-workgroup-per-CU rounds are (nearly) full.
 bool ps_rounds_ok(long long units, int ncu) {
-  if (units < ncu) return false;
-  const long long rounds = (units + ncu - 1) / ncu;
-  return units * 100 >= rounds * ncu * 85;
+  return units >= ncu && units * 100 >= cdivl(units, ncu) * ncu * 85;
 }
 
 // ---- cost model of one launch of the 64 x 64 / 128 x 128 / 128 x 160 DMA tiles (round 4) ---------------------------------------------
@@ -2093,263 +2207,303 @@ SmallGridPlan small_grid_plan(int M, int N, int nkt, bool conv, bool general, in
   return best;
 }
 
-GemmPlan plan_gemm(const GemmArgs& p, bool conv, int tile_hint, int splitk_req, int batch) {
-  GemmPlan pl;
-  const int nkt = cdiv(p.K, BK);
-  // --- tile selection: fill >= ~1.5 waves of the 256 CUs with 128x128 tiles, else drop to 64x64 ---
-  int stages = 2;                         // LDS stages of the 64 / 128 / 160 DMA kernels; a hint of 3128 / 4160 / ... forces 3 or 4
-  int model_splitk = 0;                   // > 0: split-K chosen together with the tile by small_grid_plan
-  bool kt32 = false;                      // 5128 / 5064 / 5256: the 32-wide K-tile variant (4 stages in the LDS of 2 x 64-wide ones; 5256: 3)
-  if (tile_hint >= 3000 && tile_hint < 5000) { stages = tile_hint / 1000; tile_hint %= 1000; }
-  else if (tile_hint >= 5000 && tile_hint < 6000) { kt32 = true; stages = 4; tile_hint %= 1000; }
-  int tile = tile_hint;
-#ifndef E4T_EXPERIMENTAL
-  // The product library carries the tiles the planner chooses (64 / 128 / 160 with 2 - 4 LDS stages, 5256, 512, 2320) and nothing else:
-  // the measured-and-rejected variants — 32-wide K-tiles on the 64 / 128 tiles, the 64-wide 256 x 128 tile, the 512 x 128 ping-pong
-  // tile, the persistent streaming kernels of gemm_ps.hip — are built only with -DE4T_EXPERIMENTAL (csrc/build.sh:
-  // E4T_EXPERIMENTAL=1).  A hint that names one of them gets the nearest product tile.
-  if (kt32 && tile != 256) { kt32 = false; stages = 2; }
-  if (tile != 64 && tile != 128 && tile != 160) stages = 2;
-  if (tile == 256 && !kt32) { kt32 = true; stages = 3; }
-  if (tile == 640) tile = 128;
-  if (tile == 1128) tile = 128;
-  if (tile == 1160) tile = 160;
-#endif
-  static const bool allow256 = getenv("E4T_GEMM_REGSTAGE") == nullptr;
-#ifdef E4T_EXPERIMENTAL
-  static const bool auto256 = getenv("E4T_GEMM_AUTO256") != nullptr;    // measured: 128x128/2-stage >= 256x128/3-stage on every E4T shape
-#else
-  const bool auto256 = false;
-#endif
-  const bool r2_rules = false;           // (round 2's rules: 112.5 vs 110.8 ms per step, profiles/r03_ab/r03c_*)
-  const bool whole_k = p.K % BK == 0 && (!p.A2 || p.K1 % BK == 0);
-  const bool ps_ok = allow256 && whole_k && batch == 1 && !p.reduce_batch && splitk_req <= 1;      // what gemm_ps_kernel accepts
-  if (tile != 64 && tile != 128 && tile != 256 && tile != 160 && tile != 512 && tile != 640 && tile != 1128 && tile != 1160 && tile != 2320) {
-    // measured on MI355X (tools/sweep_small.py): 128x128 wins from one full round of the 256 CUs, and already from
-    // a quarter round when K is long (3x3 convs at the 16x16 / 8x8 levels) if split-K fills the chip
-    const long long t256 = (long long)cdiv(p.M, 256) * cdiv(p.N, 128) * batch;
-    const long long t128 = (long long)cdiv(p.M, 128) * cdiv(p.N, 128) * batch;
-    tile = (allow256 && auto256 && t256 >= 256) ? 256 : (t128 >= 256 || (nkt >= 32 && t128 >= 64)) ? 128 : 64;
-    // every channel count of the SD UNets is a multiple of 160 but 320 / 640 / 960 are not multiples of 128: a 128x160
-    // tile has no N padding there (conv 640->640 @32x32: 863 vs 589 TF)
-    if (allow256 && tile == 128 && p.N % 160 == 0 && p.N <= 960 && (long long)cdiv(p.M, 128) * (p.N / 160) * batch >= 128) tile = 160;
-    // K-deep shapes whose N is a multiple of 256 and that fill the chip at least twice with 256x256 tiles (the VAE's 256-
-    // and 512-channel convs): the ping-pong kernel (conv 512->512 @128^2: 1075 vs 928 TF, 8192^3: 1173 vs 971 TF)
-    const bool no_pp = false;
-    const long long tpp = (long long)cdiv(p.M, 256) * (p.N / 256) * batch;
-    if (allow256 && !no_pp && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= (conv ? 16 : (r2_rules ? 32 : 20)) && tpp >= 512) tile = 512;
-    // ... and, with split-K, for the very K-deep shapes of the 16x16 level that give it less than one round of tiles (1280-channel
-    // 3x3 convs, the GEGLU input gradient K = 10240): tools/sweep_step_shapes.py, conv 1280->1280 M4096 128 vs 141 us, conv
-    // 1280->2560 209 vs 290 us, conv 2560->1280 221 vs 265 us, GEMM 4096x1280x10240 126 vs 138 us; at K = 5120 it loses.  (Round 3:
-    // 256..511 tiles are NOT split any more — conv 1280->1280 M16384: 3 splits 545 us, 1 split 482 us, 128 x 160 tile 454 us.)
-    if (allow256 && !no_pp && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= 128 && tpp >= 64 && tpp < (r2_rules ? 512 : 256)) tile = 512;
-    // one (nearly) full round of ping-pong tiles, K >= 1280: the ViT's qkv projection M4112 N3840 (255 tiles) 44.9 vs 49.5 us,
-    // M4096 N3840 42.7 vs 48.3 us
-    if (!r2_rules && allow256 && !no_pp && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= 20 && tpp >= 224 && tpp <= 256) tile = 512;
-    // The 512 x 128 variant of the same machine (tile code 640) is NOT chosen automatically: on the shapes it was built for
-    // (the VAE's 128-channel convs, K = 1152 = 18 K-tiles) it measured 526 vs 588 TF/s for the 128 x 128 tile — one 160-KiB
-    // workgroup per CU leaves nothing to overlap its (large) epilogue and prologue with, and 18 K-tiles do not amortise
-    // them (tools/ab_pt.py).  E4T_GEMM_PT=1 turns the automatic choice on for experiments.
-#ifdef E4T_EXPERIMENTAL
-    static const bool auto_pt = getenv("E4T_GEMM_PT") != nullptr;
-#else
-    const bool auto_pt = false;
-#endif
-    if (auto_pt && allow256 && tile == 128 && p.N % 128 == 0 && p.N % 256 != 0 && p.K % BK == 0 && nkt >= 16 && !p.A2 &&
-        (long long)cdiv(p.M, 512) * (p.N / 128) * batch >= 512) tile = 640;
-    const bool general = (p.flags & E4T_ACT_GELU) || (p.rowbias && p.rows_per_batch % 32 != 0);
-    // Round 3 (tools/sweep_ps.py on the step's own shapes, cold operands):
-    //  * the 128 x 160 tile also for N > 960 when K is deep and the grid is large — conv 640->1920 M16384 350 vs 378 us, conv
-    //    1280->1280 M16384 454 vs 482 (ping-pong) / 492 (128 x 128), GEMM M4096 N5120 K1280 60 vs 64 us; on short K it loses
-    //    (M16384 N5120 K640: 145 vs 127 us), and its GELU instantiation is register-bound (M4112 N5120: 107 vs 85 us);
-    if (!r2_rules && allow256 && tile == 128 && !general && p.N % 160 == 0 && p.N > 960 && nkt >= 20 &&
-        (long long)cdiv(p.M, 128) * (p.N / 160) * batch >= 1024) tile = 160;
-    //  * 256 x 128 with 32-wide K-tiles (8 waves, wave tile 64 x 64, three 24-KiB stages = two workgroups per CU; code 5256) for
-    //    tall outputs whose N is a multiple of 128: half the B re-reads and 2/3 of the fragment LDS reads of the 128 x 128 tile per
-    //    flop.  VAE conv 128->128 @512^2 1449 vs 1744 us, stride-2 conv 455 vs 493, conv_in GEMM M4194304 N128 K32 261 vs 386 (no
-    //    padding of K to 64), GEMM M65536 N2560 K320 162 vs 185, M65536 N1280 K320 76 vs 81 us.
-    if (!r2_rules && allow256 && tile == 128 && !general && (p.N % 128 == 0 || p.N < 128) &&
-        (long long)cdiv(p.M, 256) * cdiv(p.N, 128) * batch >= 768) { tile = 256; kt32 = true; stages = 3; }
-    //  * the 256 x 320 ping-pong tile (gemm_pq_kernel, code 2320) wherever N is a multiple of 320 and its rounds of one workgroup per
-    //    CU come out full: 0.93 KB of LDS traffic per MFMA against 1.69 KB for the 128 x 160 tile.  Cold-operand sweep
-    //    (profiles/r03_sweep_tiles_c.txt): conv 320->320 @64^2 105 vs 127 us (1154 TF/s), 640->640 @64^2 374 vs 458, 1280->1280
-    //    M16384 354 vs 439 (1366 TF/s), nearest-x2 + conv 1280->1280 339 vs 472 (1424 TF/s); GEMM M65536 N320 K2560 103 vs 135,
-    //    K1280 57 vs 73, K320 26 vs 28; M4096 N10240 K1280 100 vs 112 (ping-pong 256 x 256).  It loses below one round (M16384
-    //    N640: 128 tiles) and on the K = 320 GEMMs wider than 320 (epilogue-bound: 83 vs 72 us at N1280).
-    const bool no_pq = false;              // (without the 256 x 320 tile: 108.0 vs 106.4 ms per step, profiles/r03_ab/r03h_*)
-    if (!r2_rules && !no_pq && allow256 && batch == 1 && (!general || !conv) && whole_k && p.N % 320 == 0) {
-      const long long t320 = (long long)cdiv(p.M, 256) * (p.N / 320);
-      const int ncu = device_cu_count();
-      const double eff = (double)t320 / (double)(cdivl(t320, ncu) * ncu);
-      if (t320 >= ncu && ((nkt >= 20 && eff >= 0.75) || (nkt >= 10 && eff >= 0.99) || (nkt >= 5 && p.N == 320 && eff >= 0.99))) {
-        tile = 2320; kt32 = false; stages = 2;
-      }
-    }
-    // The persistent 256 x 160 / 256 x 128 streaming kernel (gemm_ps.hip).  NOT chosen automatically: correct, but slower than the
-    // tiles above on every shape of the step (its ping-pong phases are bound by the DMA-issue / fragment-read segment).
-    // E4T_GEMM_PS=1 turns the automatic choice on for experiments.
-#ifdef E4T_EXPERIMENTAL
-    static const int auto_ps = getenv("E4T_GEMM_PS") ? atoi(getenv("E4T_GEMM_PS")) : E4T_GEMM_PS_DEFAULT;
-#else
-    const int auto_ps = 0;
-#endif
-    if (auto_ps && ps_ok && (tile == 128 || tile == 160)) {
-      const int ncu = device_cu_count();
-      const long long rows = cdiv(p.M, 256);
-      if (p.N % 160 == 0 && ps_rounds_ok(rows * (p.N / 160), ncu)) tile = 1160;
-      else if ((p.N % 128 == 0 || p.N < 128) && ps_rounds_ok(rows * cdiv(p.N, 128), ncu)) tile = 1128;
-    }
-    // Round 4: the 64 / 128 / 160 tiles, their LDS depth and split-K are arbitrated by a cost model of the launch (small_grid_plan above)
-    // instead of the rules that chose among them until round 3; the rules above still decide WHETHER one of the big tiles runs.
-    const bool no_model = false;           // (the round-3 rules instead of the cost model: C5 B = 1 44.4 vs 39.8 ms, profiles/r04_ab/r04s_*)
-    if (!no_model && allow256 && (tile == 64 || tile == 128 || tile == 160) && batch == 1 && !p.reduce_batch && !p.panel_rows) {
-      const SmallGridPlan sg = small_grid_plan(p.M, p.N, nkt, conv, general, splitk_req, p.colstats != nullptr, device_cu_count());
-      tile = sg.tile; stages = sg.stages; model_splitk = sg.splitk;
+// What launch_gemm() will run for a problem: the ONE place where tiles and split-K are chosen (e4t_gemm_plan / e4t_conv3x3_plan
+// export it, so that callers size workspaces and label timings from the launcher's own decision instead of mirroring it).
+struct GemmPlan {
+  int tile, stages;          // the tile and LDS depth as the public plan reports them
+  bool kt32, general_epi, buf_ok;      // kt32: 32-wide K-tiles (codes 5xxx); buf_ok: operands addressable through buffer resources (< 4 GB)
+  const Variant* shape;      // the row whose tile shape and capabilities the grid and split-K were planned for
+  const Variant* run;        // the row that is launched: `shape`, or the register-staged fallback
+  int gx, gy, splitk, ktiles_per_split;
+  unsigned a_bytes, a2_bytes, b_bytes;
+};
+
+// The planner is a plan under construction, with the problem and what is derived from it once.
+struct Planner : GemmPlan {
+  const GemmArgs& p;
+  const bool conv;
+  const int splitk_req, batch, nkt;
+  const bool whole_k, ps_ok, dma;      // ps_ok: what gemm_ps_kernel accepts; dma: no E4T_GEMM_REGSTAGE
+  int model_splitk;                    // > 0: split-K chosen together with the tile by small_grid_plan
+  bool decode_hint(int hint);      // the four stages, in the order plan_gemm() runs them
+  void choose_tile();
+  void apply_capabilities();
+  int choose_splitk() const;
+  const Variant* row() {      // the row the choice stands for: a K-tile width the tile has no row for selects nothing, a tile without any row is the default tile
+    const Variant* v = find_variant(tile, kt32, stages);
+    if (!v && kt32) v = find_variant(tile, false, stages);
+    if (!v) { tile = 128; stages = 2; kt32 = false; v = find_variant(128, false, 2); }
+    return v;
+  }
+};
+
+// --- stage 1: a tile hint -> (tile, stages, K-tile width).  64 | 128 | 160 (128 x 160) | 512 (256 x 256 ping-pong) | 2320 (256 x 320
+// ping-pong); 3000 / 4000 + tile: 3 / 4 LDS stages of the 64 / 128 / 160 tiles; 5000 + tile: 32-wide K-tiles.  Anything else (0): automatic.
+// The product library carries the tiles the planner chooses (64 / 128 / 160 with 2 - 4 LDS stages, 5256, 512, 2320) and nothing else: the
+// measured-and-rejected variants (5064 / 5128, 256, 640, 1128 / 1160: see their rows) are built only with -DE4T_EXPERIMENTAL.  A hint whose
+// row is absent gets the nearest product tile: a stage / K-tile prefix the tile has no row for is dropped, then `substitute` applies.
+bool Planner::decode_hint(int hint) {      // false: the hint names no tile
+  static const struct { int tile, product, stages; bool kt32; } substitute[] = {{256, 256, 3, true}, {640, 128, 2, false}, {1128, 128, 2, false}, {1160, 160, 2, false}};
+  tile = hint; stages = 2; kt32 = false;
+  if (hint >= 3000 && hint < 5000) { stages = hint / 1000; tile = hint % 1000; }
+  else if (hint >= 5000 && hint < 6000) { kt32 = true; stages = 4; tile = hint % 1000; }
+  const Variant* v = find_variant(tile, kt32, stages);
+  if (!v) {
+    stages = 2; kt32 = false;
+    v = find_variant(tile, false, 2);
+    for (const auto& s : substitute)
+      if (!v && s.tile == tile) { tile = s.product; stages = s.stages; kt32 = s.kt32; v = find_variant(tile, kt32, stages); }
+  }
+  if (v && !(v->caps & CAP_STAGED)) stages = v->stages;
+  return v != nullptr;
+}
+
+// --- stage 2: the automatic choice — the measured rules decide WHETHER one of the big tiles runs, then the cost model arbitrates the 64 / 128 /
+// 160 tiles, their LDS depth and split-K.  Enters with stages == 2, kt32 == false.  (Round 2's rules: 112.5 vs 110.8 ms per step, profiles/r03_ab/r03c_*.)
+void Planner::choose_tile() {
+  // fill >= ~1.5 waves of the 256 CUs with 128x128 tiles, else drop to 64x64.  Measured on MI355X (tools/sweep_small.py): 128x128 wins
+  // from one full round of the 256 CUs, and already from a quarter round when K is long (3x3 convs at the 16x16 / 8x8 levels) if
+  // split-K fills the chip
+  const long long t256 = (long long)cdiv(p.M, 256) * cdiv(p.N, 128) * batch;
+  const long long t128 = (long long)cdiv(p.M, 128) * cdiv(p.N, 128) * batch;
+  tile = (dma && auto_256() && t256 >= 256) ? 256 : (t128 >= 256 || (nkt >= 32 && t128 >= 64)) ? 128 : 64;
+  // every channel count of the SD UNets is a multiple of 160 but 320 / 640 / 960 are not multiples of 128: a 128x160
+  // tile has no N padding there (conv 640->640 @32x32: 863 vs 589 TF)
+  if (dma && tile == 128 && p.N % 160 == 0 && p.N <= 960 && (long long)cdiv(p.M, 128) * (p.N / 160) * batch >= 128) tile = 160;
+  // K-deep shapes whose N is a multiple of 256 and that fill the chip at least twice with 256x256 tiles (the VAE's 256-
+  // and 512-channel convs): the ping-pong kernel (conv 512->512 @128^2: 1075 vs 928 TF, 8192^3: 1173 vs 971 TF)
+  const long long tpp = (long long)cdiv(p.M, 256) * (p.N / 256) * batch;
+  if (dma && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= (conv ? 16 : 20) && tpp >= 512) tile = 512;
+  // ... and, with split-K, for the very K-deep shapes of the 16x16 level that give it less than one round of tiles (1280-channel
+  // 3x3 convs, the GEGLU input gradient K = 10240): tools/sweep_step_shapes.py, conv 1280->1280 M4096 128 vs 141 us, conv
+  // 1280->2560 209 vs 290 us, conv 2560->1280 221 vs 265 us, GEMM 4096x1280x10240 126 vs 138 us; at K = 5120 it loses.  (Round 3:
+  // 256..511 tiles are NOT split any more — conv 1280->1280 M16384: 3 splits 545 us, 1 split 482 us, 128 x 160 tile 454 us.)
+  if (dma && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= 128 && tpp >= 64 && tpp < 256) tile = 512;
+  // one (nearly) full round of ping-pong tiles, K >= 1280: the ViT's qkv projection M4112 N3840 (255 tiles) 44.9 vs 49.5 us,
+  // M4096 N3840 42.7 vs 48.3 us
+  if (dma && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= 20 && tpp >= 224 && tpp <= 256) tile = 512;
+  // The 512 x 128 variant of the same machine (tile code 640) is NOT chosen automatically: on the shapes it was built for
+  // (the VAE's 128-channel convs, K = 1152 = 18 K-tiles) it measured 526 vs 588 TF/s for the 128 x 128 tile — one 160-KiB
+  // workgroup per CU leaves nothing to overlap its (large) epilogue and prologue with, and 18 K-tiles do not amortise
+  // them (tools/ab_pt.py).  E4T_GEMM_PT=1 turns the automatic choice on for experiments.
+  if (auto_pt() && dma && tile == 128 && p.N % 128 == 0 && p.N % 256 != 0 && p.K % BK == 0 && nkt >= 16 && !p.A2 &&
+      (long long)cdiv(p.M, 512) * (p.N / 128) * batch >= 512) tile = 640;
+  // Round 3 (tools/sweep_ps.py on the step's own shapes, cold operands):
+  //  * the 128 x 160 tile also for N > 960 when K is deep and the grid is large — conv 640->1920 M16384 350 vs 378 us, conv
+  //    1280->1280 M16384 454 vs 482 (ping-pong) / 492 (128 x 128), GEMM M4096 N5120 K1280 60 vs 64 us; on short K it loses
+  //    (M16384 N5120 K640: 145 vs 127 us), and its GELU instantiation is register-bound (M4112 N5120: 107 vs 85 us);
+  if (dma && tile == 128 && !general_epi && p.N % 160 == 0 && p.N > 960 && nkt >= 20 &&
+      (long long)cdiv(p.M, 128) * (p.N / 160) * batch >= 1024) tile = 160;
+  //  * 256 x 128 with 32-wide K-tiles (8 waves, wave tile 64 x 64, three 24-KiB stages = two workgroups per CU; code 5256) for
+  //    tall outputs whose N is a multiple of 128: half the B re-reads and 2/3 of the fragment LDS reads of the 128 x 128 tile per
+  //    flop.  VAE conv 128->128 @512^2 1449 vs 1744 us, stride-2 conv 455 vs 493, conv_in GEMM M4194304 N128 K32 261 vs 386 (no
+  //    padding of K to 64), GEMM M65536 N2560 K320 162 vs 185, M65536 N1280 K320 76 vs 81 us.
+  if (dma && tile == 128 && !general_epi && (p.N % 128 == 0 || p.N < 128) &&
+      (long long)cdiv(p.M, 256) * cdiv(p.N, 128) * batch >= 768) { tile = 256; kt32 = true; stages = 3; }
+  //  * the 256 x 320 ping-pong tile (gemm_pq_kernel, code 2320) wherever N is a multiple of 320 and its rounds of one workgroup per
+  //    CU come out full: 0.93 KB of LDS traffic per MFMA against 1.69 KB for the 128 x 160 tile.  Cold-operand sweep
+  //    (profiles/r03_sweep_tiles_c.txt): conv 320->320 @64^2 105 vs 127 us (1154 TF/s), 640->640 @64^2 374 vs 458, 1280->1280
+  //    M16384 354 vs 439 (1366 TF/s), nearest-x2 + conv 1280->1280 339 vs 472 (1424 TF/s); GEMM M65536 N320 K2560 103 vs 135,
+  //    K1280 57 vs 73, K320 26 vs 28; M4096 N10240 K1280 100 vs 112 (ping-pong 256 x 256).  It loses below one round (M16384
+  //    N640: 128 tiles) and on the K = 320 GEMMs wider than 320 (epilogue-bound: 83 vs 72 us at N1280).
+  //    (Without the 256 x 320 tile: 108.0 vs 106.4 ms per step, profiles/r03_ab/r03h_*.)
+  if (dma && batch == 1 && (!general_epi || !conv) && whole_k && p.N % 320 == 0) {
+    const long long t320 = (long long)cdiv(p.M, 256) * (p.N / 320);
+    const int ncu = device_cu_count();
+    const double eff = (double)t320 / (double)(cdivl(t320, ncu) * ncu);
+    if (t320 >= ncu && ((nkt >= 20 && eff >= 0.75) || (nkt >= 10 && eff >= 0.99) || (nkt >= 5 && p.N == 320 && eff >= 0.99))) {
+      tile = 2320; kt32 = false; stages = 2;
     }
   }
+  // The persistent 256 x 160 / 256 x 128 streaming kernel (gemm_ps.hip).  NOT chosen automatically: correct, but slower than the
+  // tiles above on every shape of the step (its ping-pong phases are bound by the DMA-issue / fragment-read segment).
+  // E4T_GEMM_PS=1 turns the automatic choice on for experiments.
+  if (auto_ps() && ps_ok && (tile == 128 || tile == 160)) {
+    const int ncu = device_cu_count();
+    const long long rows = cdiv(p.M, 256);
+    if (p.N % 160 == 0 && ps_rounds_ok(rows * (p.N / 160), ncu)) tile = 1160;
+    else if ((p.N % 128 == 0 || p.N < 128) && ps_rounds_ok(rows * cdiv(p.N, 128), ncu)) tile = 1128;
+  }
+  // Round 4: the 64 / 128 / 160 tiles, their LDS depth and split-K are arbitrated by a cost model of the launch (small_grid_plan above)
+  // instead of the rules that chose among them until round 3; the rules above still decide WHETHER one of the big tiles runs.
+  // (The round-3 rules instead of the cost model: C5 B = 1 44.4 vs 39.8 ms, profiles/r04_ab/r04s_*.)
+  if (dma && (tile == 64 || tile == 128 || tile == 160) && batch == 1 && !p.reduce_batch && !p.panel_rows) {
+    const SmallGridPlan sg = small_grid_plan(p.M, p.N, nkt, conv, general_epi, splitk_req, p.colstats != nullptr, device_cu_count());
+    tile = sg.tile; stages = sg.stages; model_splitk = sg.splitk;
+  }
+}
+
+// --- stage 3: every capability the chosen row lacks for this problem sends it to a narrower tile — 128 x 128, or 128 x 160 where the
+// row's own width is a multiple of 160 and N allows it.  Also computes the operand extents (buf_ok).
+void Planner::apply_capabilities() {
+  auto narrower = [&](const Variant* v) { return v && v->tn % 160 == 0 && p.N % 160 == 0 ? 160 : 128; };
   // epilogues with the exact GELU or a per-row row-bias lookup run the GENERAL instantiation, built for the 2-stage 64 / 128 / 160 tiles (and
-  // the 3-stage 64 tile), the 256 x 256 / 256 x 320 ping-pong kernels and the persistent kernels
-  const bool general_epi = (p.flags & E4T_ACT_GELU) || (p.rowbias && p.rows_per_batch % 32 != 0);
-  if (general_epi) { if (!(tile == 64 && stages == 3)) stages = 2; kt32 = false; if (tile == 256 || tile == 640) tile = 128; }
-  if (kt32 && tile != 128 && tile != 64 && tile != 256) kt32 = false;
-  if (kt32 && tile == 256) stages = 3;
-  if (tile == 256 && !allow256) tile = 128;
-  if (tile == 160 && !allow256) tile = 128;
-  if (tile == 640 && (!allow256 || p.A2)) tile = 128;
-  if ((tile == 1128 || tile == 1160) && !ps_ok) tile = tile == 1160 && p.N % 160 == 0 ? 160 : 128;
-  if (tile == 2320 && !allow256) tile = 128;
-  if (tile == 2320 && general_epi && conv) tile = p.N % 160 == 0 ? 160 : 128;      // (the GENERAL instantiation of the 256 x 320 tile exists for GEMMs only)
-  // row panels exist in the 256 x 320 ping-pong kernel only
-  if (p.panel_rows && !(tile == 2320 && allow256)) tile = (p.N % 320 == 0 && whole_k && !conv) ? 2320 : tile;
+  // the 3-stage 64 tile), the 256 x 256 / 256 x 320 (GEMM only) ping-pong kernels and the persistent kernels; no 32-wide-K kernel has it
+  if (general_epi) {
+    kt32 = false;
+    const Variant* v = find_variant(tile, false, stages);
+    if (!(v && (v->caps & CAP_STAGED) && kernel_of(*v, conv, true).text)) { stages = 2; v = find_variant(tile, false, 2); }
+    if (!(v && kernel_of(*v, conv, true).text)) tile = narrower(v);
+  }
+  const Variant* v = row();
+  auto fall = [&](int t) { tile = t; v = row(); };
+  // E4T_GEMM_REGSTAGE: only the tiles the register-staged kernel is built for.  PRESERVED OVERSIGHT: a persistent hint is exempt, the next
+  // rule may give it the 128 x 160 tile, which has no register-staged row: plan_gemm() then runs the 64 x 64 kernel on a 128 x 160 grid.
+  if (!dma && !(v->caps & CAP_PERSISTENT) && !find_variant(tile, false, 2, false)) fall(128);
+  if ((v->caps & CAP_PERSISTENT) && !ps_ok) fall(narrower(v));
+  if ((v->caps & CAP_ONE_A) && p.A2) fall(128);
+  // row panels: the row that carries them, where the problem meets its other needs
+  if (p.panel_rows && !(v->caps & CAP_PANELS))
+    for (const Variant& w : kVariants)
+      if ((w.caps & CAP_PANELS) && p.N % w.tn == 0 && whole_k && !conv) fall(w.tile);
   // The DMA kernels address their operands through buffer resources (32-bit byte offsets): operands beyond 4 GB fall back to
   // the register-staged kernel.  The ping-pong kernels additionally need whole K-tiles.
-  bool buf_ok = true;
-  {
-    const unsigned long long lim = 0xFFFF0000ull;
-    unsigned long long ab, a2b = 0, bb = ((unsigned long long)(p.N - 1) * p.ldb + p.K) * 2;
-    if (conv) ab = (unsigned long long)((long long)p.M / ((long long)p.Hout * p.Wout)) * p.Hin * p.Win * p.Cin * 2;   // batch * Hin * Win * Cin
-    else {
-      const unsigned long long last = p.panel_rows ? (unsigned long long)((p.M - 1) / p.panel_rows) * p.panel_stride + p.panel_off + (p.M - 1) % p.panel_rows : (unsigned long long)(p.M - 1);
-      ab = (last * p.lda + p.K1) * 2;
-      if (p.A2) a2b = (last * p.lda2 + (p.K - p.K1)) * 2;
-    }
-    buf_ok = ab < lim && a2b < lim && bb < lim;
-    if (tile == 512 && (!allow256 || !buf_ok || !whole_k)) tile = 128;
-    if (tile == 2320 && (!buf_ok || !whole_k || p.N % 320 != 0)) tile = 128;      // (ragged N is only exercised for the narrower tiles)
-    if (tile == 640 && (!buf_ok || p.K % BK != 0)) tile = 128;
-    pl.a_bytes = (unsigned)(buf_ok ? ab : 0); pl.a2_bytes = (unsigned)(buf_ok ? a2b : 0); pl.b_bytes = (unsigned)(buf_ok ? bb : 0);
-    if (!buf_ok && tile != 64) { tile = 128; kt32 = false; stages = 2; }      // the register-staged fallback exists as 128x128 and 64x64 only
+  const unsigned long long lim = 0xFFFF0000ull;
+  unsigned long long ab, a2b = 0, bb = ((unsigned long long)(p.N - 1) * p.ldb + p.K) * 2;
+  if (conv) ab = (unsigned long long)((long long)p.M / ((long long)p.Hout * p.Wout)) * p.Hin * p.Win * p.Cin * 2;   // batch * Hin * Win * Cin
+  else {
+    const unsigned long long last = p.panel_rows ? (unsigned long long)((p.M - 1) / p.panel_rows) * p.panel_stride + p.panel_off + (p.M - 1) % p.panel_rows : (unsigned long long)(p.M - 1);
+    ab = (last * p.lda + p.K1) * 2;
+    if (p.A2) a2b = (last * p.lda2 + (p.K - p.K1)) * 2;
   }
-  // 256 = 256x128, 160 = 128x160, 512 = 256x256 ping-pong, 640 = 512x128 ping-pong, 1128 / 1160 = persistent 256x128 / 256x160
-  const int tm = tile == 160 ? 128 : (tile == 512 || tile >= 1000 ? 256 : (tile == 640 ? 512 : tile));
-  const int tn = tile == 256 ? 128 : (tile == 512 ? 256 : (tile == 640 ? 128 : (tile >= 1000 ? tile % 1000 : tile)));
-  const bool pingpong = tile == 512 || tile == 2320;      // one 512-thread workgroup per CU
-  const int gx = cdiv(p.N, tn), gy = cdiv(p.M, tm);
-  // --- split-K: only when the grid underfills the chip and K is long ---
+  buf_ok = ab < lim && a2b < lim && bb < lim;
+  if ((v->caps & CAP_WHOLE_K) && !whole_k) fall(128);
+  if ((v->caps & CAP_WHOLE_N) && p.N % v->tn != 0) fall(128);
+  a_bytes = (unsigned)(buf_ok ? ab : 0); a2_bytes = (unsigned)(buf_ok ? a2b : 0); b_bytes = (unsigned)(buf_ok ? bb : 0);
+  if (!buf_ok && v->tm >= 128) { tile = 128; stages = 2; kt32 = false; }      // the register-staged fallback exists as 128x128 and 64x64 only
+}
+
+// --- stage 4: split-K — only when the grid underfills the chip and K is long.
+int Planner::choose_splitk() const {
+  const Variant& v = *shape;
   int splitk = splitk_req;
-  if (tile >= 1000 && tile < 2000) splitk = 1;
-  if (p.panel_rows) splitk = 1;
-  if (splitk <= 0 && model_splitk > 0 && (tile == 64 || tile == 128 || tile == 160)) splitk = model_splitk;
+  if (!(v.caps & CAP_SPLITK) || p.panel_rows) splitk = 1;
+  if (splitk <= 0 && model_splitk > 0 && (v.caps & CAP_STAGED)) splitk = model_splitk;
   if (splitk <= 0) {
     splitk = 1;
     const long long tiles = (long long)gx * gy * batch;
-    if (pingpong && (tiles < 256 || !r2_rules)) {
+    if (v.caps & CAP_ONE_PER_CU) {
       if (tiles < 256) {
         splitk = (int)(256 / tiles);                 // one 512-thread workgroup per CU: fill one round
         if (splitk > nkt / 16) splitk = nkt / 16;
       }                                              // (a second, partial round is not split: 3 splits of 320 tiles measured 545 vs 482 us)
-    } else if (tile >= 128 && tiles < 512 && nkt >= 32) {
+    } else if (v.tm >= 128 && tiles < 512 && nkt >= 32) {
       // 2 workgroups/CU = 512 slots: aim at one full round (<= 256 tiles) or two (measured, tools/sweep_sk.py: 8x8 convs
       // 80 tiles -> 6 splits -16..19 %, 16x16 convs 320 tiles -> 3 splits -10..17 %), keeping >= 16 K-tiles per split
       splitk = (int)((tiles <= 256 ? 512 : 1024) / tiles);
       if (splitk > 8) splitk = 8;
       if (splitk > nkt / 16) splitk = nkt / 16;
       if (tiles > 256 && nkt < 128) splitk = 1;      // the second round only pays on long K (4096x1280x5120: 3 splits +4 %)
-    } else if (tile == 64 && tiles < 256 && nkt >= 32) {
+    } else if (v.tm < 128 && tiles < 256 && nkt >= 32) {
       splitk = (int)((512 + tiles - 1) / tiles);
       if (splitk > nkt / 16) splitk = nkt / 16;
     }
     if (splitk < 1) splitk = 1;
   }
-  if (splitk > nkt) splitk = nkt;
-  pl.ktiles_per_split = cdiv(nkt, splitk);
-  pl.splitk = cdiv(nkt, pl.ktiles_per_split);
-  pl.tile = tile; pl.stages = stages; pl.kt32 = kt32; pl.general_epi = general_epi; pl.buf_ok = buf_ok;
-  pl.tm = tm; pl.tn = tn; pl.gx = gx; pl.gy = gy;
-  return pl;
+  return splitk > nkt ? nkt : splitk;
 }
 
-size_t plan_workspace_bytes(const GemmPlan& pl, const GemmArgs& p, int batch) {
-  return (pl.splitk > 1 || p.reduce_batch) ? (size_t)pl.splitk * batch * p.M * p.N * sizeof(float) : 0;
+GemmPlan plan_gemm(const GemmArgs& p, bool conv, int tile_hint, int splitk_req, int batch) {
+  const bool whole_k = p.K % BK == 0 && (!p.A2 || p.K1 % BK == 0), dma = dma_allowed();
+  Planner s = {{}, p, conv, splitk_req, batch, cdiv(p.K, BK), whole_k, dma && whole_k && batch == 1 && !p.reduce_batch && splitk_req <= 1, dma, 0};
+  s.general_epi = (p.flags & E4T_ACT_GELU) || (p.rowbias && p.rows_per_batch % 32 != 0);
+  if (!s.decode_hint(tile_hint)) s.choose_tile();
+  s.apply_capabilities();
+  s.shape = s.row();
+  // the register-staged row of the tile; PRESERVED OVERSIGHT (see apply_capabilities): a tile without one runs the 64 x 64 row
+  const Variant* reg = find_variant(s.tile, false, 2, false);
+  s.run = dma && s.buf_ok ? s.shape : reg ? reg : find_variant(64, false, 2, false);
+  s.gx = cdiv(p.N, s.shape->tn); s.gy = cdiv(p.M, s.shape->tm);
+  s.ktiles_per_split = cdiv(s.nkt, s.choose_splitk());
+  s.splitk = cdiv(s.nkt, s.ktiles_per_split);
+  return s;
 }
 
 // Tail rows (gemm_common.h, gemm_tail): a dense GEMM whose M is a multiple of 128 plus at most 32 rows — the CLIP-ViT's 16 x 257 =
 // 4112 token rows — is planned for its first M - r rows; the r tail rows are computed at the end of the same launch.  Returns the plan
 // and sets `tail` (0: the ordinary plan over all M rows).  The plan of the M - r rows must be a single pass of one of the LDS-DMA kernels
-// that carry the tail code (128 x 160, 256 x 256 and 256 x 320 tiles): anything else falls back to the plan over all rows.
+// that carry the tail code (CAP_TAIL: 128 x 160, 256 x 256 and 256 x 320 tiles): anything else falls back to the plan over all rows.
+// (Without the tail stage: README recipe 134.1 vs 133.5 ms, C4 139.6 vs 139.4, headline step equal; profiles/r05_ab.)
 GemmPlan plan_gemm_tail(const GemmArgs& p, bool conv, int tile_hint, int splitk_req, int batch, int& tail) {
-  const bool no_tail = false;              // (without the tail stage: README recipe 134.1 vs 133.5 ms, C4 139.6 vs 139.4, headline step equal; profiles/r05_ab)
-  static const bool use_dma = getenv("E4T_GEMM_REGSTAGE") == nullptr;
   tail = 0;
   const int r = p.M % 128;
-  if (!no_tail && use_dma && !conv && batch == 1 && !p.reduce_batch && !p.A2 && !p.panel_rows && !p.colstats && splitk_req <= 1 && r > 0 && r <= 32 &&
+  if (dma_allowed() && !conv && batch == 1 && !p.reduce_batch && !p.A2 && !p.panel_rows && !p.colstats && splitk_req <= 1 && r > 0 && r <= 32 &&
       p.M - r >= 1024 && p.K % 16 == 0 && p.lda % 8 == 0 && p.ldb % 8 == 0 && (((uintptr_t)p.A | (uintptr_t)p.B) & 15) == 0) {
     GemmArgs q = p;
     q.M = p.M - r;
     const GemmPlan pl = plan_gemm(q, conv, tile_hint, splitk_req, batch);
-    const bool kernel_ok = pl.buf_ok && pl.splitk == 1 && (pl.tile == 160 || pl.tile == 512 || pl.tile == 2320);      // the kernels that carry gemm_tail()
-    if (kernel_ok) { tail = r; return pl; }
+    if (pl.buf_ok && pl.splitk == 1 && (pl.run->caps & CAP_TAIL)) { tail = r; return pl; }
   }
   return plan_gemm(p, conv, tile_hint, splitk_req, batch);
 }
 
-// the float4 reduction: fp32 C, nothing in the epilogue but alpha (and accumulate), 16-byte aligned rows
-bool reduce4f_ok(const GemmArgs& p) {
-  return p.ws && (p.flags & E4T_OUT_F32) && !(p.flags & E4T_ACT_GELU) && !p.bias && !p.rowbias && !p.residual && p.N % 4 == 0 && p.ldc % 4 == 0 &&
-         p.strideC % 4 == 0 && (((uintptr_t)p.C | (uintptr_t)p.ws) & 15) == 0;
+// bf16 C (and residual) with nothing but whole 16-byte groups in every row: what the 8-columns-per-thread epilogues need
+bool bf16_rows_aligned16(const GemmArgs& p) {
+  return !(p.flags & (E4T_OUT_F32 | E4T_ACCUM | E4T_RES_F32)) && p.N % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 &&
+         (!p.residual || (p.ldr % 8 == 0 && ((uintptr_t)p.residual & 15) == 0));
+}
+
+struct ReduceKernel { void (*fn)(GemmArgs, int); const char* text; int cols; };      // cols: columns per thread
+// the 8-columns-per-thread kernel when C is bf16 and everything it touches is 16-byte aligned (vec8); the float4 reduction for fp32 C
+// with nothing in the epilogue but alpha (and accumulate) and 16-byte aligned rows; else the scalar kernel
+const ReduceKernel& reduce_kernel(const GemmArgs& p, bool vec8) {
+  static const ReduceKernel k8 = {splitk_reduce8_kernel, "splitk_reduce8_kernel", 8}, k4f = {splitk_reduce4f_kernel, "splitk_reduce4f_kernel", 4},
+                            k1 = {splitk_reduce_kernel, "splitk_reduce_kernel", 1};
+  const bool f4 = p.ws && (p.flags & E4T_OUT_F32) && !(p.flags & E4T_ACT_GELU) && !p.bias && !p.rowbias && !p.residual && p.N % 4 == 0 && p.ldc % 4 == 0 &&
+                  p.strideC % 4 == 0 && (((uintptr_t)p.C | (uintptr_t)p.ws) & 15) == 0;
+  return vec8 ? k8 : f4 ? k4f : k1;
+}
+// (the log line of a launch's reduction is written with the launch's own, before anything is launched)
+void log_splitk_reduce(const GemmArgs& p, int nz, int slabs, bool vec8) {
+  E4T_LOG_LAUNCH("%s|M%d N%d nz%d|%.0f|0", reduce_kernel(p, vec8).text, p.M, p.N, nz,
+                 4.0 * (double)p.M * p.N * slabs + ((p.flags & E4T_OUT_F32) ? 4.0 : 2.0) * (double)p.M * p.N);
+}
+int launch_splitk_reduce(const GemmArgs& p, int nz, int batch_dim, bool vec8, hipStream_t st) {
+  const ReduceKernel& k = reduce_kernel(p, vec8);
+  const size_t total = (size_t)p.M * p.N;
+  int blocks = (int)((total / k.cols + 255) / 256);
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(k.fn, dim3(blocks, batch_dim), dim3(256), 0, st, p, nz);
+  E4T_CHECK_LAUNCH("splitk_reduce_kernel");
+  return 0;
 }
 
 int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
   int tail = 0;
   const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
+  const Variant& v = *pl.run;
   const int m_all = p.M;                 // (launch log: the caller's shape)
   if (tail) { p.M -= tail; p.tail_row0 = p.M; p.tail_rows = tail; }      // the tile grid covers [0, M - tail); gemm_tail() the rest
-  const int nkt = cdiv(p.K, BK);
-  const int tile = pl.tile, stages = pl.stages, gx = pl.gx, gy = pl.gy;
-  const bool kt32 = pl.kt32, general_epi = pl.general_epi, buf_ok = pl.buf_ok;
   int splitk = pl.splitk;
   p.ktiles_per_split = pl.ktiles_per_split;
   p.a_bytes = pl.a_bytes; p.a2_bytes = pl.a2_bytes; p.b_bytes = pl.b_bytes;
   // stride-1 3x3 convs walk K channel-chunk-major (gemm_common.h, cm_step) in every DMA kernel
-  const bool tap_major = false;            // (tap-major K order: 109.7 vs 107.5 ms per step, 2.4-5.2 x the HBM traffic; profiles/r03_ab/r03p_*)
-  p.chan_major = conv && !tap_major && buf_ok && p.mode == E4T_CONV_S1 && p.Cin % BK == 0 && p.K == 9 * p.Cin && batch == 1 &&
+  // (tap-major K order: 109.7 vs 107.5 ms per step, 2.4-5.2 x the HBM traffic; profiles/r03_ab/r03p_*)
+  p.chan_major = conv && pl.buf_ok && p.mode == E4T_CONV_S1 && p.Cin % BK == 0 && p.K == 9 * p.Cin && batch == 1 &&
                  (unsigned long long)p.a_bytes + (unsigned long long)(p.Win + 1) * p.Cin * 2 < 0xFFFF0000ull;
-  static const bool allow256 = getenv("E4T_GEMM_REGSTAGE") == nullptr;
-  (void)allow256;
   const bool need_ws = splitk > 1 || p.reduce_batch;
   const size_t need = (size_t)splitk * batch * p.M * p.N * sizeof(float);
   if (need_ws && (p.ws == nullptr || ws_bytes < need)) {
     if (splitk_req > 1 || p.reduce_batch)
       E4T_FAIL(-12, "gemm: split-K=%d batch=%d needs %zu workspace bytes, have %zu", splitk, batch, need, ws_bytes);
     splitk = 1;  // auto mode: fall back to a single pass rather than fail
-    p.ktiles_per_split = nkt;
+    p.ktiles_per_split = cdiv(p.K, BK);
   }
   if (!(splitk > 1 || p.reduce_batch)) p.ws = nullptr;
   p.splitk = splitk;
   p.group_m = 8;                           // row panels per raster group (swept in round 4: profiles/r04_ab/r04f_*)
-  p.fast_epi = !(p.flags & (E4T_OUT_F32 | E4T_ACCUM | E4T_RES_F32)) && p.N % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 &&
-               (p.strideC % 8 == 0) && (!p.residual || (p.ldr % 8 == 0 && ((uintptr_t)p.residual & 15) == 0));
+  p.fast_epi = bf16_rows_aligned16(p) && p.strideC % 8 == 0;
   p.fast_f32 = (p.flags & E4T_OUT_F32) && !(p.flags & E4T_ACCUM) && !p.rowbias && (!p.residual || (p.flags & E4T_RES_F32)) &&
-               (!(p.flags & E4T_ACT_GELU) || general_epi);
+               (!(p.flags & E4T_ACT_GELU) || pl.general_epi);
   if (p.colstats && (p.ws || !p.fast_epi || p.M % 32 != 0 || batch != 1)) p.colstats = nullptr;   // only the bf16 single-pass epilogue produces them
-  const int stats_written = p.colstats != nullptr;
-  // split-K / batch reduction: the 8-columns-per-thread kernel when C is bf16 and everything it touches is 16-byte aligned
-  const bool vec8 = p.ws && !(p.flags & (E4T_OUT_F32 | E4T_ACCUM | E4T_RES_F32)) && p.N % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 &&
-                    p.strideC % 8 == 0 && (!p.residual || (p.ldr % 8 == 0 && ((uintptr_t)p.residual & 15) == 0)) &&
+  const int stats_written = p.colstats != nullptr && (v.caps & CAP_COLSTATS);
+  // split-K / batch reduction: 8 columns per thread when bias, row bias and workspace are 16-byte aligned too
+  const bool vec8 = p.ws && bf16_rows_aligned16(p) && p.strideC % 8 == 0 &&
                     (!p.bias || (((uintptr_t)p.bias & 15) == 0 && p.strideBias % 4 == 0)) &&
                     (!p.rowbias || (((uintptr_t)p.rowbias & 15) == 0 && p.ldrb % 4 == 0)) && ((uintptr_t)p.ws & 15) == 0;
-  dim3 grid(gx, gy, splitk * batch), block(256);
-  static const bool use_dma = getenv("E4T_GEMM_REGSTAGE") == nullptr;   // A/B switch: register-staged reference kernel
+  const int nz = p.reduce_batch ? splitk * batch : splitk;
+  const KernelEntry& k = select_entry(v, p, conv, pl.general_epi, splitk, batch);
+  if (!k.text) E4T_FAIL(-22, "gemm: no kernel is built for tile %d (%s, GENERAL %d)", pl.tile, conv ? "conv" : "gemm", (int)pl.general_epi);
   if (e4t_launch_log_enabled()) {
     // algorithmic bytes: every operand element once (conv: the input map once, not once per tap), the output once
     const double osz = (p.flags & E4T_OUT_F32) ? 4.0 : 2.0;
@@ -2357,158 +2511,19 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
     double by = 2.0 * a_el + 2.0 * (double)p.N * p.K * (p.strideB || batch == 1 ? batch : 1) + osz * (double)p.M * p.N * (p.reduce_batch ? 1 : batch);
     if (p.residual) by += ((p.flags & E4T_RES_F32) ? 4.0 : 2.0) * (double)p.M * p.N;
     if (p.flags & E4T_ACCUM) by += osz * (double)p.M * p.N;
-    const char* sym = !(use_dma && buf_ok) ? "gemm_kernel"
-                      : tile == 512 && conv && conv_pps_ok(p, batch) ? (general_epi ? "gemm_pps_kernel<true>" : "gemm_pps_kernel<false>")
-                      : tile == 512 ? (general_epi ? (conv ? (p.chan_major ? "gemm_pp_kernel<1, true, true>" : "gemm_pp_kernel<1, true, false>") : "gemm_pp_kernel<0, true, false>")
-                                                   : (conv ? (p.chan_major ? "gemm_pp_kernel<1, false, true>" : "gemm_pp_kernel<1, false, false>") : "gemm_pp_kernel<0, false, false>"))
-                      : tile == 640 ? (conv ? "gemm_pt_kernel<1>" : "gemm_pt_kernel<0>")
-                      : tile == 256 && !kt32 ? (conv ? "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 64>" : "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 64>")
-                      : tile == 256 ? (conv ? (conv_strip_ok(p, splitk, batch) ? "conv_strip_kernel<2>" : "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32>")
-                                            : "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32>")
-                      : nullptr;
-    char symbuf[64];
-    if (!sym && tile >= 2000) {
-      snprintf(symbuf, sizeof(symbuf), "gemm_pq_kernel<%d, %d, %s>", conv ? 1 : 0, tile - 2000, general_epi ? "true" : "false");
-      sym = symbuf;
-    }
-    if (!sym && tile >= 1000) {
-      snprintf(symbuf, sizeof(symbuf), "gemm_ps_kernel<%d, %d, %s>", conv ? 1 : 0, tile - 1000, general_epi ? "true" : "false");
-      sym = symbuf;
-    }
-    if (!sym) {
-      snprintf(symbuf, sizeof(symbuf), "gemm_dma_kernel<%d, %d, %d, %d, %d, %d, %s, %d>", tile == 64 ? 64 : 128, tile == 160 ? 160 : tile, tile == 64 ? 2 : 4,
-               tile == 160 ? 1 : 2, conv ? 1 : 0, stages, general_epi ? "true" : "false", kt32 ? 32 : 64);      // as rocprofv3 prints the symbol
-      sym = symbuf;
-    }
-    if (conv) E4T_LOG_LAUNCH("%s|conv mode%d %dx%d->%dx%d Cin%d Cout%d M%d splitk%d|%.0f|%.0f", sym, p.mode, p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.N,
+    if (conv) E4T_LOG_LAUNCH("%s|conv mode%d %dx%d->%dx%d Cin%d Cout%d M%d splitk%d|%.0f|%.0f", k.text, p.mode, p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.N,
                              p.M, splitk, by, 2.0 * p.M * p.N * (double)p.K);
-    else E4T_LOG_LAUNCH("%s|gemm M%d N%d K%d batch%d splitk%d flags%d|%.0f|%.0f", sym, m_all, p.N, p.K, batch, splitk, p.flags,
+    else E4T_LOG_LAUNCH("%s|gemm M%d N%d K%d batch%d splitk%d flags%d|%.0f|%.0f", k.text, m_all, p.N, p.K, batch, splitk, p.flags,
                         by + (double)tail * (2.0 * p.K + (osz + (p.residual ? ((p.flags & E4T_RES_F32) ? 4.0 : 2.0) : 0.0)) * p.N), 2.0 * m_all * p.N * (double)p.K * batch);
-    if (p.ws) E4T_LOG_LAUNCH("%s|M%d N%d nz%d|%.0f|0", vec8 ? "splitk_reduce8_kernel" : reduce4f_ok(p) ? "splitk_reduce4f_kernel" : "splitk_reduce_kernel",
-                             p.M, p.N, p.reduce_batch ? splitk * batch : splitk, 4.0 * (double)p.M * p.N * splitk * batch + osz * (double)p.M * p.N);
+    if (p.ws) log_splitk_reduce(p, nz, splitk * batch, vec8);
   }
-  if (p.panel_rows && !(use_dma && buf_ok && tile == 2320 && splitk == 1 && !p.ws))
-    E4T_FAIL(-22, "gemm: row panels need the 256 x 320 ping-pong tile (N %% 320 == 0, K %% 64 == 0, no split-K); the plan chose tile %d", tile);
-  if (use_dma && buf_ok) {
-    if (tile == 2320) {
-      block = dim3(512);
-      if (conv) hipLaunchKernelGGL((gemm_pq_kernel<1, 320, false>), grid, block, 0, st, p);
-      else if (general_epi) hipLaunchKernelGGL((gemm_pq_kernel<0, 320, true>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((gemm_pq_kernel<0, 320, false>), grid, block, 0, st, p);
-#ifdef E4T_EXPERIMENTAL
-    } else if (tile >= 1000) {
-      static const bool ps_pre = getenv("E4T_PS_PRE") == nullptr || atoi(getenv("E4T_PS_PRE")) != 0;      // A/B switch
-      p.ps_pre = ps_pre && p.fast_epi && nkt >= 2 && (!p.rowbias || p.rows_per_batch % 256 == 0);
-      const int rc = e4t_launch_gemm_ps(&p, conv ? 1 : 0, tile - 1000, general_epi ? 1 : 0, device_cu_count(), st);
-      if (rc < 0) return rc;
-#endif
-    } else if (tile == 512) {
-      block = dim3(512);
-      if (conv && conv_pps_ok(p, batch)) {
-        if (general_epi) hipLaunchKernelGGL((gemm_pps_kernel<true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_pps_kernel<false>), grid, block, 0, st, p);
-      } else if (general_epi) {
-        if (conv && p.chan_major) hipLaunchKernelGGL((gemm_pp_kernel<1, true, true>), grid, block, 0, st, p);
-        else if (conv) hipLaunchKernelGGL((gemm_pp_kernel<1, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_pp_kernel<0, true>), grid, block, 0, st, p);
-      } else {
-#ifdef E4T_EXPERIMENTAL
-        // measured and rejected (round 6): the 16-wave 256 x 256 strip kernel EQUALS the ping-pong kernel on every conv shape of the step (1072 / 1007 /
-        // 526 / 254 / 126 us against 1046-1082 / 995-1011 / 515-531 / 253 / 125-128) although it fills a third of the A bytes — with 64 x 64 wave tiles
-        // it needs one fragment ds_read per MFMA, 125 B/clk/CU of LDS reads at the MFMA peak against the LDS's 128
-        static const bool strip256 = getenv("E4T_CONV_STRIP256") != nullptr && atoi(getenv("E4T_CONV_STRIP256")) != 0;
-        if (conv && strip256 && conv_strip_ok(p, splitk, batch)) hipLaunchKernelGGL(conv_strip_kernel<4>, grid, dim3(1024), 0, st, p);
-        else
-#endif
-        if (conv && p.chan_major) hipLaunchKernelGGL((gemm_pp_kernel<1, false, true>), grid, block, 0, st, p);
-        else if (conv) hipLaunchKernelGGL((gemm_pp_kernel<1>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_pp_kernel<0>), grid, block, 0, st, p);
-      }
-#ifdef E4T_EXPERIMENTAL
-    } else if (tile == 640) {
-      block = dim3(512);
-      if (conv) hipLaunchKernelGGL((gemm_pt_kernel<1>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((gemm_pt_kernel<0>), grid, block, 0, st, p);
-#endif
-    } else if (tile == 256 && kt32) {
-      block = dim3(512);       // experimental (5256): 256 x 128 with 32-wide K-tiles, 3 x 24 KiB stages = two workgroups per CU
-      if (conv && conv_strip_ok(p, splitk, batch)) hipLaunchKernelGGL(conv_strip_kernel<2>, grid, block, 0, st, p);
-      else if (conv) hipLaunchKernelGGL((gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32>), grid, block, 0, st, p);
-#ifdef E4T_EXPERIMENTAL
-    } else if (tile == 256) {
-      block = dim3(512);
-      if (conv) hipLaunchKernelGGL((gemm_dma_kernel<256, 128, 4, 2, 1, 3>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((gemm_dma_kernel<256, 128, 4, 2, 0, 3>), grid, block, 0, st, p);
-#endif
-    } else {
-      // 64 / 128 / 160 tiles: 2 LDS stages and 2 workgroups per CU by default; 3 or 4 stages (one workgroup per CU, 2-3 K-tiles
-      // in flight) when the grid cannot give a CU two workgroups anyway — see the stage choice above
-#define E4T_LAUNCH_DMA_STAGES(BM_, BN_, WGM_, WGN_)                                                                       \
-    if (!general_epi && stages == 4) { if (conv) hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 1, 4>), grid, block, 0, st, p); \
-                       else hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 0, 4>), grid, block, 0, st, p); }    \
-    else if (!general_epi && stages == 3) { if (conv) hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 1, 3>), grid, block, 0, st, p); \
-                            else hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 0, 3>), grid, block, 0, st, p); } \
-    else
-#define E4T_LAUNCH_DMA(BM_, BN_, WGM_, WGN_, NT_)                                                                         \
-  do {                                                                                                                   \
-    block = dim3(NT_);                                                                                                   \
-    E4T_LAUNCH_DMA_STAGES(BM_, BN_, WGM_, WGN_)                                                                          \
-    if (general_epi) { if (conv) hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 1, 2, true>), grid, block, 0, st, p); \
-                            else hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 0, 2, true>), grid, block, 0, st, p); } \
-    else { if (conv) hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 1, 2>), grid, block, 0, st, p);            \
-           else hipLaunchKernelGGL((gemm_dma_kernel<BM_, BN_, WGM_, WGN_, 0, 2>), grid, block, 0, st, p); }               \
-  } while (0)
-      // 128x128: 8 waves (wave tile 32x64): ~4 waves/SIMD at 2 workgroups/CU hide the DMA/LDS latency that the 4-wave
-      // version of the same tile exposed (measured +5..18 % on every E4T shape, 8192^3: 956 -> 980 TF)
-#ifdef E4T_EXPERIMENTAL
-      if (kt32 && tile == 128) {
-        block = dim3(512);
-        if (conv) hipLaunchKernelGGL((gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 32>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 32>), grid, block, 0, st, p);
-      } else if (kt32 && tile == 64) {
-        block = dim3(256);
-        if (conv) hipLaunchKernelGGL((gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 32>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 32>), grid, block, 0, st, p);
-      } else
-#endif
-      if (tile == 64 && general_epi && stages == 3) {
-        block = dim3(256);
-        if (conv) hipLaunchKernelGGL((gemm_dma_kernel<64, 64, 2, 2, 1, 3, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((gemm_dma_kernel<64, 64, 2, 2, 0, 3, true>), grid, block, 0, st, p);
-      } else if (tile == 160) E4T_LAUNCH_DMA(128, 160, 4, 1, 256);
-      else if (tile == 128) E4T_LAUNCH_DMA(128, 128, 4, 2, 512);
-      else E4T_LAUNCH_DMA(64, 64, 2, 2, 256);
-#undef E4T_LAUNCH_DMA
-#undef E4T_LAUNCH_DMA_STAGES
-    }
-  } else if (tile == 128) {
-    if (conv) hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 2, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((gemm_kernel<128, 128, 2, 2, 0>), grid, block, 0, st, p);
-  } else {
-    if (conv) hipLaunchKernelGGL((gemm_kernel<64, 64, 2, 2, 1>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((gemm_kernel<64, 64, 2, 2, 0>), grid, block, 0, st, p);
-  }
+  if (p.panel_rows && !((v.caps & CAP_PANELS) && splitk == 1 && !p.ws))
+    E4T_FAIL(-22, "gemm: row panels need the 256 x 320 ping-pong tile (N %% 320 == 0, K %% 64 == 0, no split-K); the plan chose tile %d", pl.tile);
+  if (!(v.caps & CAP_PERSISTENT)) hipLaunchKernelGGL(k.fn, dim3(pl.gx, pl.gy, splitk * batch), dim3(k.threads), 0, st, p);
+  else if (const int rc = launch_persistent(p, v, conv, pl.general_epi, st); rc < 0) return rc;
   E4T_CHECK_LAUNCH("gemm_kernel");
-  if (p.ws) {
-    const size_t total = (size_t)p.M * p.N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    const int nz = p.reduce_batch ? splitk * batch : splitk;
-    if (vec8) {
-      int b8 = (int)((total / 8 + 255) / 256);
-      if (b8 > 2048) b8 = 2048;
-      hipLaunchKernelGGL(splitk_reduce8_kernel, dim3(b8, p.reduce_batch ? 1 : batch), dim3(256), 0, st, p, nz);
-    } else if (reduce4f_ok(p)) {
-      int b4 = (int)((total / 4 + 255) / 256);
-      if (b4 > 2048) b4 = 2048;
-      hipLaunchKernelGGL(splitk_reduce4f_kernel, dim3(b4, p.reduce_batch ? 1 : batch), dim3(256), 0, st, p, nz);
-    } else {
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, p.reduce_batch ? 1 : batch), dim3(256), 0, st, p, nz);
-    }
-    E4T_CHECK_LAUNCH("splitk_reduce_kernel");
-  }
-  return (use_dma && buf_ok) ? stats_written : 0;
+  if (const int rc = p.ws ? launch_splitk_reduce(p, nz, p.reduce_batch ? 1 : batch, vec8, st) : 0; rc < 0) return rc;
+  return stats_written;
 }
 
 }  // namespace
@@ -2554,10 +2569,11 @@ int tn_splitk(int M, int N, int K, int req) {
   return cdiv(nkt, cdiv(nkt, splitk));
 }
 
+// 5000 + tile for 32-wide K-tiles; `stages` only where it is a choice (the 64-wide 64 / 128 / 160 tiles)
 void export_plan(const GemmPlan& pl, const GemmArgs& p, int batch, e4t_gemm_plan_t* out, int tail = 0) {
-  out->tile = pl.kt32 ? 5000 + pl.tile : pl.tile; out->tile_m = pl.tm; out->tile_n = pl.tn; out->splitk = pl.splitk;
-  out->workspace_bytes = plan_workspace_bytes(pl, p, batch);
-  out->tail_rows = tail; out->stages = (!pl.kt32 && (pl.tile == 64 || pl.tile == 128 || pl.tile == 160)) ? pl.stages : 0;
+  out->tile = pl.kt32 ? 5000 + pl.tile : pl.tile; out->tile_m = pl.shape->tm; out->tile_n = pl.shape->tn; out->splitk = pl.splitk;
+  out->workspace_bytes = (pl.splitk > 1 || p.reduce_batch) ? (size_t)pl.splitk * batch * p.M * p.N * sizeof(float) : 0;
+  out->tail_rows = tail; out->stages = (!pl.kt32 && (pl.shape->caps & CAP_STAGED)) ? pl.stages : 0;
 }
 
 }  // namespace
@@ -2619,7 +2635,7 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   E4T_REQUIRE(!(d->flags & E4T_ACT_GELU), "gemm_tn: the GELU epilogue is not built for the TN kernel");
   E4T_REQUIRE(d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && ((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0,
               "gemm_tn: M, N, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
-  GemmArgs p;
+  GemmArgs p;      // (not fill_gemm_args: the fields the TN kernel does not support — lda2, strides, row panels, ... — stay zero whatever the caller left there)
   memset(&p, 0, sizeof(p));
   p.zslab = -1;
   p.A = (const bf16_t*)d->A; p.lda = d->lda; p.B = (const bf16_t*)d->B; p.ldb = d->ldb;
@@ -2645,32 +2661,17 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   p.splitk = splitk;
   p.group_m = 8;
   p.xcd3 = splitk > 1;                     // (2-D raster: gemm_tn M960 N320 K65536 90.6 vs 67.4 us)
-  p.fast_epi = !(p.flags & (E4T_OUT_F32 | E4T_ACCUM | E4T_RES_F32)) && p.N % 8 == 0 && p.ldc % 8 == 0 && ((uintptr_t)p.C & 15) == 0 &&
-               (!p.residual || (p.ldr % 8 == 0 && ((uintptr_t)p.residual & 15) == 0));
+  p.fast_epi = bf16_rows_aligned16(p);
   hipStream_t st = (hipStream_t)stream;
   if (e4t_launch_log_enabled()) {
     const double osz = (p.flags & E4T_OUT_F32) ? 4.0 : 2.0;
     E4T_LOG_LAUNCH("gemm_tn_kernel|gemm_tn M%d N%d K%d splitk%d flags%d|%.0f|%.0f", p.M, p.N, p.K, splitk, p.flags,
                    2.0 * (double)p.K * (p.M + p.N) + osz * (double)p.M * p.N * ((p.flags & E4T_ACCUM) ? 2 : 1), 2.0 * p.M * p.N * (double)p.K);
-    if (p.ws) E4T_LOG_LAUNCH("%s|M%d N%d nz%d|%.0f|0", reduce4f_ok(p) ? "splitk_reduce4f_kernel" : "splitk_reduce_kernel", p.M, p.N, splitk,
-                             4.0 * (double)p.M * p.N * splitk + osz * (double)p.M * p.N);
+    if (p.ws) log_splitk_reduce(p, splitk, splitk, false);
   }
   hipLaunchKernelGGL(gemm_tn_kernel, dim3(gx, gy, splitk), dim3(512), 0, st, p);
   E4T_CHECK_LAUNCH("gemm_tn_kernel");
-  if (p.ws) {
-    const size_t total = (size_t)p.M * p.N;
-    int blocks = (int)((total + 255) / 256);
-    if (blocks > 2048) blocks = 2048;
-    if (reduce4f_ok(p)) {
-      int b4 = (int)((total / 4 + 255) / 256);
-      if (b4 > 2048) b4 = 2048;
-      hipLaunchKernelGGL(splitk_reduce4f_kernel, dim3(b4, 1), dim3(256), 0, st, p, splitk);
-    } else {
-      hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks, 1), dim3(256), 0, st, p, splitk);
-    }
-    E4T_CHECK_LAUNCH("splitk_reduce_kernel");
-  }
-  return 0;
+  return p.ws ? launch_splitk_reduce(p, splitk, 1, false, st) : 0;
 }
 
 extern "C" int e4t_conv3x3(const e4t_conv_desc* d, e4t_stream stream) {

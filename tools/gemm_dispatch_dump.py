@@ -1,0 +1,291 @@
+#!/usr/bin/env python
+"""What the GEMM / 3x3-conv host code decides for a fixed corpus of descriptors, one line per descriptor:
+
+    <kind> <descriptor> -> <tile tile_m tile_n splitk workspace_bytes tail_rows stages> [| rc <rc> <error text> | <launch-log lines>]
+
+Two builds of the library (E4T_LIB=<path to libe4t_hip.so> selects another one) decide alike iff their dumps are byte-identical:
+
+    python tools/gemm_dispatch_dump.py > new.txt;  E4T_LIB=/path/to/old/libe4t_hip.so python tools/gemm_dispatch_dump.py > old.txt;  diff old.txt new.txt
+
+The plan half (e4t_gemm_plan / e4t_conv3x3_plan / e4t_gemm_tn_plan) is pure host code.  The launch half calls e4t_gemm_nt / e4t_conv3x3 /
+e4t_gemm_tn with FAKE operand pointers and the launch log on: the library writes the symbol | shape | bytes | flops line(s) of what it
+would launch and then fails with "no ROCm-capable device".  That only works — and is only safe — on a machine WITHOUT a GPU: where a
+device answers, the tool prints the plan half only and says so.  Environment switches of the library (E4T_GEMM_REGSTAGE,
+E4T_CONV_NOSTRIP, ...) are read once per process: one run per setting.
+
+    --plans            plan half only
+    --group 'gemm t160'  only that corpus group (a group = one tile hint x {gemm, conv}, 'tn', or 'step')
+    --anchor           check the 'step' group against profiles/r06_roofline_per_shape.csv: every GEMM / conv / TN launch recorded there
+                       on hardware is reproduced (symbol and shape string), every split-K reduce row by a launch's second log line
+    --record           rewrite tests/gemm_dispatch_record.txt (what tests/test_gemm_dispatch.py compares against) from this library
+"""
+import argparse
+import collections
+import csv
+import ctypes as C
+import hashlib
+import itertools
+import os
+import re
+import sys
+import tempfile
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [os.path.join(R, "e4t-diffusion_amd")]
+from e4t import _C  # noqa: E402
+
+STEP_CSV = os.path.join(R, "profiles", "r06_roofline_per_shape.csv")
+RECORD = os.path.join(R, "tests", "gemm_dispatch_record.txt")
+FAKE = 1 << 24                       # a non-NULL, 16-byte aligned "pointer": never dereferenced by host code
+OUT_F32, RES_F32, ACT_GELU, ACCUM, REDUCE_BATCH = 1, 2, 4, 8, 16
+HINTS = [0, 64, 128, 160, 256, 512, 640, 1128, 1160, 2320, 3064, 3128, 3160, 4064, 4128, 4160, 5064, 5128, 5256, 7]      # 7: not a tile code
+EXPERIMENTAL_HINTS = (256, 640, 1128, 1160, 5064, 5128)      # an E4T_EXPERIMENTAL=1 library answers these with other kernels
+Item = collections.namedtuple("Item", "group kind kw")
+
+
+def gemm_item(group, kind="gemm", **kw):
+    return Item(group, kind, kw)
+
+
+def conv_geometry(mode, H):
+    """(Hin, Hout) of a consistent square problem"""
+    return {1: (H, H), 2: (H, (H - 1) // 2 + 1), 3: (H, 2 * H), 4: (H, 2 * H), 5: (H, (H - 2) // 2 + 1)}[mode]
+
+
+def step_rows():
+    rows = [r for r in csv.reader(l for l in open(STEP_CSV) if not l.startswith("#"))][1:]
+    return [(r[0], r[1]) for r in rows if re.match(r"gemm|conv_strip|splitk_reduce", r[0])]
+
+
+def step_items():
+    """The GEMM / conv / TN launches of the training step as profiles/r06_roofline_per_shape.csv recorded them.  Its shape string does not
+    carry every descriptor field: each row comes with the combinations of the unrecorded ones (--anchor finds the one that was run)."""
+    for sym, shape in step_rows():
+        m = re.match(r"gemm M(\d+) N(\d+) K(\d+) batch(\d+) splitk(\d+) flags(\d+)$", shape)
+        if m:
+            M, N, K, b, _, fl = map(int, m.groups())
+            for cs, (rb, rpb) in itertools.product((0, 1), ((0, 0), (1, 257), (1, 77))):
+                yield Item("step", "gemm", dict(M=M, N=N, K=K, batch=b, flags=fl, colstats=cs, rowbias=rb, rows_per_batch=rpb, residual=1 if fl & RES_F32 else 0))
+        m = re.match(r"conv mode(\d) (\d+)x(\d+)->(\d+)x(\d+) Cin(\d+) Cout(\d+) M(\d+) splitk(\d+)$", shape)
+        if m:
+            mode, Hi, Wi, Ho, Wo, Ci, Co, M, _ = map(int, m.groups())
+            for cs in (0, 1):
+                yield Item("step", "conv", dict(B=M // (Ho * Wo), Hin=Hi, Win=Wi, Cin=Ci, Hout=Ho, Wout=Wo, Cout=Co, mode=mode, colstats=cs))
+        m = re.match(r"gemm_tn M(\d+) N(\d+) K(\d+) splitk(\d+) flags(\d+)$", shape)
+        if m:
+            M, N, K, _, fl = map(int, m.groups())
+            yield Item("step", "tn", dict(M=M, N=N, K=K, flags=fl))
+
+
+def corpus():
+    yield from step_items()
+    Ms = [16, 77, 257, 576, 1024, 1232, 2056, 4096, 4112, 4128, 4129, 16384, 65536]
+    Ns = [64, 72, 128, 200, 320, 640, 768, 1000, 1280, 2560, 3840, 5120, 10240]
+    Ks = [64, 72, 192, 320, 328, 640, 1280, 2560, 5120, 10240]
+    flag_sets = [dict(flags=0), dict(flags=OUT_F32), dict(flags=OUT_F32 | RES_F32, residual=1), dict(flags=ACT_GELU), dict(flags=ACCUM | OUT_F32)]
+    ms, ns, ks = [77, 1024, 4096, 4112, 65536], [128, 320, 1280, 2560], [64, 320, 1280, 10240]
+    for t in HINTS:
+        g = "gemm t%d" % t
+        for M, N, K, sk, fl in itertools.product(Ms, Ns, Ks, [0, 1, 2, 3, 8], flag_sets):
+            yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, **fl)
+        for M, N, K in itertools.product(ms, ns, ks):
+            for rpb in (77, 96, 4096):
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, rowbias=1, rows_per_batch=rpb)
+            for K1 in sorted({64, K // 128 * 64} - {0, K}):
+                if K1 < K:
+                    yield gemm_item(g, M=M, N=N, K=K, tile=t, A2=1, K1=K1, lda=K1, lda2=K - K1)
+            for sk in (0, 1):
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, colstats=1)
+            if M % 256 == 0:
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, panel_rows=256, panel_stride=257, panel_off=1)
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, panel_rows=256, panel_stride=257, panel_off=1, flags=ACT_GELU)
+            if M <= 4112:
+                for b, fl in itertools.product((2, 129), (0, OUT_F32, REDUCE_BATCH | OUT_F32)):
+                    yield gemm_item(g, M=M, N=N, K=K, tile=t, batch=b, flags=fl)
+            for sk in (0, 3):      # the scalar epilogue and the scalar reduce
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, ldc=N + 4)
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, C_off=8)
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, flags=OUT_F32, ldc=N + 2)
+            for sk, ws in itertools.product((0, 3), ("none", "small")):      # automatic: one pass; explicit: -12
+                yield gemm_item(g, M=M, N=N, K=K, tile=t, splitk=sk, ws=ws)
+        yield gemm_item(g, M=1280, N=1280, K=8, tile=t, batch=129, flags=REDUCE_BATCH | OUT_F32)      # the E4T head's weight gradient
+        for N in (320, 1280):      # an operand beyond 4 GB: the register-staged fallback
+            yield gemm_item(g, M=1 << 20, N=N, K=4096, tile=t)
+            yield gemm_item(g, M=1 << 20, N=N, K=4096, tile=t, flags=ACT_GELU)
+    Cs = [64, 128, 256, 320, 512, 640, 1280, 2560]
+    for t in HINTS:
+        g = "conv t%d" % t
+        for mode, B, H, Cin, Cout, sk in itertools.product((1, 2, 3, 4, 5), (1, 4, 16), (8, 16, 32, 64, 128), Cs, Cs, (0, 1, 3)):
+            Hin, Hout = conv_geometry(mode, H)
+            yield Item(g, "conv", dict(B=B, Hin=Hin, Win=Hin, Cin=Cin, Hout=Hout, Wout=Hout, Cout=Cout, mode=mode, tile=t, splitk=sk))
+        for mode, B, H, Cin, Cout in itertools.product((1, 2, 3), (1, 16), (8, 32, 64), (128, 320, 1280), (128, 320, 512, 1280)):
+            Hin, Hout = conv_geometry(mode, H)
+            base = dict(B=B, Hin=Hin, Win=Hin, Cin=Cin, Hout=Hout, Wout=Hout, Cout=Cout, mode=mode, tile=t)
+            yield Item(g, "conv", dict(base, flags=ACT_GELU))
+            yield Item(g, "conv", dict(base, colstats=1, rowbias=1))
+            yield Item(g, "conv", dict(base, flags=OUT_F32, residual=1))
+            yield Item(g, "conv", dict(base, ws="none"))
+            yield Item(g, "conv", dict(base, ws="small", splitk=3))
+    for M, N, K, sk, fl, ws in itertools.product((64, 320, 960, 1280), (64, 320, 1280), (512, 4096, 65536, 1 << 20), (0, 1, 4, 32),
+                                                 (dict(flags=0), dict(flags=OUT_F32), dict(flags=ACCUM | OUT_F32), dict(flags=RES_F32, residual=1)),
+                                                 ("big", "none", "small")):
+        yield Item("tn", "tn", dict(M=M, N=N, K=K, splitk=sk, ws=ws, **fl))
+
+
+def describe(kw):
+    return " ".join("%s=%s" % kv for kv in kw.items())
+
+
+def make_desc(item):
+    """ctypes descriptor of a corpus item: dense row-major operands, FAKE wherever a pointer is wanted, a large workspace offered unless ws="""
+    kw = dict(item.kw)
+    ws = kw.pop("ws", "big")
+    wskw = dict(workspace=None if ws == "none" else FAKE, workspace_bytes={"big": 1 << 40, "none": 0, "small": 16}[ws])
+    ptr = lambda name: FAKE if kw.pop(name, 0) else None
+    if item.kind == "conv":
+        return _C.ConvDesc(X=FAKE, W=FAKE, Y=FAKE, bias=ptr("bias"), residual=ptr("residual"), rowbias=ptr("rowbias"), colstats=ptr("colstats"), **wskw, **kw)
+    M, N, K = kw["M"], kw["N"], kw["K"]
+    base = dict(A=FAKE, B=FAKE, C=FAKE + kw.pop("C_off", 0), A2=ptr("A2"), bias=ptr("bias"), residual=ptr("residual"), rowbias=ptr("rowbias"), colstats=ptr("colstats"),
+                K1=K, lda=K, ldb=K, ldc=N, ldr=N, batch=1, alpha=1.0, strideA=M * K, strideB=N * K, strideC=M * N)
+    if item.kind == "tn":
+        base.update(lda=M, ldb=N, strideA=0, strideB=0, strideC=0)
+    base.update(wskw)
+    base.update(kw)
+    return _C.GemmDesc(**base)
+
+
+class Dumper:
+    def __init__(self, launches):
+        self.lib = _C.load()
+        self.plan_fn = {"gemm": self.lib.e4t_gemm_plan, "conv": self.lib.e4t_conv3x3_plan, "tn": self.lib.e4t_gemm_tn_plan}
+        self.launch_fn = {"gemm": self.lib.e4t_gemm_nt, "conv": self.lib.e4t_conv3x3, "tn": self.lib.e4t_gemm_tn}
+        self.log = None
+        if launches:
+            fd, self.log_path = tempfile.mkstemp(suffix=".launchlog")
+            os.close(fd)
+            assert self.lib.e4t_set_launch_log(self.log_path.encode()) == 0
+            self.log = open(self.log_path)
+
+    def close(self):
+        if self.log:
+            self.lib.e4t_set_launch_log(None)
+            self.log.close()
+            os.remove(self.log_path)
+
+    def plan(self, item, d=None):
+        d = d or make_desc(item)
+        pl = _C.GemmPlan()
+        rc = self.plan_fn[item.kind](C.byref(d), C.byref(pl))
+        if rc != 0:
+            return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
+        return "%d %d %d %d %d %d %d" % (pl.tile, pl.tile_m, pl.tile_n, pl.splitk, pl.workspace_bytes, pl.tail_rows, pl.stages)
+
+    def launch(self, item, d=None):
+        """(rc, error text, [log lines])"""
+        d = d or make_desc(item)
+        rc = self.launch_fn[item.kind](C.byref(d), None)
+        return rc, (self.lib.e4t_last_error().decode() if rc < 0 else ""), self.log.read().splitlines()
+
+    def line(self, item):
+        d = make_desc(item)
+        s = "%s %s -> %s" % (item.kind, describe(item.kw), self.plan(item, d))
+        if self.log:
+            rc, err, lines = self.launch(item, d)
+            s += " | rc %d %s | %s" % (rc, err, " ; ".join(lines))
+        return s
+
+
+def gpu_visible(lib):
+    n = C.c_int(0)
+    return lib.e4t_device_info(None, 0, C.byref(n)) == 0
+
+
+def plan_digests(dumper, only_groups=None):
+    """{group: (lines, sha256 of the plan half)} in corpus order, and the plan lines of the 'step' group"""
+    h, n, step = collections.OrderedDict(), collections.Counter(), []
+    for item in corpus():
+        if only_groups is not None and item.group not in only_groups:
+            continue
+        s = "%s %s -> %s" % (item.kind, describe(item.kw), dumper.plan(item))
+        h.setdefault(item.group, hashlib.sha256()).update((s + "\n").encode())
+        n[item.group] += 1
+        if item.group == "step":
+            step.append(s)
+    return collections.OrderedDict((g, (n[g], h[g].hexdigest())) for g in h), step
+
+
+def anchor(dumper):
+    """every launch row of the step table is reproduced by one of its field combinations; every reduce row by a second log line"""
+    want = step_rows()
+    got, matched = collections.defaultdict(list), []
+    for item in step_items():
+        rc, err, lines = dumper.launch(item)
+        for i, l in enumerate(lines):
+            got[tuple(l.split("|")[:2])].append((i, item))
+    miss = 0
+    for sym, shape in want:
+        hits = [it for i, it in got.get((sym, shape), []) if (i == 1) == sym.startswith("splitk_reduce")]
+        if hits:
+            matched.append((sym, shape, hits[0]))
+        else:
+            miss += 1
+            print("MISS %s|%s" % (sym, shape))
+    launches = sum(1 for s, _ in want if not s.startswith("splitk_reduce"))
+    print("step table: %d rows (%d launches, %d reduces), %d reproduced, %d missed" % (len(want), launches, len(want) - launches, len(matched), miss))
+    return matched, miss
+
+
+def write_record(dumper, path):
+    if not dumper.log:      # (before the file is opened: a refused --record leaves the committed record as it is)
+        sys.exit("--record needs the launch half (a machine without a GPU) to anchor the step shapes")
+    digests, _ = plan_digests(dumper)
+    matched, miss = anchor(dumper)
+    if miss:
+        sys.exit("--record: %d rows of the step table are not reproduced" % miss)
+    with open(path, "w") as f:
+        f.write("# What the DEFAULT build of the library plans for the corpus of tools/gemm_dispatch_dump.py (tests/test_gemm_dispatch.py).\n")
+        f.write("# Regenerate after an intentional planner change: python tools/gemm_dispatch_dump.py --record\n")
+        for g, (n, hx) in digests.items():
+            if g != "step":
+                f.write("group %s | %d | %s\n" % (g, n, hx))
+        f.write("# the training step's shapes (profiles/r06_roofline_per_shape.csv), with the field combination that reproduces the recorded launch\n")
+        for sym, shape, item in matched:
+            f.write("step %s|%s | %s %s -> %s\n" % (sym, shape, item.kind, describe(item.kw), dumper.plan(item)))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--plans", action="store_true")
+    ap.add_argument("--group", action="append")
+    ap.add_argument("--anchor", action="store_true")
+    ap.add_argument("--record", action="store_true")
+    args = ap.parse_args()
+    lib = _C.load()
+    launches = not args.plans
+    if launches and gpu_visible(lib):
+        print("# a GPU is visible: the launch half would hand fake pointers to a real device — plan half only", flush=True)
+        launches = False
+    d = Dumper(launches)
+    try:
+        if args.record:
+            if lib.e4t_build_flags() != 0:
+                sys.exit("--record is for the default build (e4t_build_flags() == 0)")
+            write_record(d, RECORD)
+            print("wrote", RECORD)
+            return 0
+        if args.anchor:
+            if not d.log:
+                sys.exit("--anchor needs the launch half")
+            return 1 if anchor(d)[1] else 0
+        print("# build_flags %d %s" % (lib.e4t_build_flags(), " ".join("%s=%s" % (k, os.environ[k]) for k in sorted(os.environ) if k.startswith("E4T_") and k != "E4T_LIB")))
+        for item in corpus():
+            if args.group and item.group not in args.group:
+                continue
+            print(d.line(item))
+        return 0
+    finally:
+        d.close()
+
+
+if __name__ == "__main__":
+    sys.exit(main())
