@@ -18,7 +18,7 @@ else
 fi
 pids=()
 for f in $SRCS; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || { [[ $f == gemm* ]] && [ gemm_common.h -nt obj/$f.o ]; } || [ ../../include/e4t_hip.h -nt obj/$f.o ]; then
+  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || { [[ $f == gemm* ]] && { [ gemm_common.h -nt obj/$f.o ] || [ gemm_dma_kernel.inc -nt obj/$f.o ] || [ gemm_pq_kernel.inc -nt obj/$f.o ]; }; } || [ ../../include/e4t_hip.h -nt obj/$f.o ]; then
     EXTRA=""
     [ $f = image ] && EXTRA="-ffp-contract=off"      # byte-exact INTER_AREA: float ops must not be fused (see image.hip)
     [ $f = attention ] && EXTRA="-fno-slp-vectorize" # packed fp32 VALU beside MFMAs is slower than the scalar pair (attention.hip: ATTN_PK)

@@ -159,5 +159,11 @@ __device__ __forceinline__ float dgelu_f(float x) {
   return fmaf(x * 0.39894228040143268f, e, cdf);
 }
 
+// GEGLU per element: h = a * gelu(g); its gradient for the incoming d: da = d * gelu(g), dg = d * a * gelu'(g).  The ONE statement of this arithmetic,
+// used by the standalone kernels (elementwise.hip) and by the fused GEMM epilogues (gemm_common.h, write_tile) alike, so the two cannot round differently
+__device__ __forceinline__ float geglu_f(float a, float g) { return a * gelu_f(g); }
+__device__ __forceinline__ float geglu_da_f(float d, float g) { return d * gelu_f(g); }
+__device__ __forceinline__ float geglu_dg_f(float d, float a, float g) { return d * a * dgelu_f(g); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }

@@ -17,7 +17,7 @@ __global__ __launch_bounds__(256) void geglu_fwd_kernel(const bf16_t* u, bf16_t*
     unpack8(*(const uint4*)(u + m * 2 * H + j), a);
     unpack8(*(const uint4*)(u + m * 2 * H + H + j), g);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) a[k] *= gelu_f(g[k]);
+    for (int k = 0; k < 8; ++k) a[k] = geglu_f(a[k], g[k]);
     *(uint4*)(h + m * H + j) = pack8(a);
   }
 }
@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void geglu_bwd_kernel(const bf16_t* u, const b
     unpack8(*(const uint4*)(u + m * 2 * H + H + j), g);
     unpack8(*(const uint4*)(dh + m * H + j), d);
 #pragma unroll
-    for (int k = 0; k < 8; ++k) { oa[k] = d[k] * gelu_f(g[k]); og[k] = d[k] * a[k] * dgelu_f(g[k]); }
+    for (int k = 0; k < 8; ++k) { oa[k] = geglu_da_f(d[k], g[k]); og[k] = geglu_dg_f(d[k], a[k], g[k]); }
     *(uint4*)(du + m * 2 * H + j) = pack8(oa);
     *(uint4*)(du + m * 2 * H + H + j) = pack8(og);
   }

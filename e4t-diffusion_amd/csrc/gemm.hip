@@ -224,301 +224,16 @@ template <int BM, int BN, int WGM, int WGN, int MODE, int NSTAGE, bool GENERAL =
 // (second argument = waves per SIMD the register allocation must leave room for: the 2-stage 128 x 160 tile runs TWO 4-wave workgroups per CU — at 260
 // registers instead of 256 it ran one, 40 % slower: M16384 N640 K640 22.8 -> 31.9 us, round 6)
 __global__ __launch_bounds__(WGM * WGN * 64, (BM == 256 && KT == 32) ? 4 : (BN == 160 ? 2 : 1)) void gemm_dma_kernel(GemmArgs p) {
-#ifdef DMA_TRACE
-  const int dt_lin = blockIdx.y * gridDim.x + blockIdx.x;
-  const int dt_wg = dt_lin >> 3;
-  const bool dt_on = (threadIdx.x == 0) && (dt_lin & 7) == 0 && dt_wg < 128 && blockIdx.z == 0;
-  DT(0);
-#endif
-  constexpr int WM = BM / WGM, WN = BN / WGN;
-  constexpr int FM = WM / 32, FN = WN / 32;
-  constexpr int NW = WGM * WGN;                       // waves per workgroup (4 or 8)
-  constexpr int SL = KT / 8;                          // 16-byte slots per LDS row
-  constexpr int RPP = 512 / KT;                       // rows per 1-KiB DMA piece (8 or 16)
-  constexpr int NA = BM / RPP / NW, NB = (BN / RPP + NW - 1) / NW;   // pieces per wave per K-tile (B: last wave may own fewer)
-  constexpr int LOOK = NSTAGE - 1;                    // K-tiles in flight
-  constexpr int TILE = (BM + BN) * KT;          // elements per LDS buffer
-  static_assert(NA >= 1 && NB >= 1 && (NW == 4 || NW == 8) && (NSTAGE >= 2 && NSTAGE <= 4), "bad tile configuration");
-  constexpr bool RAGGED_B = (BN / RPP) % NW != 0;     // the last wave(s) own fewer B pieces: their counted waits use their own count
-  static_assert(!RAGGED_B || NB <= 3, "counted vmcnt: per-wave piece counts are enumerated up to 3 B pieces");
-  static_assert((KT == 64 || KT == 32) && BM % (RPP * NW) == 0, "bad K-tile width");
-
-  __shared__ __attribute__((aligned(16))) bf16_t smem[NSTAGE * TILE];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // (an SGPR: the DMA destinations are wave-uniform)
-  const int wm = wave / WGN, wn = wave % WGN;
-  // B pieces this wave issues per K-tile (wave-uniform): NB, or fewer in the last wave(s) of a ragged split
-  const int nbw = RAGGED_B ? min(NB, max(0, BN / RPP - wave * NB)) : NB;
-  int tile_x, tile_y;
-  xcd_tile(tile_x, tile_y, p.group_m);
-  const int m0 = tile_y * BM, n0 = tile_x * BN;
-
-  const int nkt = (p.K + KT - 1) / KT;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split * (BK / KT);          // the launcher counts 64-wide tiles
-  int kt_end = kt_begin + p.ktiles_per_split * (BK / KT);
-  if (kt_end > nkt) kt_end = nkt;
-
-  // Operands are addressed through buffer resources (buffer_load ... lds): a 32-bit per-lane byte offset that changes only
-  // when the tile starts a new region — the first tile, a new 3x3 tap (conv), the switch to the second concat source
-  // (dense), the ragged last tile — plus a wave-uniform SGPR offset that walks K (+128 B per K-tile).  Issuing a tile costs
-  // no VALU at all (a per-tile 64-bit address recomputation cost ~1.2k issue cycles per wave, carried 64-bit pointers still
-  // 3 VALU each), and out-of-range rows / conv padding / K tails carry an out-of-range offset: the hardware returns zeros.
-  const bool cm = MODE != 0 && p.chan_major;          // channel-chunk-major K order (gemm_common.h, cm_step)
-  const __amdgpu_buffer_rsrc_t rs_a = cm ? cm_rsrc(p) : __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, (int)(p.A2 ? p.a2_bytes : p.a_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;          // >= every extent the launcher accepts
-  const int lrow = lane / SL, lslot = lane % SL;   // position of this lane inside a 1-KiB piece
-  auto swz = [](int r) { return KT == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); };      // source-side XOR swizzle of the 16-byte slots
-
-  // rows this lane feeds: piece q = wave*NA + i covers tile rows q*8 .. q*8+7
-  long long a_base[NA];
-  int a_oy[NA], a_ox[NA], a_kc[NA];
-  bool a_ok[NA];
-#pragma unroll
-  for (int i = 0; i < NA; ++i) {
-    const int r = (wave * NA + i) * RPP + lrow;
-    const int gr = m0 + r;
-    a_ok[i] = gr < p.M;
-    a_kc[i] = (lslot ^ swz(r)) * 8;       // logical k offset (elements) this lane fetches for that row
-    if (MODE == 0) {
-      a_base[i] = (long long)gr; a_oy[i] = a_ox[i] = 0;
-    } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[i] = rem / p.Wout;
-      a_ox[i] = rem - a_oy[i] * p.Wout;
-      a_base[i] = (long long)b * p.Hin * p.Win;
-    }
-  }
-  unsigned b_row[NB];
-  int b_kc[NB];
-  bool b_ok[NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i) {
-    const int r = (wave * NB + i) * RPP + lrow;
-    const int gn = n0 + r;
-    b_ok[i] = gn < p.N && r < BN;
-    b_kc[i] = (lslot ^ swz(r)) * 8;
-    b_row[i] = (unsigned)(((size_t)(b_ok[i] ? gn : 0) * p.ldb + b_kc[i]) * 2);
-  }
-
-  unsigned a_vo[NA], b_vo[NB];
-  int a_so = 0, b_so = 0;          // wave-uniform byte offsets along K
-  bool a_second = false;           // reading the second concat source
-  auto place_a = [&](int k0) {
-    if (MODE == 0) {
-      int ld = p.lda, koff = k0;
-      a_second = k0 >= p.K1;
-      if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
-      a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        const bool ok = a_ok[i] && (k0 + a_kc[i] < p.K);
-        a_vo[i] = ok ? (unsigned)((a_base[i] * ld + a_kc[i]) * 2) : OOB;
-      }
-    } else {
-      const int tap = k0 / p.Cin;
-      const int ci0 = k0 - tap * p.Cin;
-      const int ky = tap / 3, kx = tap - ky * 3;
-      a_so = __builtin_amdgcn_readfirstlane(ci0 * 2);
-#pragma unroll
-      for (int i = 0; i < NA; ++i) {
-        int iy, ix;
-        bool ok = a_ok[i];
-        if (p.mode == E4T_CONV_S1) {
-          iy = a_oy[i] + ky - 1; ix = a_ox[i] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_S2) {
-          iy = 2 * a_oy[i] + ky - 1; ix = 2 * a_ox[i] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_UP2) {
-          iy = a_oy[i] + ky - 1; ix = a_ox[i] + kx - 1;
-          ok = ok && iy >= 0 && iy < 2 * p.Hin && ix >= 0 && ix < 2 * p.Win;
-          iy >>= 1; ix >>= 1;
-        } else if (p.mode == E4T_CONV_S2A) {
-          iy = 2 * a_oy[i] + ky; ix = 2 * a_ox[i] + kx;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        } else {
-          const int sy = a_oy[i] + ky - 1, sx = a_ox[i] + kx - 1;
-          ok = ok && sy >= 0 && sx >= 0 && !(sy & 1) && !(sx & 1);
-          iy = sy >> 1; ix = sx >> 1;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        }
-        a_vo[i] = ok ? (unsigned)(((a_base[i] + (long long)iy * p.Win + ix) * p.Cin + a_kc[i]) * 2) : OOB;
-      }
-    }
-  };
-  auto place_b = [&](int k0) {
-    b_so = k0 * 2;
-#pragma unroll
-    for (int i = 0; i < NB; ++i) {
-      const bool ok = b_ok[i] && (k0 + b_kc[i] < p.K);
-      b_vo[i] = ok ? b_row[i] : OOB;
-    }
-  };
-  if (cm) {                        // a_vo = the output position's own pixel (all taps), a_oy = inverted 9-bit tap validity mask
-#pragma unroll
-    for (int i = 0; i < NA; ++i) {
-      a_vo[i] = cm_center(p, a_base[i], a_oy[i], a_ox[i], a_kc[i]);
-      a_oy[i] = cm_inv_mask(p, a_ok[i], a_oy[i], a_ox[i]);
-    }
-  }
-  CmWalk wk;                       // cm: (tap, chunk) of the next K-tile to issue
-  wk.init(kt_begin, KT);
-  const int cm_table = cm ? cm_tap_table(p, lane) : 0;
-  auto issue_tile = [&](int kt, bf16_t* buf) __attribute__((always_inline)) {
-    const int k0 = kt * KT;
-    bf16_t* As = buf;
-    bf16_t* Bs = buf + BM * KT;
-    if (cm) {                      // whole K-tiles only (Cin % KT == 0): no ragged tile; tiles are issued in increasing kt
-      if (kt == kt_begin) place_b(k0);
-      const int aso = cm_a_so(cm_table, wk), bso = cm_b_so(p, wk);
-#pragma unroll
-      for (int i = 0; i < NA; ++i)
-        buf_dma16(rs_a, cm_row_off(a_vo[i], a_oy[i], wk), aso, As + (wave * NA + i) * 512);
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-        if ((BN / RPP) % NW == 0 || wave * NB + i < BN / RPP)
-          buf_dma16(rs_b, b_vo[i], bso, Bs + (wave * NB + i) * 512);
-      wk.next(KT);
-      return;
-    }
-    const bool ragged = k0 + KT > p.K;                                      // wave-uniform conditions
-    const bool fresh_a = kt == kt_begin || ragged || (MODE == 0 ? k0 == p.K1 : (k0 % p.Cin) == 0);
-    if (fresh_a) place_a(k0);
-    else a_so += KT * 2;
-    if (kt == kt_begin || ragged) place_b(k0);
-    else b_so += KT * 2;
-#pragma unroll
-    for (int i = 0; i < NA; ++i)
-      buf_dma16(a_second ? rs_a2 : rs_a, a_vo[i], a_so, As + (wave * NA + i) * 512);
-#pragma unroll
-    for (int i = 0; i < NB; ++i)
-      if ((BN / RPP) % NW == 0 || wave * NB + i < BN / RPP)
-        buf_dma16(rs_b, b_vo[i], b_so, Bs + (wave * NB + i) * 512);
-  };
-
-  f32x16 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int frow = lane & 31, fhi = lane >> 5;
-  // fragment offsets inside a stage (elements), one per (fragment, k-step): computed once; the stage base is a
-  // compile-time constant of the unrolled loop below, so every ds_read_b128 is "vgpr + immediate"
-  int a_off[FM][KT / 16], b_off[FN][KT / 16];
-#pragma unroll
-  for (int ks = 0; ks < KT / 16; ++ks) {
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      const int r = wm * WM + i * 32 + frow;
-      a_off[i][ks] = r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int r = wn * WN + j * 32 + frow;
-      b_off[j][ks] = BM * KT + r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
-    }
-  }
-  // prologue: LOOK tiles in flight
-#pragma unroll
-  for (int s = 0; s < LOOK; ++s)
-    if (kt_begin + s < kt_end) issue_tile(kt_begin + s, smem + s * TILE);
-  DT(1);
-
-  auto body = [&](auto CURc, int kt) {
-    constexpr int CUR = decltype(CURc)::value;
-    constexpr int NXT = (CUR + LOOK) % NSTAGE;
-    // this wave's pieces of tile kt have landed once at most the pieces of the newer tiles in flight (LOOK-1 of them, fewer
-    // at the end of the K range) are outstanding: a counted wait, the loads of the deeper stages keep flying
-    auto wait_tiles = [&](auto Tc) {          // at most T newer K-tiles of this wave's pieces outstanding
-      constexpr int T = decltype(Tc)::value;
-      if (!RAGGED_B || nbw == NB) wait_vmcnt<T * (NA + NB)>();
-      else if (nbw == NB - 1) wait_vmcnt<T * (NA + (NB > 1 ? NB - 1 : 0))>();
-      else if (nbw == NB - 2) wait_vmcnt<T * (NA + (NB > 2 ? NB - 2 : 0))>();
-      else wait_vmcnt<T * NA>();
-    };
-    if (LOOK >= 3 && kt + 2 < kt_end) wait_tiles(std::integral_constant<int, 2>{});
-    else if (LOOK >= 2 && kt + 1 < kt_end) wait_tiles(std::integral_constant<int, 1>{});
-    else wait_vmcnt<0>();
-    loop_barrier();                                    // ... everyone's have; and everyone finished reading slot NXT
-#ifdef DMA_TRACE
-    if (kt - kt_begin < 8) DT(2 + (kt - kt_begin));
-#endif
-    const bf16_t* st = smem + CUR * TILE;
-    bf16x8 af[2][FM], bfr[2][FN];
-#pragma unroll
-    for (int i = 0; i < FM; ++i) af[0][i] = *(const bf16x8*)(st + a_off[i][0]);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) bfr[0][j] = *(const bf16x8*)(st + b_off[j][0]);
-    if (kt + LOOK < kt_end) issue_tile(kt + LOOK, smem + NXT * TILE);   // after the first fragment reads are in flight
-#pragma unroll
-    for (int ks = 0; ks < KT / 16; ++ks) {
-      const int c = ks & 1, n = c ^ 1;
-      if (ks + 1 < KT / 16) {
-#pragma unroll
-        for (int i = 0; i < FM; ++i) af[n][i] = *(const bf16x8*)(st + a_off[i][ks + 1]);
-#pragma unroll
-        for (int j = 0; j < FN; ++j) bfr[n][j] = *(const bf16x8*)(st + b_off[j][ks + 1]);
-      }
-#pragma unroll
-      for (int i = 0; i < FM; ++i)
-#pragma unroll
-        for (int j = 0; j < FN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[c][i], bfr[c][j], acc[i][j], 0, 0, 0);
-    }
-  };
-  {
-    int kt = kt_begin;
-    for (; kt + NSTAGE <= kt_end; kt += NSTAGE) {
-      body(std::integral_constant<int, 0>{}, kt);
-      body(std::integral_constant<int, 1>{}, kt + 1);
-      if (NSTAGE >= 3) body(std::integral_constant<int, 2 % NSTAGE>{}, kt + 2);
-      if (NSTAGE >= 4) body(std::integral_constant<int, 3 % NSTAGE>{}, kt + 3);
-    }
-    if (kt < kt_end) { body(std::integral_constant<int, 0>{}, kt); ++kt; }
-    if (kt < kt_end) { body(std::integral_constant<int, 1>{}, kt); ++kt; }
-    if (NSTAGE >= 4 && kt < kt_end) { body(std::integral_constant<int, 2 % NSTAGE>{}, kt); ++kt; }
-  }
-  DT(10);
-  __syncthreads();   // all fragment reads done before the epilogue reuses the LDS
-  DT(11);
-#ifdef DMA_TRACE
-  write_tile<WM, WN, FM, FN, GENERAL>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN, dt_on ? g_dma_trace + dt_wg * 16 : nullptr);
-#else
-  if constexpr (NW * WM * (WN + 8) > NSTAGE * TILE || WM >= 128) {
-    // tall wave tiles (the 4-wave 256-row variants): two row halves, so that the staging fits the operand buffers and the
-    // (fully unrolled) epilogue stays at the size of the other kernels'
-    static_assert(FM % 2 == 0 && NW * (WM / 2) * (WN + 8) <= NSTAGE * TILE, "epilogue staging must fit");
-    write_tile<WM / 2, WN, FM / 2, FN, GENERAL>(p, *(f32x16(*)[FM / 2][FN])(acc + 0), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
-    __syncthreads();
-    write_tile<WM / 2, WN, FM / 2, FN, GENERAL>(p, *(f32x16(*)[FM / 2][FN])(acc + FM / 2), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM + WM / 2, n0 + wn * WN);
-  } else {
-    write_tile<WM, WN, FM, FN, GENERAL>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
-  }
-  // tail rows: only in the 128 x 160 instantiations (and the ping-pong kernels), which have the registers for its 16 loads in flight — inlined
-  // into the 64 / 128 / 256 x 128 tiles it cost them an occupancy step (92 -> 162 VGPRs on the 128 x 128 tile); the planner knows (plan_gemm_tail)
-  if constexpr (MODE == 0 && BN == 160) {
-    static_assert(NSTAGE * TILE * 2 >= NW * 16 * 64 * 4, "tail reduction must fit the operand buffers");
-    if (p.tail_rows) gemm_tail<NW, GENERAL>(p, (float*)smem, wave, lane);      // (its first barrier orders it behind the staging reads above)
-  }
-#endif
-  DT(12);
+  constexpr int EPI = EPI_PLAIN;
+#include "gemm_dma_kernel.inc"
+}
+// The same kernel with the GEGLU fused into the store phase of its epilogue (EPI = EPI_GEGLU | EPI_GEGLU_BWD; gemm_common.h, write_tile): dense GEMM,
+// plain staging.  The forward kind differs outside the epilogue in ONE place, the global B row of each DMA piece (geglu_col).
+template <int BM, int BN, int WGM, int WGN, int NSTAGE, int KT, int EPI>
+__global__ __launch_bounds__(WGM * WGN * 64, (BM == 256 && KT == 32) ? 4 : (BN == 160 ? 2 : 1)) void gemm_dma_geglu_kernel(GemmArgs p) {
+  constexpr int MODE = 0;
+  constexpr bool GENERAL = false;
+#include "gemm_dma_kernel.inc"
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1282,277 +997,15 @@ static bool conv_pps_ok(const GemmArgs& p, int /*splitk*/, int batch) {
 // ------------------------------------------------------------------------------------------------
 template <int MODE, int BN, bool GENERAL>
 __global__ __launch_bounds__(512) void gemm_pq_kernel(GemmArgs p) {
-  constexpr int BM = 256, HK = 32;
-  constexpr int WR = BN == 320 ? 4 : 2, WC = 8 / WR;
-  constexpr int WM = BM / WR, WN = BN / WC;                  // 128 x 64 | 64 x 160
-  constexpr int FM = WM / 32, FN = WN / 32;                  // 4 x 2 | 2 x 5
-  constexpr int QA = BM * HK, QB = BN * HK;                  // elements per A / B quarter
-  constexpr int HALF = QA + QB, BUF = 2 * HALF;              // [A | B] of one k half; one buffer = lo half + hi half
-  constexpr int NBP = BN / 16;                               // B pieces per quarter: 16 | 20
-  constexpr int NBJ = (NBP + 7) / 8;                         // per wave: 2 | 3 (the last one only in waves < NBP - 8 * (NBJ - 1))
-  constexpr int NBLAST = NBP - 8 * (NBJ - 1);                // waves that carry NBJ pieces: 8 | 4
-  constexpr int ESTG = 8 * 32 * (WN + 8);                    // epilogue staging: 8 waves x 32 rows
-  static_assert(BN == 256 || BN == 320, "tile width");
-  static_assert(2 * BUF * 2 <= 160 * 1024 && ESTG <= 2 * BUF, "LDS budget");
-  __shared__ __attribute__((aligned(16))) bf16_t smem[2 * BUF];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2;
-  const int wr = wave / WC, wc = wave % WC;
-  int tile_x, tile_y;
-  xcd_tile(tile_x, tile_y, p.group_m);
-  int m0 = tile_y * BM;
-  const int n0 = tile_x * BN;
-  const int mrows = p.M - m0;                       // valid (logical) rows of this tile
-  if (p.panel_rows) m0 = (m0 / p.panel_rows) * p.panel_stride + p.panel_off + m0 % p.panel_rows;      // physical first row (panel_rows % 256 == 0)
-
-  const int nkt = p.K / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split;
-  int kt_end = kt_begin + p.ktiles_per_split;
-  if (kt_end > nkt) kt_end = nkt;
-
-  const bool cm = MODE != 0 && p.chan_major;          // channel-chunk-major K order (gemm_common.h, cm_step)
-  const __amdgpu_buffer_rsrc_t rs_a = cm ? cm_rsrc(p) : __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, (int)(p.A2 ? p.a2_bytes : p.a_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;
-  // DMA: one wave-instruction = 16 rows x 64 B; wave w feeds A rows 32w + 16j + (lane >> 2), j = 0, 1, and B pieces w + 8j
-  const int drow = lane >> 2, dslot = lane & 3;
-  long long a_base[2];
-  int a_oy[2], a_ox[2], a_kc[2];
-  bool a_ok[2];
-  unsigned b_vo[NBJ];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int r = wave * 32 + j * 16 + drow;
-    a_kc[j] = (dslot ^ ((r >> 2) & 3)) * 8;
-    const int gr = m0 + r;
-    a_ok[j] = r < mrows;
-    if (MODE == 0) {
-      a_base[j] = (long long)gr; a_oy[j] = a_ox[j] = 0;
-    } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[j] = rem / p.Wout;
-      a_ox[j] = rem - a_oy[j] * p.Wout;
-      a_base[j] = (long long)b * p.Hin * p.Win;
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < NBJ; ++j) {
-    const int r = (wave + 8 * j) * 16 + drow;
-    const int kc = (dslot ^ ((r >> 2) & 3)) * 8;
-    const int gn = n0 + r;
-    b_vo[j] = (r < BN && gn < p.N) ? (unsigned)(((size_t)gn * p.ldb + kc) * 2) : OOB;
-  }
-  unsigned a_vo[2];
-  if (cm) {                        // a_vo = the output position's own pixel (all taps), a_oy = inverted 9-bit tap validity mask
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      a_vo[j] = cm_center(p, a_base[j], a_oy[j], a_ox[j], a_kc[j]);
-      a_oy[j] = cm_inv_mask(p, a_ok[j], a_oy[j], a_ox[j]);
-    }
-  }
-  unsigned a_eff[2] = {0u, 0u};    // cm: the offsets of the K-tile whose quarters are being issued
-  CmWalk wa, wb;                   // cm: one walker per operand stream (A and B are issued at different times)
-  wa.init(kt_begin, BK); wb = wa;
-  const int cm_table = cm ? cm_tap_table(p, lane) : 0;
-  int a_so = 0, b_so = 0;
-  bool a_second = false;
-  auto place_a = [&](int k0) {
-    if (MODE == 0) {
-      int ld = p.lda, koff = k0;
-      a_second = k0 >= p.K1;
-      if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
-      a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) a_vo[j] = a_ok[j] ? (unsigned)((a_base[j] * ld + a_kc[j]) * 2) : OOB;
-    } else {
-      const int tap = k0 / p.Cin;
-      const int ci0 = k0 - tap * p.Cin;
-      const int ky = tap / 3, kx = tap - ky * 3;
-      a_so = __builtin_amdgcn_readfirstlane(ci0 * 2);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        int iy, ix;
-        bool ok = a_ok[j];
-        if (p.mode == E4T_CONV_S1) {
-          iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_S2) {
-          iy = 2 * a_oy[j] + ky - 1; ix = 2 * a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_UP2) {
-          iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < 2 * p.Hin && ix >= 0 && ix < 2 * p.Win;
-          iy >>= 1; ix >>= 1;
-        } else if (p.mode == E4T_CONV_S2A) {
-          iy = 2 * a_oy[j] + ky; ix = 2 * a_ox[j] + kx;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        } else {
-          const int sy = a_oy[j] + ky - 1, sx = a_ox[j] + kx - 1;
-          ok = ok && sy >= 0 && sx >= 0 && !(sy & 1) && !(sx & 1);
-          iy = sy >> 1; ix = sx >> 1;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        }
-        a_vo[j] = ok ? (unsigned)(((a_base[j] + (long long)iy * p.Win + ix) * p.Cin + a_kc[j]) * 2) : OOB;
-      }
-    }
-  };
-  // the A and B streams are each issued in increasing k: lo(t), hi(t), lo(t+1), ...
-  auto issue_a = [&](int kt, bool hi, bf16_t* dst) __attribute__((always_inline)) {
-    if (cm) {                        // lo(t), hi(t), lo(t+1), ...: the walker advances after each hi
-      if (!hi) {
-        a_so = cm_a_so(cm_table, wa);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) a_eff[j] = cm_row_off(a_vo[j], a_oy[j], wa);
-      } else {
-        a_so = __builtin_amdgcn_readfirstlane(a_so + HK * 2);
-      }
-#pragma unroll
-      for (int j = 0; j < 2; ++j) buf_dma16(rs_a, a_eff[j], a_so, dst + (wave * 32 + j * 16) * HK);
-      if (hi) wa.next(BK);
-      return;
-    }
-    const int k0 = kt * BK;
-    const bool fresh = !hi && (kt == kt_begin || (MODE == 0 ? k0 == p.K1 : (k0 % p.Cin) == 0));
-    if (fresh) place_a(k0);
-    else a_so = __builtin_amdgcn_readfirstlane(a_so + HK * 2);
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-      buf_dma16(a_second ? rs_a2 : rs_a, a_vo[j], a_so, dst + (wave * 32 + j * 16) * HK);
-  };
-  auto issue_b = [&](int kt, bool hi, bf16_t* dst) __attribute__((always_inline)) {
-    if (cm && !hi) b_so = cm_b_so(p, wb);
-    else if (!cm && !hi && kt == kt_begin) b_so = kt * BK * 2;
-    else b_so = __builtin_amdgcn_readfirstlane(b_so + HK * 2);
-#pragma unroll
-    for (int j = 0; j < NBJ; ++j)
-      if (j < NBJ - 1 || wave < NBLAST) buf_dma16(rs_b, b_vo[j], b_so, dst + ((wave + 8 * j) * 16) * HK);
-    if (cm && hi) wb.next(BK);
-  };
-  // at most the 3 newest quarters of this wave outstanding: 2 A + 1 B after an even phase, 1 A + 2 B after an odd one
-  constexpr int NBW_HI = NBJ, NBW_LO = NBJ - 1;
-  auto wait3 = [&](auto ODDc) {
-    constexpr bool ODD = decltype(ODDc)::value;
-    if (NBLAST == 8 || wave < NBLAST) wait_vmcnt<(ODD ? 2 + 2 * NBW_HI : 4 + NBW_HI)>();
-    else wait_vmcnt<(ODD ? 2 + 2 * NBW_LO : 4 + NBW_LO)>();
-  };
-
-  f32x16 acc[FM][FN];
-#pragma unroll
-  for (int i = 0; i < FM; ++i)
-#pragma unroll
-    for (int j = 0; j < FN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int frow = lane & 31, fhi = lane >> 5;
-  int a_off[FM][2], b_off[FN][2];     // fragment offsets inside a quarter (elements), [block][k step of the half]
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-    for (int i = 0; i < FM; ++i) {
-      const int r = wr * WM + i * 32 + frow;
-      a_off[i][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < FN; ++j) {
-      const int r = wc * WN + j * 32 + frow;
-      b_off[j][ks] = QA + r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
-    }
-  }
-  // buffer b = smem + b * BUF: [lo: A | B][hi: A | B].  Prologue: lo(t0), hi(t0), B-lo(t0+1), A-lo(t0+1) — the stream position the
-  // first phase expects (its own issue is A-lo(t+2)... of the NEXT tile: see the phase schedule).
-  issue_b(kt_begin, false, smem + QA);
-  issue_a(kt_begin, false, smem);
-  issue_b(kt_begin, true, smem + HALF + QA);
-  issue_a(kt_begin, true, smem + HALF);
-  if (kt_begin + 1 < kt_end) {
-    issue_b(kt_begin + 1, false, smem + BUF + QA);
-    issue_a(kt_begin + 1, false, smem + BUF);
-  }
-  wait_vmcnt<0>();                 // (one-off: the first K-tile and the next one's lo half)
-  __builtin_amdgcn_s_barrier();
-
-  auto phase = [&](auto Bc, auto Pc, int kt) {
-    constexpr int b = decltype(Bc)::value, ph = decltype(Pc)::value;
-    constexpr int kh = ph >> 1, ks = ph & 1;
-    bf16_t* const buf = smem + b * BUF;
-    bf16_t* const other = smem + (b ^ 1) * BUF;
-    const bf16_t* const q = buf + kh * HALF;
-    bf16x8 af[FM], bfr[FN];
-    // ---- L segment ----
-#pragma unroll
-    for (int i = 0; i < FM; ++i) af[i] = *(const bf16x8*)(q + a_off[i][ks]);
-#pragma unroll
-    for (int j = 0; j < FN; ++j) bfr[j] = *(const bf16x8*)(q + b_off[j][ks]);
-    bool staged;
-    if (ph == 0)      { staged = kt + 1 < kt_end && kt > kt_begin; if (staged) issue_a(kt + 1, false, other); }       // A-lo(t+1) (the prologue issued the first one)
-    else if (ph == 1) { staged = kt + 1 < kt_end; if (staged) issue_b(kt + 1, true, other + HALF + QA); }              // B-hi(t+1)
-    else if (ph == 2) { staged = kt + 1 < kt_end; if (staged) issue_a(kt + 1, true, other + HALF); }                   // A-hi(t+1)
-    else              { staged = kt + 2 < kt_end; if (staged) issue_b(kt + 2, false, buf + QA); }                      // B-lo(t+2)
-    if (staged) wait3(std::integral_constant<bool, (ph & 1) != 0>{}); else wait_vmcnt<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- M segment ----
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int i = 0; i < FM; ++i)
-#pragma unroll
-      for (int j = 0; j < FN; ++j)
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-
-  if (grp == 1) __builtin_amdgcn_s_barrier();        // group 1 runs one barrier interval behind group 0
-  {
-    int kt = kt_begin;
-    for (; kt + 2 <= kt_end; kt += 2) {
-      phase(I0{}, I0{}, kt); phase(I0{}, I1{}, kt); phase(I0{}, I2{}, kt); phase(I0{}, I3{}, kt);
-      phase(I1{}, I0{}, kt + 1); phase(I1{}, I1{}, kt + 1); phase(I1{}, I2{}, kt + 1); phase(I1{}, I3{}, kt + 1);
-    }
-    if (kt < kt_end) { phase(I0{}, I0{}, kt); phase(I0{}, I1{}, kt); phase(I0{}, I2{}, kt); phase(I0{}, I3{}, kt); }
-  }
-  if (grp == 0) __builtin_amdgcn_s_barrier();
-  __syncthreads();   // every fragment read and every DMA is done before the epilogue reuses the LDS
-  if (p.panel_rows) p.M = m0 + min(mrows, BM);      // the epilogue bounds PHYSICAL rows (never with split-K: p.M is the slab stride there)
-  // 32-row slices of the wave tile: the staging of 8 waves x 32 x (WN + 8) fits the operand buffers, the unrolled epilogue stays small
-  // (compile-time row index: a runtime-indexed accumulator array is placed in scratch memory — 704 bytes per lane written and read back
-  // through HBM cost ~55 us per tile in the first version of this kernel)
-  auto slice = [&](auto Ic) {
-    constexpr int i = decltype(Ic)::value;
-    write_tile<32, WN, 1, FN, GENERAL>(p, *(f32x16(*)[1][FN])(&acc[i][0]), wave_stage<32, WN>(smem, wave), lane, m0 + wr * WM + i * 32, n0 + wc * WN);
-  };
-  slice(I0{});
-  __syncthreads();
-  slice(I1{});
-  if constexpr (FM == 4) {
-    __syncthreads();
-    slice(I2{});
-    __syncthreads();
-    slice(I3{});
-  }
-  if constexpr (MODE == 0) {
-    if (p.tail_rows) gemm_tail<8, GENERAL>(p, (float*)smem, wave, lane);
-  }
+  constexpr int EPI = EPI_PLAIN;
+#include "gemm_pq_kernel.inc"
+}
+// (the fused GEGLU epilogues, as gemm_dma_geglu_kernel)
+template <int BN, int EPI>
+__global__ __launch_bounds__(512) void gemm_pq_geglu_kernel(GemmArgs p) {
+  constexpr int MODE = 0;
+  constexpr bool GENERAL = false;
+#include "gemm_pq_kernel.inc"
 }
 
 #ifdef E4T_EXPERIMENTAL
@@ -2048,6 +1501,7 @@ enum : unsigned {
   CAP_PANELS = 1u << 8,      // carries row panels
   CAP_ONE_PER_CU = 1u << 9,  // one 512-thread workgroup per CU: the "ping-pong" split-K rule
   CAP_PERSISTENT = 1u << 10, // launched through e4t_launch_gemm_ps (gemm_ps.hip): at most one workgroup per CU walks all tiles
+  CAP_GEGLU = 1u << 11,      // carries the fused GEGLU epilogues (Variant::geglu; E4T_EPI_GEGLU / E4T_EPI_GEGLU_BWD)
   CAP_DMA = CAP_BUF | CAP_COLSTATS | CAP_SPLITK,
 };
 // A conv launch of the row goes to a strip-staged kernel instead when ok(p, splitk, batch) holds at launch time.
@@ -2057,6 +1511,7 @@ struct Variant {
   unsigned caps;
   KernelEntry gemm[2], conv[2], conv_cm[2];      // [GENERAL]; conv_cm: channel-major K order as a template argument (else a run-time flag)
   StripAlt alt[2];
+  KernelEntry geglu[2];      // [EPI_GEGLU - 1], [EPI_GEGLU_BWD - 1]: dense GEMM with the GEGLU in the store phase (CAP_GEGLU)
 };
 
 // ---- hooks of the measured-and-rejected variants (csrc/build.sh: E4T_EXPERIMENTAL=1); the product build answers "no" -----------------
@@ -2094,25 +1549,33 @@ int launch_persistent(GemmArgs&, const Variant&, bool, bool, hipStream_t) { E4T_
 #define DMA_FN_GENERAL(nt, bm, bn, wgm, wgn, st)                                                                                  \
   {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 0, st, false, 64), KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 0, st, true, 64)}, \
   {KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 1, st, false, 64), KERNEL(nt, gemm_dma_kernel, bm, bn, wgm, wgn, 1, st, true, 64)}
+// (the epilogue kind is spelled as its number, 1 = EPI_GEGLU, 2 = EPI_GEGLU_BWD: the text is the kernel symbol as a trace shows it)
+#define DMA_GEGLU(nt, bm, bn, wgm, wgn, st, kt) {KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 1), KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 2)}
+#define DMA_GEGLU_F(nt, bm, bn, wgm, wgn, st, kt) {KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 1), NO_KERNEL}
+#define DMA_GEGLU_B(nt, bm, bn, wgm, wgn, st, kt) {NO_KERNEL, KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 2)}
 #define PS_TEXT(mode, bn, general) {nullptr, "gemm_ps_kernel<" #mode ", " #bn ", " #general ">", 512}
 #define PS_FN(bn) {PS_TEXT(0, bn, false), PS_TEXT(0, bn, true)}, {PS_TEXT(1, bn, false), PS_TEXT(1, bn, true)}
 #define REG_FN(bm, bn, mode) {{&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}, {&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}}
 static const Variant kVariants[] = {
     // 64 / 128 / 160 tiles: 2 LDS stages and 2 workgroups per CU by default; 3 or 4 stages (one workgroup per CU, 2-3 K-tiles in flight)
     // when the grid cannot give a CU two workgroups anyway (small_grid_plan).  GENERAL: the 2-stage tiles and the 3-stage 64 tile.
+    // CAP_GEGLU: the fused GEGLU epilogues are built for exactly the (tile, stages, kind) the planner gives a feed-forward GEMM of the training step
+    // (B = 16: 5256, 2320, 160 s2 forward, 160 s3 backward) or of SD-2.x @768 (B = 1, 4: 5256, 128 s2, 128 s4 backward, 64 s3 forward, 64 s4 backward);
+    // anything else is refused (geglu_refusal) and the caller runs the unfused pair
     {64, 64, 2, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(256, 64, 64, 2, 2, 2)},
-    {64, 64, 3, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(256, 64, 64, 2, 2, 3)},
-    {64, 64, 4, 64, 64, CAP_DMA | CAP_STAGED, DMA_FN(256, 64, 64, 2, 2, 4, 64)},
+    {64, 64, 3, 64, 64, CAP_DMA | CAP_STAGED | CAP_GEGLU, DMA_FN_GENERAL(256, 64, 64, 2, 2, 3), {}, {}, DMA_GEGLU_F(256, 64, 64, 2, 2, 3, 64)},
+    {64, 64, 4, 64, 64, CAP_DMA | CAP_STAGED | CAP_GEGLU, DMA_FN(256, 64, 64, 2, 2, 4, 64), {}, {}, DMA_GEGLU_B(256, 64, 64, 2, 2, 4, 64)},
     // 128x128: 8 waves (wave tile 32x64): ~4 waves/SIMD at 2 workgroups/CU hide the DMA/LDS latency that the 4-wave
     // version of the same tile exposed (measured +5..18 % on every E4T shape, 8192^3: 956 -> 980 TF)
-    {128, 64, 2, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN_GENERAL(512, 128, 128, 4, 2, 2)},
+    {128, 64, 2, 128, 128, CAP_DMA | CAP_STAGED | CAP_GEGLU, DMA_FN_GENERAL(512, 128, 128, 4, 2, 2), {}, {}, DMA_GEGLU(512, 128, 128, 4, 2, 2, 64)},
     {128, 64, 3, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN(512, 128, 128, 4, 2, 3, 64)},
-    {128, 64, 4, 128, 128, CAP_DMA | CAP_STAGED, DMA_FN(512, 128, 128, 4, 2, 4, 64)},
-    {160, 64, 2, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN_GENERAL(256, 128, 160, 4, 1, 2)},
-    {160, 64, 3, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN(256, 128, 160, 4, 1, 3, 64)},
+    {128, 64, 4, 128, 128, CAP_DMA | CAP_STAGED | CAP_GEGLU, DMA_FN(512, 128, 128, 4, 2, 4, 64), {}, {}, DMA_GEGLU_B(512, 128, 128, 4, 2, 4, 64)},
+    {160, 64, 2, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL | CAP_GEGLU, DMA_FN_GENERAL(256, 128, 160, 4, 1, 2), {}, {}, DMA_GEGLU_F(256, 128, 160, 4, 1, 2, 64)},
+    {160, 64, 3, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL | CAP_GEGLU, DMA_FN(256, 128, 160, 4, 1, 3, 64), {}, {}, DMA_GEGLU_B(256, 128, 160, 4, 1, 3, 64)},
     {160, 64, 4, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN(256, 128, 160, 4, 1, 4, 64)},
     // 5256: 256 x 128 with 32-wide K-tiles, 3 x 24 KiB stages = two workgroups per CU; stride-1 convs on conv_strip_kernel where it applies
-    {256, 32, 3, 256, 128, CAP_DMA, DMA_FN(512, 256, 128, 4, 2, 3, 32), {}, {{conv_strip_ok, {KERNEL(512, conv_strip_kernel, 2), NO_KERNEL}}}},
+    {256, 32, 3, 256, 128, CAP_DMA | CAP_GEGLU, DMA_FN(512, 256, 128, 4, 2, 3, 32), {}, {{conv_strip_ok, {KERNEL(512, conv_strip_kernel, 2), NO_KERNEL}}},
+     DMA_GEGLU(512, 256, 128, 4, 2, 3, 32)},
     // 512: 256 x 256 ping-pong; stride-1 convs on gemm_pps_kernel where it applies
     {512, 64, 2, 256, 256, CAP_DMA | CAP_WHOLE_K | CAP_TAIL | CAP_ONE_PER_CU,
      {KERNEL(512, gemm_pp_kernel, 0, false, false), KERNEL(512, gemm_pp_kernel, 0, true, false)},
@@ -2121,8 +1584,9 @@ static const Variant kVariants[] = {
      {{conv_pps_ok, {KERNEL(512, gemm_pps_kernel, false), KERNEL(512, gemm_pps_kernel, true)}},
       {strip256_ok, {XKERNEL(1024, conv_strip_kernel, 4), NO_KERNEL}}}},
     // 2320: 256 x 320 ping-pong (the GENERAL instantiation exists for GEMMs only)
-    {2320, 64, 2, 256, 320, CAP_DMA | CAP_WHOLE_K | CAP_WHOLE_N | CAP_TAIL | CAP_PANELS | CAP_ONE_PER_CU,
-     {KERNEL(512, gemm_pq_kernel, 0, 320, false), KERNEL(512, gemm_pq_kernel, 0, 320, true)}, {KERNEL(512, gemm_pq_kernel, 1, 320, false), NO_KERNEL}},
+    {2320, 64, 2, 256, 320, CAP_DMA | CAP_WHOLE_K | CAP_WHOLE_N | CAP_TAIL | CAP_PANELS | CAP_ONE_PER_CU | CAP_GEGLU,
+     {KERNEL(512, gemm_pq_kernel, 0, 320, false), KERNEL(512, gemm_pq_kernel, 0, 320, true)}, {KERNEL(512, gemm_pq_kernel, 1, 320, false), NO_KERNEL},
+     {}, {}, {KERNEL(512, gemm_pq_geglu_kernel, 320, 1), KERNEL(512, gemm_pq_geglu_kernel, 320, 2)}},
     // the register-staged fallback (operands beyond 4 GB, E4T_GEMM_REGSTAGE), logged as bare "gemm_kernel", GENERAL at run time
     {128, 64, 2, 128, 128, CAP_SPLITK, REG_FN(128, 128, 0), REG_FN(128, 128, 1)},
     {64, 64, 2, 64, 64, CAP_SPLITK, REG_FN(64, 64, 0), REG_FN(64, 64, 1)},
@@ -2468,10 +1932,39 @@ int launch_splitk_reduce(const GemmArgs& p, int nz, int batch_dim, bool vec8, hi
   return 0;
 }
 
+// ---- fused GEGLU epilogues (E4T_EPI_GEGLU / E4T_EPI_GEGLU_BWD) --------------------------------------------------------------------------
+// The flags do not enter the plan: a fused descriptor gets the plan of the plain descriptor of the same M, N, K.  The launch (and the exported
+// plan) is refused with E4T_ERR_NO_FUSED unless that plan is ONE pass of a CAP_GEGLU row with the vectorised bf16 epilogue over all rows.
+int epi_kind(const GemmArgs& p) { return (p.flags & E4T_EPI_GEGLU) ? EPI_GEGLU : (p.flags & E4T_EPI_GEGLU_BWD) ? EPI_GEGLU_BWD : EPI_PLAIN; }
+const char* geglu_refusal(const GemmPlan& pl, const GemmArgs& p, int tail, int batch) {
+  const int epi = epi_kind(p);
+  if ((p.flags & ~(E4T_EPI_GEGLU | E4T_EPI_GEGLU_BWD)) || ((p.flags & E4T_EPI_GEGLU) && (p.flags & E4T_EPI_GEGLU_BWD))) return "no other epilogue flag combines with it";
+  if (p.residual || p.rowbias || p.colstats || p.A2 || p.panel_rows || batch != 1) return "no residual / row bias / column statistics / two-source A / row panels / batch";
+  if (epi == EPI_GEGLU_BWD && p.bias) return "the backward kind takes no bias";
+  if (p.N % (epi == EPI_GEGLU ? 16 : 8) != 0 || p.ldaux % 8 != 0 || ((uintptr_t)p.aux & 15) != 0) return "the halves of u and the rows of aux must be whole 16-byte groups";
+  if (epi == EPI_GEGLU_BWD && (p.ldc < 2 * p.N || p.ldaux < 2 * p.N)) return "du and u are 2 N columns wide";
+  if (!(bf16_rows_aligned16(p))) return "the scalar epilogue would run (C rows not 16-byte aligned)";
+  if (tail) return "the plan hands tail rows to the tail stage";
+  if (pl.splitk > 1 || p.reduce_batch) return "the plan needs split-K";
+  if (pl.general_epi) return "the plan needs the GENERAL epilogue";
+  if (pl.run != pl.shape) return "the plan runs the register-staged fallback";
+  if (!(pl.run->caps & CAP_GEGLU) || !pl.run->geglu[epi - 1].text) return "the planned tile carries no fused GEGLU epilogue";
+  if (epi == EPI_GEGLU && p.N % pl.run->tn != 0) return "N is not a multiple of the planned tile's width";
+  return nullptr;
+}
+#define E4T_REFUSE_FUSED(pl, p, tail, batch)                                                                                              \
+  do {                                                                                                                                    \
+    if (epi_kind(p) != EPI_PLAIN)                                                                                                        \
+      if (const char* why = geglu_refusal(pl, p, tail, batch))                                                                            \
+        E4T_FAIL(E4T_ERR_NO_FUSED, "gemm: fused GEGLU M=%d N=%d K=%d not run (plan: tile %d, split-K %d): %s", p.M, p.N, p.K, pl.tile, pl.splitk, why); \
+  } while (0)
+
 int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
   int tail = 0;
   const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
   const Variant& v = *pl.run;
+  const int epi = conv ? EPI_PLAIN : epi_kind(p);
+  E4T_REFUSE_FUSED(pl, p, tail, batch);
   const int m_all = p.M;                 // (launch log: the caller's shape)
   if (tail) { p.M -= tail; p.tail_row0 = p.M; p.tail_rows = tail; }      // the tile grid covers [0, M - tail); gemm_tail() the rest
   int splitk = pl.splitk;
@@ -2502,7 +1995,7 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
                     (!p.bias || (((uintptr_t)p.bias & 15) == 0 && p.strideBias % 4 == 0)) &&
                     (!p.rowbias || (((uintptr_t)p.rowbias & 15) == 0 && p.ldrb % 4 == 0)) && ((uintptr_t)p.ws & 15) == 0;
   const int nz = p.reduce_batch ? splitk * batch : splitk;
-  const KernelEntry& k = select_entry(v, p, conv, pl.general_epi, splitk, batch);
+  const KernelEntry& k = epi != EPI_PLAIN ? v.geglu[epi - 1] : select_entry(v, p, conv, pl.general_epi, splitk, batch);
   if (!k.text) E4T_FAIL(-22, "gemm: no kernel is built for tile %d (%s, GENERAL %d)", pl.tile, conv ? "conv" : "gemm", (int)pl.general_epi);
   if (e4t_launch_log_enabled()) {
     // algorithmic bytes: every operand element once (conv: the input map once, not once per tap), the output once
@@ -2513,6 +2006,9 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
     if (p.flags & E4T_ACCUM) by += osz * (double)p.M * p.N;
     if (conv) E4T_LOG_LAUNCH("%s|conv mode%d %dx%d->%dx%d Cin%d Cout%d M%d splitk%d|%.0f|%.0f", k.text, p.mode, p.Hin, p.Win, p.Hout, p.Wout, p.Cin, p.N,
                              p.M, splitk, by, 2.0 * p.M * p.N * (double)p.K);
+    else if (epi != EPI_PLAIN)      // u written + h written | u read + du written (2 N columns each); dh is never stored
+      E4T_LOG_LAUNCH("%s|%s M%d N%d K%d batch%d splitk%d flags%d|%.0f|%.0f", k.text, epi == EPI_GEGLU ? "gemm_geglu" : "gemm_geglu_bwd", m_all, p.N, p.K, batch, splitk,
+                     p.flags, 2.0 * a_el + 2.0 * (double)p.N * p.K + (p.bias ? 4.0 * p.N : 0.0) + (epi == EPI_GEGLU ? 3.0 : 8.0) * (double)p.M * p.N, 2.0 * m_all * p.N * (double)p.K);
     else E4T_LOG_LAUNCH("%s|gemm M%d N%d K%d batch%d splitk%d flags%d|%.0f|%.0f", k.text, m_all, p.N, p.K, batch, splitk, p.flags,
                         by + (double)tail * (2.0 * p.K + (osz + (p.residual ? ((p.flags & E4T_RES_F32) ? 4.0 : 2.0) : 0.0)) * p.N), 2.0 * m_all * p.N * (double)p.K * batch);
     if (p.ws) log_splitk_reduce(p, nz, splitk * batch, vec8);
@@ -2541,6 +2037,7 @@ void fill_gemm_args(const e4t_gemm_desc* d, GemmArgs& p) {
   p.reduce_batch = (d->flags & E4T_REDUCE_BATCH) ? 1 : 0;
   p.colstats = d->colstats;
   p.panel_rows = d->panel_rows; p.panel_stride = d->panel_stride; p.panel_off = d->panel_off;
+  p.aux = d->aux; p.ldaux = d->ldaux;
 }
 
 void fill_conv_args(const e4t_conv_desc* d, GemmArgs& p) {
@@ -2586,6 +2083,7 @@ extern "C" int e4t_gemm_plan(const e4t_gemm_desc* d, e4t_gemm_plan_t* out) {
   int tail = 0;
   const GemmPlan pl = plan_gemm_tail(p, false, d->tile, d->splitk, batch, tail);
   export_plan(pl, p, batch, out, tail);      // (no workspace with tail rows: their plan is a single pass)
+  E4T_REFUSE_FUSED(pl, p, tail, batch);      // a fused descriptor: the plain plan is exported either way; the code says whether the fused kernel will run
   return 0;
 }
 
@@ -2624,6 +2122,7 @@ extern "C" int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream) {
     E4T_REQUIRE(batch == 1 && !d->rowbias && !d->colstats && !d->A2 && !(d->flags & (E4T_ACCUM | E4T_REDUCE_BATCH)) && d->splitk <= 1,
                 "gemm_nt: row panels do not combine with batch / row bias / column statistics / two-source A / accumulate / split-K");
   }
+  E4T_REQUIRE(!(d->flags & (E4T_EPI_GEGLU | E4T_EPI_GEGLU_BWD)) || d->aux, "gemm_nt: the fused GEGLU epilogues need aux (h out / u in)");
   GemmArgs p;
   fill_gemm_args(d, p);
   return launch_gemm(p, false, d->tile, d->workspace_bytes, d->splitk, batch, (hipStream_t)stream);
@@ -2632,7 +2131,7 @@ extern "C" int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream) {
 extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   E4T_REQUIRE(d && d->A && d->B && d->C, "gemm_tn: null operand");
   E4T_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->batch <= 1 && !d->A2 && !d->rowbias, "gemm_tn: bad / unsupported arguments");
-  E4T_REQUIRE(!(d->flags & E4T_ACT_GELU), "gemm_tn: the GELU epilogue is not built for the TN kernel");
+  E4T_REQUIRE(!(d->flags & (E4T_ACT_GELU | E4T_EPI_GEGLU | E4T_EPI_GEGLU_BWD)), "gemm_tn: the GELU / GEGLU epilogues are not built for the TN kernel");
   E4T_REQUIRE(d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && ((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0,
               "gemm_tn: M, N, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
   GemmArgs p;      // (not fill_gemm_args: the fields the TN kernel does not support — lda2, strides, row panels, ... — stay zero whatever the caller left there)

@@ -49,6 +49,8 @@ struct GemmArgs {
   long long strideA, strideB, strideC, strideBias;
   float* colstats;                       // optional [M/32][N][2] column statistics of the output (fast bf16 epilogue only)
   unsigned a_bytes, a2_bytes, b_bytes;   // operand extents from the (batch-adjusted) base pointers, for buffer resources (pp kernel)
+  void* aux;                             // fused GEGLU epilogues (write_tile<..., EPI>): h [M][ldaux] (out, forward) / u [M][ldaux] (in, backward)
+  int ldaux;
 };
 
 namespace {
@@ -56,6 +58,16 @@ namespace {
 constexpr int BK = 64;        // K-tile (bf16 elements)
 constexpr int LDS_LD = BK + 8;  // padded LDS row stride (elements): 144 B
 
+// Epilogue kinds of write_tile (a template argument: separate instantiations, like GENERAL)
+constexpr int EPI_PLAIN = 0, EPI_GEGLU = 1, EPI_GEGLU_BWD = 2;
+// EPI_GEGLU: C = u [M][N = 2H].  A wave's WN-wide tile holds WN/2 "value" columns of u and, behind them, the WN/2 "gate" columns that belong
+// to them, so that the wave forms h = value * gelu(gate) from its own staging area.  Column c of the tile whose plain origin would be n0 (c
+// counted from n0; any multiple of WN added to both cancels) -> the column of u, = the row of W1 and the entry of the bias.
+template <int WN>
+__device__ __forceinline__ int geglu_col(int n0, int c, int N) {
+  const int wn = c / WN, cw = c - wn * WN;
+  return (cw < WN / 2 ? 0 : (N >> 1)) + (n0 >> 1) + wn * (WN / 2) + (cw < WN / 2 ? cw : cw - WN / 2);
+}
 
 template <bool GELU_OK = true>
 __device__ __forceinline__ void epilogue_store(const GemmArgs& p, float v, int row, int col) {
@@ -97,13 +109,20 @@ __device__ __forceinline__ bf16_t* wave_stage(bf16_t* smem, int wave) { return s
 // and no compiler-placed vmcnt(0) sits between the K loop and the staging writes, so the operand DMA of the NEXT tile, in flight
 // at this point, is not drained in front of the epilogue (vmcnt is an in-order counter: waiting for a load issued here means
 // waiting for every DMA issued before it).
-template <int WM, int WN, int FM, int FN, bool GENERAL = false, bool PRE = false>
+// EPI (fast bf16 path only; the launcher admits nothing else): the staging is the plain one — bf16(acc * alpha + bias), so the fused results
+// are bitwise those of the plain GEMM followed by the standalone GEGLU kernel (same helper, common.h) — and the STORE phase differs:
+//   EPI_GEGLU      (nw = wave-tile origin in the tile raster of width 2H; value columns nw/2 .., see geglu_col): per row, the staged value
+//                  chunks go to u[:, nw/2 ..], the gate chunks to u[:, H + nw/2 ..], and h = value * gelu(gate), computed from the staged bf16
+//                  values after the accumulators are dead, to aux[:, nw/2 ..];
+//   EPI_GEGLU_BWD  (N = H; the staged tile is dh, which is never stored): per 16-byte chunk of dh at column j the chunks of u = aux at j and
+//                  H + j are loaded (unconditionally, RB at a time, like the residual) and du[:, j], du[:, H + j] are written to C.
+template <int WM, int WN, int FM, int FN, bool GENERAL = false, bool PRE = false, int EPI = EPI_PLAIN>
 __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][FN], bf16_t* stage, int lane, int mw, int nw,
                                            unsigned long long* dt_ptr = nullptr, const float* pre_bias = nullptr, const float* pre_rb = nullptr) {
   const int frow = lane & 31, fhi = lane >> 5;
   // ---- epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ----
   const bool partial = p.ws != nullptr;
-  if (!partial && p.fast_epi) {
+  if (EPI != EPI_PLAIN || (!partial && p.fast_epi)) {
     // bf16 output: stage the wave's WM x WN tile through LDS (the operand tiles are dead after the loop's final
     // barrier) so that C is written — and the residual read — as 16-byte chunks, 128 B contiguous per row.
     // alpha, bias, row bias and GELU are applied in fp32 before the bf16 rounding; the residual is added to the
@@ -127,7 +146,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
     } else {
 #pragma unroll
       for (int j = 0; j < FN; ++j) {
-        const int col = min(nw + j * 32 + frow, p.N - 1);
+        const int col = min(EPI == EPI_GEGLU ? geglu_col<WN>(nw, j * 32 + frow, p.N) : nw + j * 32 + frow, p.N - 1);
         bv[j] = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
@@ -184,6 +203,69 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
     if constexpr (PRE) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
     else __syncthreads();
     WT_STAMP(15);
+    if constexpr (EPI == EPI_GEGLU) {
+      static_assert(WN % 16 == 0, "value / gate halves of whole 16-byte chunks");
+      constexpr int HW = WN / 2, HCPR = HW / 8;          // value columns of the wave tile; their 16-byte chunks per row
+      constexpr int HNIT = (WM * HCPR + 63) / 64;
+      const int H = p.N >> 1, hw0 = nw >> 1;
+      bf16_t* Ub = (bf16_t*)p.C;
+      bf16_t* Hb = (bf16_t*)p.aux;
+#pragma unroll
+      for (int it = 0; it < HNIT; ++it) {
+        const int idx = it * 64 + lane;
+        const int rl = idx / HCPR, cch = idx - rl * HCPR;
+        const int row = mw + rl, col = hw0 + cch * 8;
+        if (idx < WM * HCPR && row < p.M && col < H) {
+          const uint4 va = *(const uint4*)(stage + rl * ELD + cch * 8), vg = *(const uint4*)(stage + rl * ELD + HW + cch * 8);
+          float a[8], g[8];
+          unpack8(va, a);
+          unpack8(vg, g);
+#pragma unroll
+          for (int k = 0; k < 8; ++k) a[k] = geglu_f(a[k], g[k]);
+          *(uint4*)(Ub + (size_t)row * p.ldc + col) = va;
+          *(uint4*)(Ub + (size_t)row * p.ldc + H + col) = vg;
+          *(uint4*)(Hb + (size_t)row * p.ldaux + col) = pack8(a);
+        }
+      }
+      return;
+    }
+    if constexpr (EPI == EPI_GEGLU_BWD) {
+      constexpr int BCPR = WN / 8, BNIT = (WM * BCPR + 63) / 64, BRB = BNIT < 4 ? BNIT : 4;
+      const int H = p.N;
+      const bf16_t* Ub = (const bf16_t*)p.aux;
+      bf16_t* Db = (bf16_t*)p.C;
+#pragma unroll
+      for (int it0 = 0; it0 < BNIT; it0 += BRB) {
+        uint4 ua[BRB], ug[BRB];
+#pragma unroll
+        for (int u = 0; u < BRB; ++u) {
+          const int idx = min((it0 + u) * 64 + lane, WM * BCPR - 1);
+          const int rl = idx / BCPR, cch = idx - rl * BCPR;
+          const int row = min(mw + rl, p.M - 1), col = min(nw + cch * 8, H - 8);
+          ua[u] = *(const uint4*)(Ub + (size_t)row * p.ldaux + col);
+          ug[u] = *(const uint4*)(Ub + (size_t)row * p.ldaux + H + col);
+        }
+#pragma unroll
+        for (int u = 0; u < BRB; ++u) {
+          const int it = it0 + u;
+          if (it >= BNIT) break;
+          const int idx = it * 64 + lane;
+          const int rl = idx / BCPR, cch = idx - rl * BCPR;
+          const int row = mw + rl, col = nw + cch * 8;
+          if (idx < WM * BCPR && row < p.M && col < H) {
+            float a[8], g[8], d[8], oa[8], og[8];
+            unpack8(ua[u], a);
+            unpack8(ug[u], g);
+            unpack8(*(const uint4*)(stage + rl * ELD + cch * 8), d);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { oa[k] = geglu_da_f(d[k], g[k]); og[k] = geglu_dg_f(d[k], a[k], g[k]); }
+            *(uint4*)(Db + (size_t)row * p.ldc + col) = pack8(oa);
+            *(uint4*)(Db + (size_t)row * p.ldc + H + col) = pack8(og);
+          }
+        }
+      }
+      return;
+    }
     constexpr int CPR = WN / 8;          // 16-byte chunks per row
     constexpr int NIT = (WM * CPR + 63) / 64;
     bf16_t* Cb = (bf16_t*)p.C;

@@ -25,6 +25,7 @@ class GemmDesc(C.Structure):
         ("strideA", i64), ("strideB", i64), ("strideC", i64), ("strideBias", i64),
         ("alpha", f32), ("ldrb", i32), ("colstats", vp),
         ("panel_rows", i32), ("panel_stride", i32), ("panel_off", i32),
+        ("aux", vp), ("ldaux", i32),
     ]
 
 
@@ -120,6 +121,8 @@ SIGNATURES = {
 
 # flag / enum mirrors of the header
 OUT_F32, RES_F32, ACT_GELU, ACCUM, REDUCE_BATCH = 1, 2, 4, 8, 16
+EPI_GEGLU, EPI_GEGLU_BWD = 32, 64      # GEGLU fused into the GEMM epilogue (e4t_hip.h)
+ERR_NO_FUSED = -95                     # e4t_gemm_nt: no fused kernel for the descriptor's plan; nothing was launched
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 1, 2, 3, 4, 5
 WO_STORE_F32, WO_OFFSETS_ONLY = 1, 2
 SAMPLER_MAX_HIST, SAMPLER_ROW = 4, 16

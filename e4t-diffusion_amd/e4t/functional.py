@@ -186,6 +186,93 @@ def linear(x, weight, bias, prep, residual=None, x2=None, gelu=False, out_f32=Fa
 
 
 # ----------------------------------------------------------------------------------------------
+# GEGLU feed-forward in one autograd node:  u = x W1^T + b1,  h = u[:, :H] * gelu(u[:, H:]),  y = h W2^T + b2 + residual
+# ----------------------------------------------------------------------------------------------
+def has_fused_feed_forward():
+    """the backend offers the GEMMs with the GEGLU in their epilogue (the CPU suite's emulation backend does not)"""
+    be = ops.backend()
+    return hasattr(be, "gemm_geglu") or hasattr(be, "gemm_geglu_bwd")
+
+
+def _linear_param_grads(ctx_needs_w, ctx_needs_b, weight, bias, dyb, x):
+    """weight / bias gradient of y = x W^T + b as LinearFn forms them (into the .grad slots when the trainer opted in)"""
+    dw = db = None
+    if ctx_needs_w:
+        N, kw = weight.shape[0], weight[0].numel()
+        g = _grad_slot(weight)
+        if g is not None and x.shape[1] == kw:
+            _weight_grad(dyb, x, out=g.view(N, kw))
+        else:
+            dw = _weight_grad(dyb, x)
+            if dw.shape[1] != kw:
+                dw = dw[:, :kw].contiguous()
+            dw = dw.reshape(weight.shape)
+    if ctx_needs_b:
+        g = _grad_slot(bias) if (bias.requires_grad and bias.is_leaf) else None
+        if g is not None:
+            ops.backend().colsum(dyb, out=g, accumulate=True)
+        else:
+            db = ops.backend().colsum(dyb)
+    return dw, db
+
+
+class FeedForwardFn(torch.autograd.Function):
+    """fc1 + GEGLU + fc2 (+ bias, + residual).  With a backend that has them, fc1 writes u and h from one launch (gemm_geglu) and the backward
+    forms du in the epilogue of fc2's data-gradient GEMM (gemm_geglu_bwd: dh never exists); a backend that lacks one of the two, or answers
+    None for a shape, gets the unfused pair for it — bit for bit the same tensors.  Saved: x, u, and h only when W2 needs its gradient."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, residual, prep1: PreparedLinear, prep2: PreparedLinear):
+        be = ops.backend()
+        w1c, _ = prep1.get()
+        w2c, _ = prep2.get()
+        K, H = x.shape[1], w2.shape[1]
+        w1v = w1c[:, :K] if w1c.shape[1] != K else w1c
+        w2v = w2c[:, :H] if w2c.shape[1] != H else w2c
+        # (column statistics of u, were a caller ever to ask for them, come from the plain epilogue only)
+        uh = be.gemm_geglu(x, w1v, b1) if hasattr(be, "gemm_geglu") and not prep1.colstats else None
+        if uh is None:
+            u = be.gemm(x, w1v, bias=b1, out_dtype=act_dtype(), colstats=prep1.colstats)
+            uh = (u, be.geglu_fwd(u))
+        u, h = uh
+        y = be.gemm(h, w2v, bias=b2, residual=residual, out_dtype=act_dtype(), colstats=prep2.colstats)
+        ctx.prep1, ctx.prep2 = prep1, prep2
+        ctx.params = (w1, b1, w2, b2)
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        ctx.save_for_backward(x if w1.requires_grad else None, u, h if w2.requires_grad else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        be = ops.backend()
+        x, u, h = ctx.saved_tensors
+        w1, b1, w2, b2 = ctx.params
+        need = ctx.needs_input_grad
+        dyb = (dy if dy.dtype == act_dtype() else dy.to(act_dtype())).contiguous()
+        dx = dw1 = db1 = dw2 = db2 = dres = None
+        if need[0] or need[1] or (b1 is not None and need[2]):
+            _, w2T = ctx.prep2.get()
+            N2, H = w2.shape
+            w2Tn = w2T[:, :N2] if w2T.shape[1] != N2 else w2T
+            du = be.gemm_geglu_bwd(dyb, w2Tn, u) if hasattr(be, "gemm_geglu_bwd") else None
+            if du is None:
+                du = be.geglu_bwd(u, be.gemm(dyb, w2Tn))
+            if need[0]:
+                _, w1T = ctx.prep1.get()
+                N1 = w1.shape[0]
+                dx = be.gemm(du, w1T[:, :N1] if w1T.shape[1] != N1 else w1T)
+            dw1, db1 = _linear_param_grads(need[1], b1 is not None and need[2], w1, b1, du, x)
+        dw2, db2 = _linear_param_grads(need[3], b2 is not None and need[4], w2, b2, dyb, h)
+        if ctx.res_dtype is not None and need[5]:
+            dres = dy if dy.dtype == ctx.res_dtype else dy.to(ctx.res_dtype)
+        return dx, dw1, db1, dw2, db2, dres, None, None
+
+
+def feed_forward(x, w1, b1, prep1, w2, b2, prep2, residual=None):
+    return FeedForwardFn.apply(x, w1, b1, w2, b2, residual, prep1, prep2)
+
+
+# ----------------------------------------------------------------------------------------------
 # Weight-offset modulated projections (cross_attention.py:506,516,518)
 # ----------------------------------------------------------------------------------------------
 class WOSlot:

@@ -30,6 +30,9 @@ class FeedForward(nn.Module):
         self._prep = Fn.PreparedLinear(self.net[2].weight)
 
     def forward(self, x2d, residual=None):
+        if Fn.has_fused_feed_forward():      # one autograd node; the GEGLU rides in the epilogues of the fc1 / fc2 data-gradient GEMMs
+            g = self.net[0]
+            return Fn.feed_forward(x2d, g.proj.weight, g.proj.bias, g._prep, self.net[2].weight, self.net[2].bias, self._prep, residual=residual)
         h = self.net[0](x2d)
         return Fn.linear(h, self.net[2].weight, self.net[2].bias, self._prep, residual=residual)
 

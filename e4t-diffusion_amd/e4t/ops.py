@@ -232,6 +232,55 @@ class HipBackend:
             out._e4t_colstats = cs          # consumed by groupnorm_fwd (the GroupNorm of this activation skips its statistics pass)
         return out
 
+    # GEGLU fused into the epilogue of the feed-forward GEMMs (e4t_hip.h: E4T_EPI_GEGLU / E4T_EPI_GEGLU_BWD).  Both return None when the library
+    # has no fused kernel for the plan of the shape (E4T_ERR_NO_FUSED from e4t_gemm_plan: nothing is launched); the caller then runs gemm +
+    # geglu_fwd / geglu_bwd, whose results the fused launches equal bit for bit.
+    def _gemm_fused_geglu(self, key, flag, a, b, bias, M, N, K, flops, nbytes, aux=None):
+        """plans first (host only) and allocates the outputs only when the fused kernel will run.  flag EPI_GEGLU: returns (u [M, N], h [M, N / 2]);
+        EPI_GEGLU_BWD (aux = u): returns du [M, 2 N]; None when refused."""
+        fwd = flag == _C.EPI_GEGLU
+        for t, name in ((a, "A"), (b, "B")) + (() if fwd else ((aux, "aux"),)):
+            _rowmajor(t, f"{key} {name}")
+        d = _C.GemmDesc()
+        d.A, d.B, d.bias = _ptr(a), _ptr(b), _ptr(bias)
+        d.M, d.N, d.K, d.K1 = M, N, K, K
+        d.lda, d.ldb = a.stride(0), b.stride(0)
+        d.ldc, d.ldaux = (N, N // 2) if fwd else (2 * N, aux.stride(0))      # fresh outputs are dense
+        d.flags, d.batch, d.alpha = flag, 1, 1.0
+        pl = _C.GemmPlan()
+        rc = self.lib.e4t_gemm_plan(C.byref(d), C.byref(pl))
+        if rc == _C.ERR_NO_FUSED:
+            return None
+        _C.check(rc, "e4t_gemm_plan")
+        out = torch.empty((M, N if fwd else 2 * N), dtype=bf16, device=a.device)
+        if fwd:
+            aux = torch.empty((M, N // 2), dtype=bf16, device=a.device)
+        d.C, d.aux = _ptr(out), _ptr(aux)
+        st = _stream()
+        self._timed(f"{key}{pl.tile}" + (f"s{pl.stages}" if pl.stages else ""), flops,
+                    lambda: _C.check(self.lib.e4t_gemm_nt(C.byref(d), st), "e4t_gemm_nt"), nbytes)
+        return (out, aux) if fwd else out
+
+    # algorithmic FLOP of the fused ops = the GEMM's 2 M N K only: the standalone geglu ops count 0 FLOP as well, so gemm + geglu rows and fused rows
+    # of a roofline compare in FLOP; their bytes are the operands actually read and written (dh / the re-read of u are gone)
+    def gemm_geglu(self, x, w, bias):
+        """(u, h) = (x . w^T + bias [M, 2H], u[:, :H] * gelu(u[:, H:]) [M, H]) in one launch; None: not fused for this shape."""
+        (M, K), N = x.shape, w.shape[0]
+        if x.dtype != bf16 or w.dtype != bf16 or N % 2 or w.shape[1] != K:
+            return None
+        # x, w, bias read; u and h written
+        return self._gemm_fused_geglu("gemm_geglu", _C.EPI_GEGLU, x, w, bias, M, N, K, 2.0 * M * N * K,
+                                      2.0 * M * K + 2.0 * N * K + (4.0 * N if bias is not None else 0.0) + 3.0 * M * N)
+
+    def gemm_geglu_bwd(self, dy, w2T, u):
+        """du [M, 2H] = geglu_bwd(u, dy . w2T^T) with dh = dy . w2T^T [M, H] never stored (w2T: [H, K] = W2 transposed); None: not fused."""
+        (M, K), H = dy.shape, w2T.shape[0]
+        if dy.dtype != bf16 or w2T.dtype != bf16 or u.dtype != bf16 or u.shape != (M, 2 * H) or w2T.shape[1] != K:
+            return None
+        # dy, w2T, u read; du written
+        return self._gemm_fused_geglu("gemm_geglu_bwd", _C.EPI_GEGLU_BWD, dy, w2T, None, M, H, K, 2.0 * M * H * K,
+                                      2.0 * M * K + 2.0 * H * K + 8.0 * M * H, aux=u)
+
     def gemm_tn(self, a, b, *, out=None, out_dtype=f32, accum=False, alpha=1.0, splitk=0):
         """C[M, N] = alpha * a^T . b with a = [K, M], b = [K, N] (bf16, unit inner stride): contraction over the rows —
         dW = dY^T . X without transposes."""

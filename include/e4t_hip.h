@@ -46,6 +46,18 @@ int e4t_set_launch_log(const char* path);
 #define E4T_ACT_GELU 4  /* exact-erf GELU after bias, before residual */
 #define E4T_ACCUM 8     /* C += result (read-modify-write in C's dtype) */
 #define E4T_REDUCE_BATCH 16 /* sum the batch entries into ONE C (needs workspace) */
+/* GEGLU fused into the epilogue of e4t_gemm_nt (attention.py:428-430, the feed-forward of every transformer block).  H = N / 2 resp. N.
+ * E4T_EPI_GEGLU      C = u [M][N = 2H] = A . B^T + bias exactly as without the flag, and additionally aux = h [M][H] (row stride ldaux) with
+ *                    h[m][j] = u[m][j] * gelu(u[m][H + j]) formed from the bf16-rounded u: bitwise what e4t_geglu_fwd makes of u.
+ * E4T_EPI_GEGLU_BWD  the product dh [M][N = H] is not stored; C = du [M][2H] (row stride ldc) = what e4t_geglu_bwd makes of aux = u [M][2H]
+ *                    (row stride ldaux) and the bf16-rounded dh.
+ * bf16 everywhere, 16-byte aligned rows, batch 1, no residual / row bias / colstats / A2 / panels / other flags; BWD: no bias.  Built for the tiles
+ * and stage counts the planner gives the feed-forward shapes of the training step and of SD-2.x @768 (gemm.hip, kVariants: CAP_GEGLU), in a single
+ * pass over all rows, forward with N a multiple of the tile width: e4t_gemm_nt returns E4T_ERR_NO_FUSED (nothing launched, e4t_last_error
+ * says why) when the plan of the same M, N, K is anything else — the caller then runs e4t_gemm_nt + e4t_geglu_fwd / e4t_geglu_bwd. */
+#define E4T_EPI_GEGLU 32
+#define E4T_EPI_GEGLU_BWD 64
+#define E4T_ERR_NO_FUSED (-95)
 
 /* C[M,N] = epi(alpha * A[M,K] . B[N,K]^T): F.linear / 1x1 conv / their dX and dW GEMMs.
  * Replaces cross_attention.py:506,516,518,534 ; attention.py:376,419 ; transformer_2d.py:153,205,
@@ -84,6 +96,8 @@ typedef struct {
   int panel_off;       /* of a [16][257] ViT token matrix (panel_rows 256, stride 257, offset 1) run as 16 full 256-row tiles instead of
                           17 ragged ones ([3P] open_clip ViT linears, encoder.py:154).  N % 320 == 0, K % 64 == 0; no batch / row bias /
                           colstats / A2 / accumulate / split-K */
+  void* aux;           /* E4T_EPI_GEGLU: out h, bf16 [M][ldaux]; E4T_EPI_GEGLU_BWD: in u, bf16 [M][ldaux]; else unused */
+  int ldaux;
 } e4t_gemm_desc;
 /* returns 0 (or 1, see colstats) on success, a negative errno-style code on error */
 int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream);
