@@ -740,3 +740,72 @@ extern "C" int e4t_im2col_T(const void* x, void* out, int Bn, int Hin, int Win, 
   E4T_CHECK_LAUNCH("im2col_T_kernel");
   return 0;
 }
+
+// ---- masked diffusion loss (the reference's README.md:112-115 TODO on the loss of pretrain_e4t.py:645-647) ----
+// loss = sum_{b,c,p} w[b][p] * d^2 / den,  d = pred - target,  den = C * max(sum(w), 1);  dpred = g * 2 * w * d / den.
+// Two-stage reductions in a fixed order (per-thread pixel stride, block_sum, then one block over the partials): no atomics, so a
+// result is bitwise the same from run to run.  Forward = partial + final, backward = one streaming pass over the saved w * d.
+namespace {
+constexpr int MMSE_MAX_BLOCKS = 1024;
+
+// one thread per pixel (b, p), all C channels: w is read once, sum(w) falls out of the same pass.  wd (pred's layout, may be null) = w * d.
+__global__ __launch_bounds__(256) void masked_mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ w,
+                                                                 float* __restrict__ wd, float* __restrict__ partial, int B, int C, int HW, int nhwc) {
+  __shared__ float red[32];
+  const long long npix = (long long)B * HW;
+  float se = 0.f, sw = 0.f;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < npix; q += (long long)gridDim.x * 256) {
+    const long long b = q / HW;
+    const int p = (int)(q - b * HW);
+    const float wq = w[q];
+    sw += wq;
+    for (int c = 0; c < C; ++c) {
+      const long long it = (b * C + c) * HW + p;
+      const long long ip = nhwc ? q * C + c : it;
+      const float d = pred[ip] - target[it];
+      const float v = wq * d;
+      if (wd) wd[ip] = v;
+      se = fmaf(v, d, se);
+    }
+  }
+  se = block_sum(se, red);
+  sw = block_sum(sw, red + 16);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = se; partial[gridDim.x + blockIdx.x] = sw; }
+}
+// out[0] = loss, out[1] = den
+__global__ __launch_bounds__(256) void masked_mse_final_kernel(const float* __restrict__ partial, int nb, int C, float* __restrict__ out) {
+  __shared__ float red[32];
+  float se = 0.f, sw = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) { se += partial[i]; sw += partial[nb + i]; }
+  se = block_sum(se, red);
+  sw = block_sum(sw, red + 16);
+  if (threadIdx.x == 0) {
+    const float den = (float)C * fmaxf(sw, 1.f);
+    out[0] = se / den;
+    out[1] = den;
+  }
+}
+__global__ __launch_bounds__(256) void masked_mse_bwd_kernel(const float* __restrict__ wd, const float* __restrict__ stats, const float* __restrict__ g,
+                                                             float* __restrict__ dpred, long long n) {
+  const float k = g[0] * 2.f / stats[1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dpred[i] = k * wd[i];
+}
+}  // namespace
+
+extern "C" int e4t_masked_mse_fwd(const float* pred, const float* target, const float* w, float* wd, float* stats, int B, int C, int HW, int pred_nhwc,
+                                  e4t_stream s) {
+  static_assert(E4T_MASKED_MSE_STATS == 2 + 2 * MMSE_MAX_BLOCKS, "stats = {loss, den} + the two partial rows");
+  E4T_REQUIRE(pred && target && w && stats && B > 0 && C > 0 && HW > 0, "masked_mse_fwd: bad arguments");
+  const int nb = (int)min(cdivl((long long)B * HW, 256), (long long)MMSE_MAX_BLOCKS);
+  hipLaunchKernelGGL(masked_mse_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, wd, stats + 2, B, C, HW, pred_nhwc);
+  E4T_CHECK_LAUNCH("masked_mse_partial_kernel");
+  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)(stats + 2), nb, C, stats);
+  E4T_CHECK_LAUNCH("masked_mse_final_kernel");
+  return 0;
+}
+extern "C" int e4t_masked_mse_bwd(const float* wd, const float* stats, const float* g, float* dpred, long long n, e4t_stream s) {
+  E4T_REQUIRE(wd && stats && g && dpred && n > 0, "masked_mse_bwd: bad arguments");
+  hipLaunchKernelGGL(masked_mse_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, wd, stats, g, dpred, n);
+  E4T_CHECK_LAUNCH("masked_mse_bwd_kernel");
+  return 0;
+}

@@ -85,14 +85,38 @@ def make_transforms(size, random_crop=False):
 
 
 class E4TDataset:
-    """pretrain_e4t.py:147-180.  ``dataset_name``: a directory, several joined by "::", or a `datasets` name."""
+    """pretrain_e4t.py:147-180.  ``dataset_name``: a directory, several joined by "::", or a `datasets` name.
 
-    def __init__(self, dataset_name, resolution=512):
+    ``mask_dataset`` (the masked diffusion loss, the reference's README.md:112-115): directories joined by "::", one per image
+    directory in the same order.  The mask of ``<image_root>/<rel>/<stem>.<ext>`` is ``<mask_root>/<rel>/<stem>.<e>`` with <e> the
+    first of ``("png",) + IMAGE_EXTENSIONS`` that exists; it is read as 8-bit grey ("L"), must have its image's size, and a sample
+    then carries ``mask``, a uint8 H x W array that goes through the image's own plan on the device (``e4t_mask_prep``)."""
+
+    def __init__(self, dataset_name, resolution=512, mask_dataset=None):
         from_datasets = False
+        self.masks = None
         if os.path.isdir(dataset_name) or "::" in dataset_name:
             self.dataset = []
-            for name in dataset_name.split("::"):
-                self.dataset += _list_image_files_recursively(name)
+            roots = dataset_name.split("::")
+            mask_roots = mask_dataset.split("::") if mask_dataset else None
+            if mask_roots is not None and len(mask_roots) != len(roots):
+                raise ValueError(f"mask_dataset names {len(mask_roots)} directories for {len(roots)} image directories")
+            masks, missing = [], []
+            for k, name in enumerate(roots):
+                files = _list_image_files_recursively(name)
+                self.dataset += files
+                for f in files if mask_roots is not None else ():
+                    stem = os.path.join(mask_roots[k], os.path.splitext(os.path.relpath(f, name))[0])
+                    found = next((stem + "." + e for e in ("png",) + IMAGE_EXTENSIONS if os.path.isfile(stem + "." + e)), None)
+                    masks.append(found)
+                    if found is None:
+                        missing.append(stem + ".*")
+            if missing:
+                raise FileNotFoundError(f"{len(missing)} images have no mask, e.g. {', '.join(missing[:5])}")
+            if mask_roots is not None:
+                self.masks = masks
+        elif mask_dataset:
+            raise ValueError("mask_dataset is supported for image directories only, not for `datasets` sources")
         else:
             from datasets import load_dataset
             self.dataset = load_dataset(dataset_name, split="train")
@@ -112,9 +136,19 @@ class E4TDataset:
             image = Image.open(image)
         return np.ascontiguousarray(np.asarray(image.convert("RGB"), dtype=np.uint8))
 
+    def load_mask(self, idx, shape) -> np.ndarray:
+        from PIL import Image
+        mask = np.ascontiguousarray(np.asarray(Image.open(self.masks[idx]).convert("L"), dtype=np.uint8))
+        if mask.shape != tuple(shape):
+            raise ValueError(f"mask {self.masks[idx]} is {mask.shape[0]}x{mask.shape[1]}, its image {self.dataset[idx]} is {shape[0]}x{shape[1]}")
+        return mask
+
     def __getitem__(self, idx, rng=random):
         image = self.load_rgb(idx)
-        return dict(image=image, plan=self.processor.plan(image.shape[0], image.shape[1], rng))
+        sample = dict(image=image, plan=self.processor.plan(image.shape[0], image.shape[1], rng))
+        if self.masks is not None:
+            sample["mask"] = self.load_mask(idx, image.shape[:2])
+        return sample
 
 
 def braceexpand(pattern: str):
@@ -250,9 +284,11 @@ class _Slot:
         self.h_pool = self.d_pool = None
         self.h_table = self.d_table = None
         self.out = None
+        self.h_moff = self.d_moff = None        # masks (E4TDataset(mask_dataset=...)): byte offsets in the pool, and the loss mask
+        self.out_mask = None
         self.event = None
 
-    def ensure(self, nbytes, B, S):
+    def ensure(self, nbytes, B, S, masks=False):
         pin = self.device.type == "cuda"
         if self.h_pool is None or self.h_pool.numel() < nbytes:
             cap = int(nbytes * 1.25) + 4096
@@ -261,15 +297,32 @@ class _Slot:
         if self.h_table is None or self.h_table.shape[0] != B:
             self.h_table = torch.empty((B, 8), dtype=torch.int64, pin_memory=pin)
             self.d_table = torch.empty((B, 8), dtype=torch.int64, device=self.device)
+        if masks and (self.h_moff is None or self.h_moff.shape[0] != B):
+            self.h_moff = torch.empty(B, dtype=torch.int64, pin_memory=pin)
+            self.d_moff = torch.empty(B, dtype=torch.int64, device=self.device)
 
 
-def pack_batch(samples, size, h_pool=None, h_table=None):
-    """samples: [{image: uint8 HxWx3, plan: (nh, nw, y0, x0, flip)}] -> (pool bytes, int64 [B,8] table) (host tensors).
-    Image offsets are 16-byte aligned."""
+def packed_nbytes(samples):
+    """bytes of the pool pack_samples fills: every image, then every mask, each rounded up to 16"""
+    return sum((s["image"].size + 15) // 16 * 16 + ((s["mask"].size + 15) // 16 * 16 if "mask" in s else 0) for s in samples)
+
+
+def pack_samples(samples, size, h_pool=None, h_table=None, h_mask_off=None):
+    """samples: [{image: uint8 HxWx3, plan: (nh, nw, y0, x0, flip)}] -> (pool bytes, int64 [B,8] table, bytes used, mask offsets)
+    (host tensors).  Image offsets are 16-byte aligned.  Samples that carry ``mask`` (uint8 HxW, all or none): the masks are packed
+    behind the images (the image part of the pool is what it is without masks), 16-byte aligned as well, and the fourth value is
+    their int64 [B] byte offsets; without masks it is None."""
     offs, total = [], 0
     for s in samples:
         offs.append(total)
         total += (s["image"].size + 15) // 16 * 16
+    with_masks = any("mask" in s for s in samples)
+    moffs = []
+    for s in samples if with_masks else ():
+        if "mask" not in s or s["mask"].shape != s["image"].shape[:2] or s["mask"].dtype != np.uint8:
+            raise ValueError("every sample of a masked batch needs a uint8 mask of its image's height and width")
+        moffs.append(total)
+        total += (s["mask"].size + 15) // 16 * 16
     if h_pool is None:
         h_pool = torch.empty(total, dtype=torch.uint8)
     if h_table is None:
@@ -284,11 +337,27 @@ def pack_batch(samples, size, h_pool=None, h_table=None):
             raise ValueError(f"crop window ({y0},{x0})+{size} outside the resized image {nh}x{nw}")
         pool_np[off:off + img.size] = img.reshape(-1)
         h_table[i] = torch.tensor([off, H, W, nh, nw, y0, x0, flip], dtype=torch.int64)
-    return h_pool, h_table, total
+    if not with_masks:
+        return h_pool, h_table, total, None
+    if h_mask_off is None:
+        h_mask_off = torch.empty(len(samples), dtype=torch.int64)
+    for i, (s, off) in enumerate(zip(samples, moffs)):
+        pool_np[off:off + s["mask"].size] = s["mask"].reshape(-1)
+        h_mask_off[i] = off
+    return h_pool, h_table, total, h_mask_off
+
+
+def pack_batch(samples, size, h_pool=None, h_table=None, h_mask_off=None):
+    """``pack_samples`` for callers that know what they pack: (pool, table, bytes used) for plain samples, and the masks' offsets
+    as a fourth value for samples that carry masks"""
+    out = pack_samples(samples, size, h_pool, h_table, h_mask_off)
+    return out if out[3] is not None else out[:3]
 
 
 class DeviceLoader:
-    """Iterates ``dict(pixel_values=fp32 [B,3,S,S] on `device`)`` over an ``E4TDataset``.
+    """Iterates ``dict(pixel_values=fp32 [B,3,S,S] on `device`)`` over an ``E4TDataset``; over one built with ``mask_dataset``
+    the batches also carry ``loss_mask=fp32 [B,S/8,S/8]`` (``e4t_mask_prep`` on the copy stream, right behind ``e4t_image_prep``,
+    from the same plan table: the mask sees its image's resize, crop and flip).
 
     shuffle=True reshuffles every epoch with `seed` (all ranks draw the same permutation; rank r takes batches
     r, r+world, ...; the incomplete last batch is dropped).  num_workers = decode threads (0 -> decode inline in the
@@ -301,6 +370,7 @@ class DeviceLoader:
         self.shuffle, self.rank, self.world, self.seed = shuffle, rank, world, seed
         self.device = torch.device(device)
         self.size = dataset.processor.size
+        self.masks = getattr(dataset, "masks", None) is not None
         self.prefetch = max(1, int(prefetch))
         self.pool = ThreadPoolExecutor(num_workers) if num_workers > 0 else None
         # one batch with the consumer + `prefetch` queued + one being produced
@@ -349,25 +419,31 @@ class DeviceLoader:
         for k in range(len(samples)):               # stream sources: an undecodable image is replaced by the next item
             while samples[k] is None:
                 samples[k] = self._load(next(self._items), plans_rng[k])
-        nbytes = sum((s["image"].size + 15) // 16 * 16 for s in samples)
+        nbytes = packed_nbytes(samples)
         with ops.capture_lock:       # (host decode above ran unlocked) no allocation / copy / event wait while a HIP graph is being captured
             return self._upload(slot, samples, nbytes)
 
     def _upload(self, slot, samples, nbytes):
         if slot.event is not None:
             slot.event.synchronize()                     # the consumer's step that used this slot's output has been enqueued and finished
-        slot.ensure(nbytes, self.B, self.size)
-        _, _, total = pack_batch(samples, self.size, slot.h_pool, slot.h_table)
+        slot.ensure(nbytes, self.B, self.size, self.masks)
+        _, _, total, _ = pack_samples(samples, self.size, slot.h_pool, slot.h_table, slot.h_moff)
         be = ops.backend()
         if self.copy_stream is None:
             slot.d_pool[:total].copy_(slot.h_pool[:total])
             slot.d_table.copy_(slot.h_table)
             slot.out = be.image_prep(slot.d_pool, slot.d_table, self.B, self.size, out=slot.out)
+            if self.masks:
+                slot.d_moff.copy_(slot.h_moff)
+                slot.out_mask = be.mask_prep(slot.d_pool, slot.d_table, slot.d_moff, self.B, self.size, out=slot.out_mask)
             return None
         with torch.cuda.stream(self.copy_stream):
             slot.d_pool[:total].copy_(slot.h_pool[:total], non_blocking=True)
             slot.d_table.copy_(slot.h_table, non_blocking=True)
             slot.out = be.image_prep(slot.d_pool, slot.d_table, self.B, self.size, out=slot.out)
+            if self.masks:
+                slot.d_moff.copy_(slot.h_moff, non_blocking=True)
+                slot.out_mask = be.mask_prep(slot.d_pool, slot.d_table, slot.d_moff, self.B, self.size, out=slot.out_mask)
             ready = torch.cuda.Event()
             ready.record(self.copy_stream)
         return ready
@@ -407,7 +483,7 @@ class DeviceLoader:
                 if ready is not None:
                     cur = torch.cuda.current_stream(dev)
                     cur.wait_event(ready)
-                yield dict(pixel_values=slot.out)
+                yield dict(pixel_values=slot.out, loss_mask=slot.out_mask) if self.masks else dict(pixel_values=slot.out)
                 if ready is not None:
                     done = torch.cuda.Event()
                     done.record(torch.cuda.current_stream(dev))   # the slot may be rewritten once the consumer's work so far is done

@@ -627,6 +627,38 @@ def quick_gelu(x):
     return UnaryFn.apply(x, _C.OP_QGELU)
 
 
+class MaskedMSEFn(torch.autograd.Function):
+    """masked_mse on the backend's kernels: two launches forward, one backward, no host read"""
+
+    @staticmethod
+    def forward(ctx, pred, target, w):
+        loss, wd, stats = ops.backend().masked_mse(pred, target, w, save=ctx.needs_input_grad[0])
+        ctx.save_for_backward(wd, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        wd, stats = ctx.saved_tensors
+        return ops.backend().masked_mse_bwd(wd, stats, g.contiguous().float()), None, None
+
+
+def masked_mse(pred, target, w):
+    """Masked diffusion loss (the E4T paper's face-domain loss; the reference's open TODO, README.md:112-115, on the loss of
+    pretrain_e4t.py:645-647).  pred, target: [B, C, h, w]; w: [B, h, w] weights in [0, 1], broadcast over the channels:
+
+        loss = sum_{b,c,y,x} w (pred - target)^2 / den,   den = C * max(sum(w), 1)
+
+    so w == 1 is plain mean-squared error and w == 0 gives loss 0 and gradient 0.  Runs the backend's fused kernels when it has
+    them; the fp32 composition below is the executable specification (and what a backend without the op computes)."""
+    be = ops.backend()
+    if hasattr(be, "masked_mse"):
+        return MaskedMSEFn.apply(pred.float(), target.float(), w.float())
+    d = pred.float() - target.float()
+    w = w.float()
+    den = pred.shape[1] * torch.clamp(w.sum(), min=1.0)
+    return (w.unsqueeze(1) * d * d).sum() / den
+
+
 class SpatialMeanFn(torch.autograd.Function):
     """cat([m.mean(dim=(2,3)) for m in maps], -1) for NHWC maps given as [B*HW, C] matrices (encoder.py:147-148)."""
 

@@ -585,6 +585,41 @@ class HipBackend:
         _C.check(self.lib.e4t_image_prep(_ptr(pool), _ptr(table), _ptr(out), B, S, _stream()), "e4t_image_prep")
         return out
 
+    def mask_prep(self, pool, table, mask_off, B, S, out=None):
+        """single-channel uint8 masks packed in `pool` at byte offsets `mask_off` (int64 [B]) + the images' plan `table` (all on the
+        device) -> fp32 [B, S/8, S/8] loss weights in [0, 1]: the mask through its image's resize / crop / flip, averaged per latent pixel"""
+        assert pool.dtype == torch.uint8 and table.dtype == torch.int64 and table.shape == (B, 8) and table.is_contiguous()
+        assert mask_off.dtype == torch.int64 and mask_off.shape == (B,) and mask_off.is_contiguous() and S % 8 == 0
+        if out is None:
+            out = torch.empty((B, S // 8, S // 8), dtype=torch.float32, device=pool.device)
+        _C.check(self.lib.e4t_mask_prep(_ptr(pool), _ptr(table), _ptr(mask_off), _ptr(out), B, S, _stream()), "e4t_mask_prep")
+        return out
+
+    def masked_mse(self, pred, target, w, save=True):
+        """sum w (pred - target)^2 / (C max(sum w, 1)) for fp32 pred / target [B, C, h, w] and w [B, h, w] -> (loss (0-dim), wd, stats).
+        pred may be an NCHW view of NHWC storage (the native UNet's output) and is read in place; wd = w * (pred - target) in pred's
+        layout and stats (device {loss, den, workspace}) are what masked_mse_bwd needs; save=False skips wd."""
+        B, Cn = pred.shape[0], pred.shape[1]
+        HW = pred.numel() // (B * Cn)
+        assert pred.dtype == f32 and target.dtype == f32 and w.dtype == f32 and pred.dim() == 4
+        assert target.shape == pred.shape and w.numel() == B * HW
+        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
+        if not nhwc:
+            pred = pred.contiguous()
+        target, w = target.contiguous(), w.contiguous()
+        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
+        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
+        _C.check(self.lib.e4t_masked_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(wd), _ptr(stats), B, Cn, HW, int(nhwc), _stream()),
+                 "e4t_masked_mse_fwd")
+        return stats[0], wd, stats
+
+    def masked_mse_bwd(self, wd, stats, g):
+        """dpred = g * 2 * wd / den in wd's (= pred's) layout; g: device fp32 scalar (the upstream gradient)"""
+        assert g.dtype == f32 and g.numel() == 1 and wd.dtype == f32
+        dpred = torch.empty_like(wd)
+        _C.check(self.lib.e4t_masked_mse_bwd(_ptr(wd), _ptr(stats), _ptr(g), _ptr(dpred), wd.numel(), _stream()), "e4t_masked_mse_bwd")
+        return dpred
+
     def adamw(self, p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
         self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_adamw(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step,
                                                                       grad_scale, _stream()), "e4t_adamw"), 28.0 * p.numel())

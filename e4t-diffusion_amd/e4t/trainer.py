@@ -271,8 +271,11 @@ class E4TTrainer:
         s = (1 - self.acp[t]).sqrt().view(-1, 1, 1, 1)
         return a * x0 + s * noise
 
-    def losses(self, pixel_values, latents, noise, timesteps, input_ids, placeholder_idx):
-        """Forward half of the step (pretrain_e4t.py:616-647).  Returns (loss, loss_diff, loss_reg)."""
+    def losses(self, pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask=None):
+        """Forward half of the step (pretrain_e4t.py:616-647).  Returns (loss, loss_diff, loss_reg).
+        loss_mask (fp32 [B, h, w] on the latent grid, from DeviceLoader's ``loss_mask``): loss_diff becomes the masked mean-squared
+        error of functional.masked_mse (the reference's README.md:112-115).  Under data parallelism each rank normalises by the
+        sum(w) of ITS batch before the gradients are averaged, as each rank's plain mean is taken over its own batch."""
         B = latents.shape[0]
         te = self.text_encoder
         if self.text_trainable:
@@ -313,7 +316,10 @@ class E4TTrainer:
             a = self.acp[timesteps].sqrt().view(-1, 1, 1, 1)
             s = (1 - self.acp[timesteps]).sqrt().view(-1, 1, 1, 1)
             target = a * noise - s * latents
-        loss_diff = F.mse_loss(pred.float(), target.float(), reduction="mean")
+        if loss_mask is not None:
+            loss_diff = Fn.masked_mse(pred.float(), target.float(), loss_mask)
+        else:
+            loss_diff = F.mse_loss(pred.float(), target.float(), reduction="mean")
         loss_reg = self.reg_lambda * domain.pow(2).sum()
         return loss_diff + loss_reg, loss_diff, loss_reg
 
@@ -801,14 +807,15 @@ class E4TTrainer:
         ops.bump_weights_epoch()                 # bf16 compute copies of the trainable weights are stale now
 
     def train_step(self, pixel_values, input_ids, placeholder_idx, noise=None, timesteps=None, vae_eps=None, latents=None,
-                   sync=True, loss_scale=1.0):
+                   sync=True, loss_scale=1.0, loss_mask=None):
         """One training step (see _train_step); replayed from the step's HIP graph when enable_step_graph() is on and the call is a plain
-        synchronising step."""
+        synchronising step without a loss mask (a masked step always runs eagerly)."""
         def run():
             # (a replayed graph bakes in the first-write / factored treatment of the head's gradient stack: only from a clean gradient)
-            if self._step_graph_on and sync and loss_scale == 1.0 and self._next_px is None and not self._pref and not self._accum_pending:
+            if (self._step_graph_on and sync and loss_scale == 1.0 and self._next_px is None and not self._pref and not self._accum_pending
+                    and loss_mask is None):
                 return self._graphed_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents)
-            return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale)
+            return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale, loss_mask)
         ts = self._training_stream()
         if ts is None or self._step_graph_on:          # (a replayed graph's branches run on the graph executor's own streams, wherever it is launched)
             return run()
@@ -876,7 +883,7 @@ class E4TTrainer:
         return self._train_stream
 
     def _train_step(self, pixel_values, input_ids, placeholder_idx, noise=None, timesteps=None, vae_eps=None, latents=None,
-                    sync=True, loss_scale=1.0):
+                    sync=True, loss_scale=1.0, loss_mask=None):
         """Full step.  Random draws may be passed in (parity tests) or are sampled on the device.
         Gradient accumulation (``accelerator.accumulate``, pretrain_e4t.py:595): call with ``sync=False`` and
         ``loss_scale=1/k`` for the first k-1 micro-batches — gradients accumulate locally, no collective, no optimiser step —
@@ -897,7 +904,7 @@ class E4TTrainer:
             noise = torch.randn_like(latents)
         if timesteps is None:
             timesteps = torch.randint(0, self.acp.shape[0], (B,), device=dev).long()
-        loss, loss_diff, loss_reg = self.losses(pixel_values, latents, noise, timesteps, input_ids, placeholder_idx)
+        loss, loss_diff, loss_reg = self.losses(pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask)
         if self._next_px is not None:        # announced by prefetch(): the next batch's frozen encoders start with this backward
             self._start_prefetch()           # (starting them with the step instead: 101.95 vs 101.8 ms, profiles/r05_ab/r05b_at_step.json)
         self._armed = bool(sync)             # micro-batches that only accumulate start no collectives

@@ -304,6 +304,23 @@ int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist,
  * SmallestMaxSize dims), crop y0, crop x0 (in the resized image), flip}.  Byte-exact INTER_AREA (area / area-fast /
  * enlarging fixed-point branches); only the cropped window is computed. */
 int e4t_image_prep(const void* pool, const long long* table, float* out, int B, int S, e4t_stream stream);
+/* Loss mask for the masked diffusion loss (the reference's first open TODO, README.md:112-115; consumed at pretrain_e4t.py:645-647): the
+ * single-channel uint8 H x W mask of image b lies at pool + mask_off[b] (device int64 [B]) and goes through row b of the SAME plan table
+ * as its image (columns 1..7; column 0 is ignored): byte-exact SmallestMaxSize(INTER_AREA) -> crop -> flip, then
+ * out[b][i][j] = (float)((double)s / 16320.0) with s the integer sum of the 64 resized bytes of latent pixel (i, j)'s 8 x 8 block
+ * (16320 = 64 * 255).  The S x S mask is never written.  S % 8 == 0, B <= 65535. */
+int e4t_mask_prep(const void* pool, const long long* table, const long long* mask_off, float* out /* fp32 [B][S/8][S/8] */, int B, int S, e4t_stream stream);
+/* Masked mean-squared error replacing F.mse_loss at pretrain_e4t.py:645-647 when a loss mask is given (README.md:112-115): with d = pred - target
+ * and w fp32 [B][HW] broadcast over the C channels, den = C * max(sum(w), 1) and loss = sum w * d^2 / den; dpred = g * 2 * w * d / den.
+ * pred is [B][C][HW], or [B][HW][C] when pred_nhwc (the UNet's native output, as in e4t_guided_step); target is [B][C][HW]; wd (may be
+ * NULL when no gradient is wanted) receives w * d and dpred the gradient, both in pred's layout (n = B*C*HW elements).  stats: DEVICE
+ * float[E4T_MASKED_MSE_STATS]; the forward leaves {loss, den} in stats[0..1] (the rest is its reduction workspace) and the backward
+ * reads den from it and the upstream gradient scalar g from device memory: nothing is read on the host.  Two-stage reductions in a fixed
+ * order, no atomics: bitwise reproducible.  Forward = 2 launches, backward = 1; w == 0 everywhere gives loss 0 and dpred 0. */
+#define E4T_MASKED_MSE_STATS 2050
+int e4t_masked_mse_fwd(const float* pred, const float* target, const float* w, float* wd, float* stats, int B, int C, int HW, int pred_nhwc,
+                       e4t_stream stream);
+int e4t_masked_mse_bwd(const float* wd, const float* stats, const float* g, float* dpred, long long n, e4t_stream stream);
 /* in-place row softmax of a bf16 matrix [rows][ld] over the first L columns (fp32 math); L % 8 == 0, L <= 16384 */
 int e4t_softmax_rows(void* x, long long rows, int L, int ld, e4t_stream stream);
 /* 3x3/pad-1 im2col of a 3-channel NCHW fp32 image -> bf16 [B*H*W][32], column (ky*3+kx)*3+c, columns 27..31 zero */

@@ -74,7 +74,12 @@ def parse_args():
     p.add_argument("--synthetic_data", action="store_true", help="device-resident random images (benchmarking, CI); prompts still come from the templates")
     p.add_argument("--per_rank_seed", action="store_true", help="seed + rank for the step's random draws (the reference seeds every rank alike, :230-231)")
     p.add_argument("--unet_variant", type=str, default="sd14", choices=["sd14", "sd21"])
+    p.add_argument("--train_mask_dataset", type=str, default=None, metavar="DIR[::DIR]",
+                   help="loss masks for the masked diffusion loss: one directory per --train_image_dataset directory, in the same order, "
+                        "holding <rel>/<stem>.png (or an image extension) for every image <rel>/<stem>.<ext>")
     args = p.parse_args()
+    if args.train_mask_dataset and (args.webdataset or args.iterable_dataset or args.synthetic_data):
+        p.error("--train_mask_dataset needs image directories: it cannot be combined with --webdataset, --iterable_dataset or --synthetic_data")
     if args.use_8bit_adam:
         p.error("--use_8bit_adam (bitsandbytes) is CUDA-only and not part of the MI355X path; the fused fp32 AdamW kernel is used")
     if args.mixed_precision == "fp16":
@@ -107,7 +112,7 @@ def image_batches(args, dev, rank, world, prompts):
         print(f"Loading webdataset with {nshards} shards. (num_samples: {n})")
         ds = TarShardDataset(args.train_image_dataset, resolution=args.resolution)
     else:
-        ds = E4TDataset(args.train_image_dataset, resolution=args.resolution)
+        ds = E4TDataset(args.train_image_dataset, resolution=args.resolution, mask_dataset=args.train_mask_dataset)
     loader = DeviceLoader(ds, args.train_batch_size, shuffle=True, num_workers=args.dataloader_num_workers, device=dev,
                           rank=rank, world=world, seed=args.seed or 0)
     if not args.webdataset and len(loader) == 0:
@@ -115,7 +120,13 @@ def image_batches(args, dev, rank, world, prompts):
     while True:
         for batch in loader:
             ids, pidx = prompts(args.train_batch_size)
-            yield batch["pixel_values"], ids, pidx
+            if "loss_mask" in batch:            # --train_mask_dataset: a fourth element
+                # a copy (B x S/8 x S/8 floats): the loop draws the next batch before this one's step runs, which releases the
+                # loader's buffers to its producer, and the mask is read only at the end of that step (the pixels are consumed
+                # ahead of it, by E4TTrainer.prefetch)
+                yield batch["pixel_values"], ids, pidx, batch["loss_mask"].clone()
+            else:
+                yield batch["pixel_values"], ids, pidx
 
 
 def setup(args, dev, world=1, rank=0):
@@ -279,7 +290,7 @@ def main():
         pending = next(data) if global_step < args.max_train_steps else None
         if pending is not None:
             tr.prefetch(pending[0])
-        loss, ld, lr_ = tr.train_step(*batch, sync=sync, loss_scale=1.0 / ga)
+        loss, ld, lr_ = tr.train_step(*batch[:3], sync=sync, loss_scale=1.0 / ga, loss_mask=batch[3] if len(batch) > 3 else None)
         if sync:
             for _ in range(world):
                 sched.step()

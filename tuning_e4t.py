@@ -54,7 +54,11 @@ def parse_args():
     p.add_argument("--local_rank", type=int, default=-1)
     p.add_argument("--synthetic_data", action="store_true")
     p.add_argument("--unet_variant", type=str, default="sd14", choices=["sd14", "sd21"])
+    p.add_argument("--train_mask_path", type=str, default=None, metavar="FILE",
+                   help="loss mask of --train_image_path (grey image of the same size): the diffusion loss is weighted by it")
     a = p.parse_args()
+    if a.train_mask_path and not a.train_image_path:
+        p.error("--train_mask_path needs --train_image_path")
     if a.use_8bit_adam:
         p.error("--use_8bit_adam (bitsandbytes) is CUDA-only; the fused fp32 AdamW kernel is used")
     if a.gradient_accumulation_steps < 1:
@@ -112,6 +116,48 @@ def setup(args, dev):
                 placeholder_token_id=placeholder_token_id, class_token_id=class_token_id, empty_ids=empty_ids, prompt_templates=prompt_templates)
 
 
+def training_image(args, dev, g):
+    """The one training image, and its loss mask with --train_mask_path, as the loop consumes them: (pixels fp32 [B,3,S,S],
+    loss_mask fp32 [B,S/8,S/8] or None, the PIL image and the PIL mask that a checkpoint keeps as domain.png / domain_mask.png)."""
+    B, res = args.train_batch_size, args.resolution
+    pil_image = pil_mask = loss_mask = None
+    if args.synthetic_data and not args.train_image_path:
+        image = torch.rand((1, 3, res, res), generator=g, device=dev) * 2 - 1
+    elif args.train_image_path:
+        # tuning_e4t.py:174-181: make_transforms(resolution, random_crop=True) on the one training image; decode on the host,
+        # SmallestMaxSize(INTER_AREA) / crop / flip / normalise in the data-path kernel
+        import random
+
+        import numpy as np
+        from PIL import Image
+        from e4t import ops
+        from e4t.data import make_transforms, pack_samples
+        pil_image = Image.open(args.train_image_path).convert("RGB")
+        rgb = np.ascontiguousarray(np.asarray(pil_image, dtype=np.uint8))
+        plan = make_transforms(res, random_crop=True).plan(rgb.shape[0], rgb.shape[1], random.Random(args.seed))
+        sample = dict(image=rgb, plan=plan)
+        if args.train_mask_path:
+            pil_mask = Image.open(args.train_mask_path).convert("L")
+            sample["mask"] = np.ascontiguousarray(np.asarray(pil_mask, dtype=np.uint8))
+            if sample["mask"].shape != rgb.shape[:2]:
+                raise SystemExit(f"--train_mask_path is {sample['mask'].shape}, the image {rgb.shape[:2]}")
+        pool, table, _, mask_off = pack_samples([sample], res)
+        pool, table = pool.to(dev), table.to(dev)
+        image = ops.backend().image_prep(pool, table, 1, res)
+        if mask_off is not None:                     # the mask goes through the image's own plan (resize, crop, flip)
+            loss_mask = ops.backend().mask_prep(pool, table, mask_off.to(dev), 1, res).expand(B, -1, -1).contiguous()
+    else:
+        raise SystemExit("give --train_image_path <file> or --synthetic_data")
+    return image.expand(B, -1, -1, -1).contiguous(), loss_mask, pil_image, pil_mask           # tuning_e4t.py:266
+
+
+def save_domain_images(d, pil_image, pil_mask):
+    if pil_image is not None:
+        pil_image.save(os.path.join(d, "domain.png"))
+    if pil_mask is not None:
+        pil_mask.save(os.path.join(d, "domain_mask.png"))
+
+
 def main():
     args = parse_args()
     torch.cuda.set_device(0)
@@ -125,26 +171,7 @@ def main():
     ga = args.gradient_accumulation_steps
     B, res = args.train_batch_size, args.resolution
     g = torch.Generator(device=dev).manual_seed(args.seed or 0)
-    pil_image_to_save = None
-    if args.synthetic_data and not args.train_image_path:
-        image = torch.rand((1, 3, res, res), generator=g, device=dev) * 2 - 1
-    elif args.train_image_path:
-        # tuning_e4t.py:174-181: make_transforms(resolution, random_crop=True) on the one training image; decode on the host,
-        # SmallestMaxSize(INTER_AREA) / crop / flip / normalise in the data-path kernel
-        import random
-
-        import numpy as np
-        from PIL import Image
-        from e4t import ops
-        from e4t.data import make_transforms, pack_batch
-        pil_image_to_save = Image.open(args.train_image_path).convert("RGB")
-        rgb = np.ascontiguousarray(np.asarray(pil_image_to_save, dtype=np.uint8))
-        plan = make_transforms(res, random_crop=True).plan(rgb.shape[0], rgb.shape[1], random.Random(args.seed))
-        pool, table, _ = pack_batch([dict(image=rgb, plan=plan)], res)
-        image = ops.backend().image_prep(pool.to(dev), table.to(dev), 1, res)
-    else:
-        raise SystemExit("give --train_image_path <file> or --synthetic_data")
-    pixels = image.expand(B, -1, -1, -1).contiguous()                       # tuning_e4t.py:266
+    pixels, loss_mask, pil_image_to_save, pil_mask_to_save = training_image(args, dev, g)
     latents = tr.encode_latents(pixels, torch.randn((B, 4, res // 8, res // 8), generator=g, device=dev))   # once, :268-269
     sched = LRSchedule(args.lr_scheduler, lr, args.lr_warmup_steps * ga, args.max_train_steps * ga)
 
@@ -155,8 +182,7 @@ def main():
         if args.train_text_encoder:
             torch.save(text.state_dict(), os.path.join(d, "text_encoder.pt"))
         save_config(dict(vars(args), pretrained_args=dict(st["pretrained_args"])), d)
-        if pil_image_to_save is not None:
-            pil_image_to_save.save(os.path.join(d, "domain.png"))
+        save_domain_images(d, pil_image_to_save, pil_mask_to_save)
         print(f"[*] Weights saved at {d}")
 
     # the reference counts iterations (micro-batches) here too: tuning_e4t.py:270,341-343
@@ -166,7 +192,7 @@ def main():
         if (global_step - 1) % ga == 0:
             sched.apply(tr)
         ids, pidx = st["prompts"](B)
-        loss, ld, lr_ = tr.train_step(pixels, ids, pidx, latents=latents, sync=sync, loss_scale=1.0 / ga)
+        loss, ld, lr_ = tr.train_step(pixels, ids, pidx, latents=latents, sync=sync, loss_scale=1.0 / ga, loss_mask=loss_mask)
         if sync:
             sched.step()
         torch.cuda.synchronize()
