@@ -43,6 +43,11 @@ class GemmPlan(C.Structure):
     _fields_ = [("tile", i32), ("tile_m", i32), ("tile_n", i32), ("splitk", i32), ("workspace_bytes", sz), ("tail_rows", i32), ("stages", i32)]
 
 
+class AttentionPlan(C.Structure):
+    """e4t_attention_plan_t: the kernels the attention launchers choose for a shape, as the launch log spells them"""
+    _fields_ = [("fwd", C.c_char_p), ("dq", C.c_char_p), ("dkv", C.c_char_p), ("tsplit", i32), ("tchunk", i32), ("dkv_occ", i32), ("workspace_floats", sz)]
+
+
 class WODesc(C.Structure):
     _fields_ = (
         [(n, vp) for n in ("v", "w1", "b1", "w2", "b2", "wc", "bc", "wr", "br", "W", "vecs", "partial", "weff", "weffT", "dweff")]
@@ -69,6 +74,7 @@ SIGNATURES = {
     "e4t_attention_bwd": (i32, [vp] * 10 + [i32] * 9 + [i64] * 4 + [f32, i32, vp]),
     "e4t_attention_bwd_workspace_floats": (sz, [i32] * 5),
     "e4t_attention_bwd_ws": (i32, [vp] * 7 + [sz] + [vp] * 3 + [i32] * 9 + [i64] * 4 + [f32, i32, vp]),
+    "e4t_attention_plan": (i32, [i32] * 6 + [sz, C.POINTER(AttentionPlan)]),
     "e4t_groupnorm_num_chunks": (i32, [i32, i32]),
     "e4t_groupnorm_workspace_bytes": (sz, [i32, i32, i32, i32, i32]),
     "e4t_groupnorm_stats": (i32, [vp, i32, vp, i32, i32, i32, i32, f32, vp, vp, sz, vp]),

@@ -179,6 +179,20 @@ int e4t_attention_bwd_ws(const void* Q, const void* K, const void* V, const void
                          float* ws, size_t ws_floats, void* dQ, void* dK, void* dV, int B, int H, int T, int S, int DH, int ldq,
                          int ldk, int ldv, int ldo, long long bq, long long bk, long long bv, long long bo, float scale,
                          int causal, e4t_stream stream);
+/* What the attention launchers decide for a shape (pure host code, no device is touched; tests/test_gemm_dispatch.py holds it against a
+ * record): the kernel symbols of e4t_attention_fwd and of e4t_attention_bwd_ws with a workspace of ws_floats, spelled as the launch log and
+ * a kernel trace spell them (static strings), the query chunks of the dK/dV kernel (tsplit > 1: fp32 partials, summed by
+ * attn_dkv_reduce_kernel behind it; tchunk queries each), the workgroups per CU the chosen dK/dV instantiation is bounded for, and
+ * workspace_floats = e4t_attention_bwd_workspace_floats(B, H, T, S, DH).  A ws_floats too small for the part behind Delta gives the plan of
+ * the fallback (one query chunk; no {L, Delta} pairs, hence no LDS-DMA dK/dV kernel). */
+typedef struct {
+  const char* fwd;
+  const char* dq;
+  const char* dkv;
+  int tsplit, tchunk, dkv_occ;
+  size_t workspace_floats;
+} e4t_attention_plan_t;
+int e4t_attention_plan(int B, int H, int T, int S, int DH, int causal, size_t ws_floats, e4t_attention_plan_t* out);
 
 /* ---------------------------------------------------------------- norms (norm.hip) ----------- */
 /* GroupNorm over NHWC input given as up to two channel-sources (x1: C1 ch, x2: C2 ch or NULL) —

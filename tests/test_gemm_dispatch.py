@@ -6,7 +6,11 @@ shapes in clear text.  Corpus and record come from tools/gemm_dispatch_dump.py; 
     python tools/gemm_dispatch_dump.py --record
 
 rewrites the record (on a machine without a GPU: it anchors the step shapes through the launch log).  Only the plan entry points are
-called here — pure host code, safe on any machine; the launch half of the tool is never part of a test."""
+called here — pure host code, safe on any machine; the launch half of the tool is never part of a test.
+
+The attention launchers (csrc/attention.hip: plan_fwd / plan_bwd, exported as e4t_attention_plan) are held to the same record: group `attn` hashes
+`shape ws -> forward | dQ | dK/dV kernel | tsplit tchunk | workspace_floats` over both sides of every dispatch threshold and four workspace sizes,
+and the step's attention shapes stand in clear text.  A slipped threshold passes every numeric check and only costs time; here it fails."""
 import ctypes as C
 import importlib.util
 import os
@@ -28,14 +32,16 @@ def _cu_count():
 
 
 def _record():
-    groups, step = {}, []
+    groups, step, attn = {}, [], []
     for line in open(dump.RECORD):
         if line.startswith("group "):
             g, n, hx = (s.strip() for s in line[len("group "):].split("|"))
             groups[g] = (int(n), hx)
         elif line.startswith("step "):
             step.append(line[len("step "):].rstrip("\n"))
-    return groups, step
+        elif line.startswith("attn "):
+            attn.append(line.rstrip("\n"))
+    return groups, step, attn
 
 
 @pytest.fixture(scope="module")
@@ -58,16 +64,17 @@ def _checked_groups(groups):
 
 
 def test_record_covers_the_corpus():
-    groups, step = _record()
-    want = {"%s t%d" % (k, t) for k in ("gemm", "conv") for t in dump.HINTS} | {"tn"}
+    groups, step, attn = _record()
+    want = {"%s t%d" % (k, t) for k in ("gemm", "conv") for t in dump.HINTS} | {"tn", "attn"}
     assert set(groups) == want
+    assert [a.split(" -> ")[0] for a in attn] == ["attn " + dump.describe(dict(zip(("B", "H", "T", "S", "DH", "causal"), sh), ws="full")) for sh in dump.attn_step_shapes()]
     rows = dump.step_rows()
     assert len(step) == len(rows) == 167 and sum(1 for s, _ in rows if not s.startswith("splitk_reduce")) == 153
     assert [s.split(" | ")[0] for s in step] == ["%s|%s" % r for r in rows]      # every recorded launch of the step table, in its order
 
 
 def test_plans_match_the_record(dumper):
-    groups, _ = _record()
+    groups, _, _ = _record()
     checked = _checked_groups(groups)
     got, _ = dump.plan_digests(dumper, only_groups=set(checked))
     bad = [g for g in checked if got.get(g) != groups[g]]
@@ -77,10 +84,70 @@ def test_plans_match_the_record(dumper):
 
 def test_step_shapes_get_the_recorded_plans(dumper):
     """the step's 153 GEMM / conv / TN launches (and the 14 split-K reduces behind them), descriptor and plan in clear text"""
-    _, step = _record()
+    _, step, _ = _record()
     for line in step:
         sym_shape, rest = line.split(" | ", 1)
         desc, plan = rest.split(" -> ")
         kind, *kv = desc.split(" ")
         item = dump.Item("step", kind, {k: int(v) for k, v in (s.split("=") for s in kv)})
         assert dumper.plan(item) == plan, (sym_shape, desc)
+
+
+def test_step_attention_shapes_get_the_recorded_kernels(dumper):
+    """every attention shape of the step: the three kernels, the query split and the workspace in clear text; and every attention kernel the step
+    table (profiles/r06_roofline_per_shape.csv) saw on hardware for a shape is one of the three the plan names for it"""
+    _, _, attn = _record()
+    assert len(attn) == 11
+    for line, (shape, seen) in zip(attn, dump.attn_step_shapes().items()):
+        desc, plan = line.split(" -> ")
+        kw = dict(s.split("=") for s in desc.split(" ")[1:])
+        kw = {k: v if k == "ws" else int(v) for k, v in kw.items()}
+        assert tuple(kw[k] for k in ("B", "H", "T", "S", "DH", "causal")) == shape
+        assert dumper.attn_plan(kw) == plan, desc
+        assert set(seen) <= set(plan.split(" | ")[:3]), (desc, seen)
+    by_shape = {a.split(" ws=")[0]: a.split(" -> ")[1].split(" | ") for a in attn}
+    assert by_shape["attn B=16 H=8 T=4096 S=4096 DH=40 causal=0"][:4] == ["attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>", "1 4096"]
+    assert by_shape["attn B=16 H=8 T=4096 S=77 DH=40 causal=0"][:4] == ["attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "8 512"]
+
+
+# (B, H, T, S, DH[, causal]) of tests/kernel_checks.py::check_attention -> the kernels the launch log named for it, with the workspace the library asks
+# for, at the last commit before e4t_attention_plan (b388eee): which kernels the GPU suite exercises.  Not reached by any of them:
+# attn_bwd_dkv_kernel<32 | 40, 3> (S >= 2048 with T < 192, causal, or a split query range), attn_bwd_dq_dma_kernel<32>.
+CHECK_ATTENTION_KERNELS = {
+    (2, 2, 64, 64, 32): ("attn_fwd_kernel<32>", "attn_bwd_dq_kernel<32>", "attn_bwd_dkv_kernel<32, 2>"),
+    (2, 3, 200, 200, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (1, 2, 128, 77, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (2, 2, 96, 77, 80): ("attn_fwd_kernel<80>", "attn_bwd_dq_kernel<80>", "attn_bwd_dkv_kernel<80, 1>"),
+    (1, 2, 64, 64, 160): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>"),
+    (1, 2, 257, 257, 80): ("attn_fwd_kernel<80>", "attn_bwd_dq_kernel<80>", "attn_bwd_dkv_kernel<80, 1>"),
+    (2, 2, 130, 33, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),
+    (1, 8, 1024, 1024, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (3, 5, 300, 300, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (2, 8, 4096, 4096, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (1, 2, 300, 2100, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (1, 1, 2050, 2050, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_dma_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),
+    (3, 12, 77, 77, 64, True): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),
+    (2, 3, 200, 200, 40, True): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (1, 2, 128, 128, 80, True): ("attn_fwd_kernel<80>", "attn_bwd_dq_kernel<80>", "attn_bwd_dkv_kernel<80, 1>"),
+    (2, 8, 4096, 77, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (1, 2, 1000, 77, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (2, 2, 1024, 77, 80): ("attn_fwd_kernel<80>", "attn_bwd_dq_kernel<80>", "attn_bwd_dkv_kernel<80, 1>"),
+    (1, 2, 600, 33, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),
+    (1, 4, 1024, 1024, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (1, 2, 520, 520, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (2, 3, 700, 545, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (1, 1, 40, 512, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),
+    (2, 2, 256, 640, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (4, 8, 600, 2000, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (2, 16, 1100, 2090, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (16, 8, 4096, 4096, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),      # the bitwise determinism check
+    (4, 8, 4096, 4096, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),       # ... and its four batch chunks
+    (1, 1, 64, 160, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),                 # peaked scores (forward only)
+    (1, 1, 96, 840, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),           # ... on the long-key forward
+}
+
+
+def test_check_attention_shapes_keep_their_kernels(dumper):
+    for case, kernels in CHECK_ATTENTION_KERNELS.items():
+        kw = dict(zip(("B", "H", "T", "S", "DH"), case[:5]), causal=int(len(case) > 5), ws="full")
+        assert tuple(dumper.attn_plan(kw).split(" | ")[:3]) == kernels, case

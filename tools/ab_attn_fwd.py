@@ -1,5 +1,7 @@
 """Forward attention of the step's dominant shape only (B16 H8 T = S = 4096 dh 40), graph-replayed, for timing variants
-(E4T_LIB=<variant .so>; ATTN64_PROBE builds give wrong results by design).   python tools/ab_attn_fwd.py [label]"""
+(E4T_LIB=<variant .so>).   python tools/ab_attn_fwd.py [label]
+The knock-out builds this was written for (wrong results by design) were last available at b388eee; their results live in
+profiles/r03_probe_attn_variants.txt, profiles/r06_ab/attention_fwd64.txt and DESIGN 2.2."""
 import os
 import sys
 

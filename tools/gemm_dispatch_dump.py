@@ -1,23 +1,28 @@
 #!/usr/bin/env python
-"""What the GEMM / 3x3-conv host code decides for a fixed corpus of descriptors, one line per descriptor:
+"""What the GEMM / 3x3-conv and the attention host code decide for a fixed corpus of descriptors, one line per descriptor:
 
     <kind> <descriptor> -> <tile tile_m tile_n splitk workspace_bytes tail_rows stages> [| rc <rc> <error text> | <launch-log lines>]
+    attn <shape> ws=<workspace offered> -> <forward kernel | dQ kernel | dK/dV kernel | tsplit tchunk | workspace_floats> [| rc ... | ...]
 
 Two builds of the library (E4T_LIB=<path to libe4t_hip.so> selects another one) decide alike iff their dumps are byte-identical:
 
     python tools/gemm_dispatch_dump.py > new.txt;  E4T_LIB=/path/to/old/libe4t_hip.so python tools/gemm_dispatch_dump.py > old.txt;  diff old.txt new.txt
 
-The plan half (e4t_gemm_plan / e4t_conv3x3_plan / e4t_gemm_tn_plan) is pure host code.  The launch half calls e4t_gemm_nt / e4t_conv3x3 /
-e4t_gemm_tn with FAKE operand pointers and the launch log on: the library writes the symbol | shape | bytes | flops line(s) of what it
+The plan half (e4t_gemm_plan / e4t_conv3x3_plan / e4t_gemm_tn_plan / e4t_attention_plan) is pure host code.  The launch half calls e4t_gemm_nt /
+e4t_conv3x3 / e4t_gemm_tn / e4t_attention_fwd + e4t_attention_bwd_ws with FAKE operand pointers and the launch log on: the library writes the symbol | shape | bytes | flops line(s) of what it
 would launch and then fails with "no ROCm-capable device".  That only works — and is only safe — on a machine WITHOUT a GPU: where a
 device answers, the tool prints the plan half only and says so.  Environment switches of the library (E4T_GEMM_REGSTAGE,
 E4T_CONV_NOSTRIP, ...) are read once per process: one run per setting.
 
     --plans            plan half only
-    --group 'gemm t160'  only that corpus group (a group = one tile hint x {gemm, conv}, 'tn', or 'step')
+    --group 'gemm t160'  only that corpus group (a group = one tile hint x {gemm, conv}, 'tn', 'attn', or 'step')
     --anchor           check the 'step' group against profiles/r06_roofline_per_shape.csv: every GEMM / conv / TN launch recorded there
                        on hardware is reproduced (symbol and shape string), every split-K reduce row by a launch's second log line
     --record           rewrite tests/gemm_dispatch_record.txt (what tests/test_gemm_dispatch.py compares against) from this library
+    --attn-launches    the 'attn' group as the launch log alone tells it (kernel symbols; workspace floats from
+                       e4t_attention_bwd_workspace_floats): needs no e4t_attention_plan, so E4T_LIB may be a library older than that entry point
+    --attn-check FILE  hold such a dump against e4t_attention_plan of this library; prints every row that differs (the record's 'attn' group
+                       was anchored this way to the last commit before the plan existed)
 """
 import argparse
 import collections
@@ -130,6 +135,35 @@ def corpus():
                                                  (dict(flags=0), dict(flags=OUT_F32), dict(flags=ACCUM | OUT_F32), dict(flags=RES_F32, residual=1)),
                                                  ("big", "none", "small")):
         yield Item("tn", "tn", dict(M=M, N=N, K=K, splitk=sk, ws=ws, **fl))
+    yield from attn_corpus()
+
+
+ATTN_WS = ("full", "delta", "delta3", "short")      # the size the library asks for | B*H*T (Delta only) | B*H*T + 3 | one float short of the first
+
+
+def attn_items(shapes):
+    for B, H, T, S, DH, causal in shapes:
+        for ws in ATTN_WS:
+            yield Item("attn", "attn", dict(B=B, H=H, T=T, S=S, DH=DH, causal=causal, ws=ws))
+
+
+def attn_step_shapes():
+    """(B, H, T, S, DH, causal) of the attention launches profiles/r06_roofline_per_shape.csv recorded, and the kernel symbols seen for each"""
+    seen = collections.OrderedDict()
+    for l in open(STEP_CSV):
+        m = re.match(r"(attn_\w+<(\d+)[^>]*>),B(\d+) H(\d+) T(\d+) S(\d+) causal(\d),", l)
+        if m:
+            B, H, T, S, c = map(int, m.groups()[2:])
+            seen.setdefault((B, H, T, S, int(m.group(2)), c), []).append(m.group(1))
+    return seen
+
+
+def attn_corpus():
+    """both sides of every threshold of the attention dispatch (S 192 / 512 / 2048, T 192 / 512, fewer than 512 dK/dV workgroups), each with the
+    four workspace sizes; two rows around T * 8 = 2^31 (the DMA-staged dK/dV kernel's 32-bit extent of the {L, Delta} pairs)"""
+    sizes = (1, 33, 77, 191, 192, 193, 255, 256, 257, 511, 512, 513, 1024, 2047, 2048, 2050, 4096, 9216)
+    shapes = [(B, H, T, S, DH, c) for DH, c, (B, H), T, S in itertools.product((32, 40, 64, 80, 160), (0, 1), ((1, 1), (2, 8), (4, 5), (16, 8)), sizes, sizes)]
+    return attn_items(shapes + [(16, 8, (1 << 28) - 1, 512, 40, 0), (16, 8, 1 << 28, 512, 40, 0)])
 
 
 def describe(kw):
@@ -154,9 +188,21 @@ def make_desc(item):
     return _C.GemmDesc(**base)
 
 
+def load_lib():
+    """the library through e4t._C; a build from before e4t_attention_plan (E4T_LIB, for --attn-launches) through plain ctypes with the signatures it has"""
+    try:
+        return _C.load()
+    except AttributeError:
+        lib = C.CDLL(_C.LIB_PATH)
+        for name, (res, args) in _C.SIGNATURES.items():
+            if hasattr(lib, name):
+                getattr(lib, name).restype, getattr(lib, name).argtypes = res, args
+        return lib
+
+
 class Dumper:
     def __init__(self, launches):
-        self.lib = _C.load()
+        self.lib = load_lib()
         self.plan_fn = {"gemm": self.lib.e4t_gemm_plan, "conv": self.lib.e4t_conv3x3_plan, "tn": self.lib.e4t_gemm_tn_plan}
         self.launch_fn = {"gemm": self.lib.e4t_gemm_nt, "conv": self.lib.e4t_conv3x3, "tn": self.lib.e4t_gemm_tn}
         self.log = None
@@ -172,7 +218,31 @@ class Dumper:
             self.log.close()
             os.remove(self.log_path)
 
+    def attn_ws(self, kw):
+        shape = [kw[k] for k in ("B", "H", "T", "S", "DH")]
+        full, delta = self.lib.e4t_attention_bwd_workspace_floats(*shape), kw["B"] * kw["H"] * kw["T"]
+        return shape, {"full": full, "delta": delta, "delta3": delta + 3, "short": full - 1}[kw["ws"]]
+
+    def attn_plan(self, kw):
+        shape, ws = self.attn_ws(kw)
+        pl = _C.AttentionPlan()
+        rc = self.lib.e4t_attention_plan(*shape, kw["causal"], ws, C.byref(pl))
+        if rc != 0:
+            return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
+        return "%s | %s | %s | %d %d | %d" % (pl.fwd.decode(), pl.dq.decode(), pl.dkv.decode(), pl.tsplit, pl.tchunk, pl.workspace_floats)
+
+    def attn_launch(self, kw):
+        """(rc of the backward, its error text, the log lines of forward + backward); dense q | k | v rows"""
+        (B, H, T, S, DH), ws = self.attn_ws(kw)
+        ld = H * DH
+        tail = [B, H, T, S, DH, ld, ld, ld, ld, T * ld, S * ld, S * ld, T * ld, C.c_float(DH ** -0.5), kw["causal"], None]
+        self.lib.e4t_attention_fwd(FAKE, FAKE, FAKE, FAKE, FAKE, *tail)
+        rc = self.lib.e4t_attention_bwd_ws(*[FAKE] * 7, ws, FAKE, FAKE, FAKE, *tail)
+        return rc, (self.lib.e4t_last_error().decode() if rc < 0 else ""), self.log.read().splitlines()
+
     def plan(self, item, d=None):
+        if item.kind == "attn":
+            return self.attn_plan(item.kw)
         d = d or make_desc(item)
         pl = _C.GemmPlan()
         rc = self.plan_fn[item.kind](C.byref(d), C.byref(pl))
@@ -182,12 +252,14 @@ class Dumper:
 
     def launch(self, item, d=None):
         """(rc, error text, [log lines])"""
+        if item.kind == "attn":
+            return self.attn_launch(item.kw)
         d = d or make_desc(item)
         rc = self.launch_fn[item.kind](C.byref(d), None)
         return rc, (self.lib.e4t_last_error().decode() if rc < 0 else ""), self.log.read().splitlines()
 
     def line(self, item):
-        d = make_desc(item)
+        d = None if item.kind == "attn" else make_desc(item)
         s = "%s %s -> %s" % (item.kind, describe(item.kw), self.plan(item, d))
         if self.log:
             rc, err, lines = self.launch(item, d)
@@ -235,6 +307,33 @@ def anchor(dumper):
     return matched, miss
 
 
+def attn_launch_lines(dumper):
+    """the 'attn' group as the launch log tells it: descriptor -> forward | dQ | dK/dV symbol | the workspace floats the library asks for"""
+    for item in attn_corpus():
+        _, _, lines = dumper.attn_launch(item.kw)
+        full = dumper.lib.e4t_attention_bwd_workspace_floats(*[item.kw[k] for k in ("B", "H", "T", "S", "DH")])
+        yield "attn %s -> %s | %d" % (describe(item.kw), " | ".join(l.split("|")[0] for l in lines), full)
+
+
+def attn_check(dumper, path):
+    """rows of an --attn-launches dump that e4t_attention_plan of this library does not reproduce: the three symbols, the workspace floats and, where
+    the full workspace is offered, a tsplit that explains them (total = Delta + 4 + tsplit * B * H * 2 * S * DH, or 3 * Delta + 4 un-split)"""
+    want = dict(l.rstrip("\n").split(" -> ") for l in open(path) if l.startswith("attn "))
+    bad = 0
+    for item in attn_corpus():
+        desc, kw = "attn " + describe(item.kw), item.kw
+        fwd, dq, dkv, split, total = dumper.attn_plan(kw).split(" | ")
+        tsplit, delta, per = int(split.split()[0]), kw["B"] * kw["H"] * kw["T"], kw["B"] * kw["H"] * 2 * kw["S"] * kw["DH"]
+        fits = {1} if int(total) == 3 * delta + 4 else set()
+        if (int(total) - delta - 4) % per == 0 and (int(total) - delta - 4) // per > 1:
+            fits.add((int(total) - delta - 4) // per)
+        if want.get(desc) != " | ".join((fwd, dq, dkv, total)) or (kw["ws"] == "full" and tsplit not in fits):
+            bad += 1
+            print("DIFF %s: launch log %s, plan %s" % (desc, want.get(desc), dumper.attn_plan(kw)))
+    print("attn: %d rows, %d differ" % (len(want), bad))
+    return bad
+
+
 def write_record(dumper, path):
     if not dumper.log:      # (before the file is opened: a refused --record leaves the committed record as it is)
         sys.exit("--record needs the launch half (a machine without a GPU) to anchor the step shapes")
@@ -242,6 +341,10 @@ def write_record(dumper, path):
     matched, miss = anchor(dumper)
     if miss:
         sys.exit("--record: %d rows of the step table are not reproduced" % miss)
+    for shape, syms in attn_step_shapes().items():      # every attention kernel the step table saw for a shape is one the plan names
+        planned = dumper.attn_plan(dict(zip(("B", "H", "T", "S", "DH", "causal"), shape), ws="full")).split(" | ")[:3]
+        if not set(syms) <= set(planned):
+            sys.exit("--record: the step table has %s for attention %s, the plan %s" % (syms, shape, planned))
     with open(path, "w") as f:
         f.write("# What the DEFAULT build of the library plans for the corpus of tools/gemm_dispatch_dump.py (tests/test_gemm_dispatch.py).\n")
         f.write("# Regenerate after an intentional planner change: python tools/gemm_dispatch_dump.py --record\n")
@@ -251,6 +354,11 @@ def write_record(dumper, path):
         f.write("# the training step's shapes (profiles/r06_roofline_per_shape.csv), with the field combination that reproduces the recorded launch\n")
         for sym, shape, item in matched:
             f.write("step %s|%s | %s %s -> %s\n" % (sym, shape, item.kind, describe(item.kw), dumper.plan(item)))
+        f.write("# the step's attention shapes (same table): forward | dQ | dK/dV kernel | tsplit tchunk | workspace floats.  Group attn was first recorded\n")
+        f.write("# after --attn-check against the launch log of b388eee, the last commit before e4t_attention_plan, came out empty.\n")
+        for item in attn_items(attn_step_shapes()):
+            if item.kw["ws"] == "full":
+                f.write("%s %s -> %s\n" % (item.kind, describe(item.kw), dumper.plan(item)))
 
 
 def main():
@@ -259,8 +367,10 @@ def main():
     ap.add_argument("--group", action="append")
     ap.add_argument("--anchor", action="store_true")
     ap.add_argument("--record", action="store_true")
+    ap.add_argument("--attn-launches", action="store_true")
+    ap.add_argument("--attn-check", metavar="FILE")
     args = ap.parse_args()
-    lib = _C.load()
+    lib = load_lib()
     launches = not args.plans
     if launches and gpu_visible(lib):
         print("# a GPU is visible: the launch half would hand fake pointers to a real device — plan half only", flush=True)
@@ -277,6 +387,13 @@ def main():
             if not d.log:
                 sys.exit("--anchor needs the launch half")
             return 1 if anchor(d)[1] else 0
+        if args.attn_launches:
+            if not d.log:
+                sys.exit("--attn-launches needs the launch half")
+            print("\n".join(attn_launch_lines(d)))
+            return 0
+        if args.attn_check:
+            return 1 if attn_check(d, args.attn_check) else 0
         print("# build_flags %d %s" % (lib.e4t_build_flags(), " ".join("%s=%s" % (k, os.environ[k]) for k in sorted(os.environ) if k.startswith("E4T_") and k != "E4T_LIB")))
         for item in corpus():
             if args.group and item.group not in args.group:
