@@ -7,6 +7,8 @@ bf16 inputs with fp32 accumulation, so the relative L2 error against an fp32 eva
 bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumulation-order noise;
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
+
+Importable without a GPU: the attention case lists and slices() are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py).
 """
 from __future__ import annotations
 
@@ -258,55 +260,364 @@ def check_conv(hip, emu, dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ attention
+# (B, H, T, S, DH[, causal]) of check_attention.  tests/test_gemm_dispatch.py pins which kernels every one of them gets (and holds the set
+# of kernel symbols they reach against everything e4t_attention_plan can return), so this list is plain data: importable without a GPU.
+ATTENTION_CASES = [
+    (2, 2, 64, 64, 32), (2, 3, 200, 200, 40), (1, 2, 128, 77, 40), (2, 2, 96, 77, 80), (1, 2, 64, 64, 160),
+    (1, 2, 257, 257, 80), (2, 2, 130, 33, 64), (1, 8, 1024, 1024, 40),
+    (3, 5, 300, 300, 40), (2, 8, 4096, 4096, 40),        # 45 workgroups (XCD re-deal with a remainder); the step's own 64 x 64 self-attention
+    # S >= 2048, ragged tiles: dh 40 on the LDS-DMA kernels, dh 64 on attn_bwd_dkv_kernel<64, 2> with the query range cut in 7
+    (1, 2, 300, 2100, 40), (1, 1, 2050, 2050, 64),
+    (3, 12, 77, 77, 64, True), (2, 3, 200, 200, 40, True), (1, 2, 128, 128, 80, True),      # causal: CLIP text encoder
+    # few key blocks, long query range: the dK/dV kernel cuts T into chunks + fp32 partial reduce (round 4) — the step's own
+    # cross-attention shape at a smaller batch, a ragged T (3 chunks of 384 / 384 / 232), dh 80 / 64, a short self-attention
+    (2, 8, 4096, 77, 40), (1, 2, 1000, 77, 40), (2, 2, 1024, 77, 80), (1, 2, 600, 33, 64), (1, 4, 1024, 1024, 40),
+    # round 6: the 64-queries-per-wave forward (dh 40, S >= 512): last tile of 8 keys (its second sub-tile fully masked), of 33
+    # keys, ragged T inside a 256-query block, exactly one tile pair
+    (1, 2, 520, 520, 40), (2, 3, 700, 545, 40), (1, 1, 40, 512, 40), (2, 2, 256, 640, 40),
+    # ... and the 64-keys-per-wave dK/dV kernel + 64-queries-per-wave dQ kernel (dh 40, enough key blocks that the query range is
+    # not split): ragged T (last tile of 24 / 12 queries) and ragged S (last workgroup with 208 / 42 keys)
+    (4, 8, 600, 2000, 40), (2, 16, 1100, 2090, 40),
+]
+# The three-workgroups-per-CU instantiations attn_bwd_dkv_kernel<32 | 40, 3> (no register prefetch: another order of loads, barriers and
+# stores in the query loop), attn_bwd_dq_dma_kernel<32>, and the same no-prefetch loop at dh 160 over more than one query tile:
+ATTENTION_NEW_CASES = [
+    (1, 2, 130, 2100, 40),             # dkv<40, 3> (T < 192): query tiles of 64 / 64 / 2, last key block of 52
+    (1, 1, 2080, 2080, 40, True),      # dkv<40, 3> causal, query range cut in 7 chunks of 320 (the last: 160) + reduce
+    (1, 2, 200, 2100, 32),             # dq_dma<32> / dkv<32, 3>: last query tile of 8
+    (2, 2, 256, 256, 32),              # dq_dma<32> / dkv<32, 2>: the tiny-test UNet's own self-attention, fused qkv
+    (2, 2, 256, 256, 160),             # SD-1.x 16 x 16 level: 4 query tiles in the no-prefetch loop, 2 workgroups per head
+    (1, 2, 200, 77, 160),              # ... its cross-attention: ragged T and S
+    (1, 1, 300, 130, 160),             # last query tile of 44, last key block of 2
+    (1, 2, 600, 77, 160),              # query range cut in 2: fp32 partial store + attn_dkv_reduce_kernel<160>
+    (2, 2, 200, 233, 64),              # dq_dma<64> with a ragged last key tile and B, H > 1
+]
+ATTENTION_CASES += ATTENTION_NEW_CASES
+ATTENTION_DETERMINISM_CASES = [(16, 8, 4096, 4096, 40), (4, 8, 4096, 4096, 40)]      # the bitwise run-to-run check and its four batch chunks
+# The backward through the raw ABI with less workspace than the library asks for: (case, labels, entry point).  Labels as in
+# tools/gemm_dispatch_dump.py: delta = B * H * T floats, short = the stated size minus 1; "plain" = e4t_attention_bwd, which takes no size.
+ATTENTION_WS_CASES = [
+    ((1, 2, 300, 2100, 40), ("delta",), "ws"),            # no {L, Delta} pairs: dq_dma<40> with LD == nullptr in front of dkv<40, 3> (full: dkv_dma)
+    ((2, 3, 200, 200, 40), ("delta", "short"), "ws"),     # dkv<40, 2> instead of dkv_dma
+    ((2, 8, 1024, 77, 40), ("delta",), "plain"),          # one query chunk instead of four
+    ((1, 1, 2080, 2080, 40, True), ("delta",), "ws"),     # un-split causal dkv<40, 3>
+    ((1, 2, 600, 77, 160), ("delta",), "ws"),             # one query chunk instead of two
+]
+# cases that run once more with batch strides beyond dense, NaN in the input gaps and sentinels around every output (besides every new one)
+ATTENTION_GAP_CASES = [(3, 5, 300, 300, 40), (2, 2, 96, 77, 80), (2, 16, 1100, 2090, 40)]
+ATTENTION_NULL_LSE_CASES = [(2, 3, 200, 200, 40), (1, 2, 520, 520, 40)]
+# Peaked scores at scale 1.0: name -> (seed, (B, H, T, S, DH), ((key, query row, factor), ...)): k[key] = factor * q[row], i.e. a score of
+# factor * |q[row]|^2 ~ factor * DH for that pair — |LSE| up to ~1050 natural-log units.  The forward's online softmax sees large jumps of
+# the running max (first / middle / last tile, a best key that comes first, a huge negative score); the backward recomputes P from the
+# stored LSE, which the dh-40 dK/dV kernels fold into three bf16 pieces of the Q image.
+_FIVE = lambda last, mid, neg: ((3, 7, 8.0), (mid, 40, 12.0), (last, 5, 20.0), (0, 70, 30.0), (neg, 9, -30.0))
+ATTENTION_PEAKED = {
+    "dh64": (120, (1, 1, 64, 160, 64), ((130, 5, 6.0),)),
+    "dh40 long-key": (121, (1, 1, 96, 840, 40), _FIVE(834, 333, 500)),
+    "dh40 long-key T256": (122, (1, 1, 256, 840, 40), _FIVE(834, 333, 500)),      # dq_dma<40> / dkv_dma<40>; dkv<40, 2> with a Delta-only workspace
+    "dh80": (123, (1, 2, 96, 77, 80), ((70, 5, 4.0), (0, 50, 10.0))),            # attn_fwd_kernel<80>: row sum in the MFMA's spare row, lazy rescale
+    "dh40 short-key": (124, (1, 1, 96, 200, 40), _FIVE(197, 100, 150)),           # attn_fwd_kernel<40> (S < 512)
+}
+BLOCK_Q, BLOCK_K = 64, 128      # rows per query tile (O, dQ, LSE) and per dK/dV workgroup
+
+
+def peaked_attention_inputs(name, dev):
+    """(q, k, v, dO) of ATTENTION_PEAKED[name]: [T | S, H * DH] bf16, the spiked key rows set across all heads"""
+    seed, (B, H, T, S, DH), spikes = ATTENTION_PEAKED[name]
+    g = gen(seed, dev)
+    q, k, v = rnd(g, T, H * DH, dev=dev), rnd(g, S, H * DH, dev=dev), rnd(g, S, H * DH, dev=dev)
+    for key, row, mul in spikes:
+        k[key] = (q[row].float() * mul).to(bf16)
+    return q, k, v, rnd(g, T, H * DH, dev=dev)
+
+
+def lse_rows(lse):
+    """fp32 [B][H][T] -> [B * T, H]: the row layout slices() takes (one column per head)"""
+    B, H, T = lse.shape
+    return lse.permute(0, 2, 1).reshape(B * T, H)
+
+
+def slices(tag, got, ref, B, L, H, DH, block, tol=TOL2, blocks=True, every_block=False):
+    """Result rows that a whole-tensor relative L2 cannot give: got, ref = [B * L, >= H * DH] row-major, head h in columns [h * DH, (h + 1) * DH).
+      - the worst relative L2 of one (batch, head);
+      - the worst (batch, head) of the last `block`-row block alone, ragged or not, and of the block in front of it (blocks=True, L > block);
+      - the worst (batch, head, block) of all (every_block=True).
+    Never finer than a row block: a single row whose softmax is saturated has dS = 0 exactly, and its relative error means nothing.
+    The tolerance is the whole tensor's: the stated bound is per element, so it holds for any slice (tests/test_attention_slices_cpu.py
+    holds a rounding-only model of the kernels to half of it on every slice emitted here)."""
+    g = got[:, : H * DH].float().reshape(B, L, H, DH)
+    r = ref[:, : H * DH].float().reshape(B, L, H, DH)
+    d2, r2 = ((g - r) ** 2).sum(-1), (r * r).sum(-1)      # [B, L, H]
+
+    def worst(lo, hi):
+        e = (d2[:, lo:hi].sum(1) / (r2[:, lo:hi].sum(1) + 1e-38)).sqrt()
+        return float(torch.nan_to_num(e, nan=float("inf")).max())
+    out = [(f"{tag}: worst (batch, head)", worst(0, L), tol)]
+    last = (L - 1) // block * block
+    if blocks and last > 0:
+        out.append((f"{tag}: rows {last}-{L - 1} (last {block}-row block), worst (batch, head)", worst(last, L), tol))
+        out.append((f"{tag}: rows {last - block}-{last - 1} (the block in front), worst (batch, head)", worst(last - block, last), tol))
+    if every_block:
+        out.append((f"{tag}: worst {block}-row block of any (batch, head)", max(worst(lo, min(lo + block, L)) for lo in range(0, L, block)), tol))
+    return out
+
+
+def attention_slices(tag, B, H, T, S, DH, o, o_r, lse, lse_r, grads, grads_r, blocks=True, every_block=False):
+    """slices() of everything one attention case produces; o / lse may be None (backward-only comparisons)"""
+    out, kw = [], dict(blocks=blocks, every_block=every_block)
+    if o is not None:
+        out += slices(tag + " fwd O", o, o_r, B, T, H, DH, BLOCK_Q, **kw)
+        out += slices(tag + " fwd LSE", lse_rows(lse), lse_rows(lse_r), B, T, H, 1, BLOCK_Q, tol=1e-3, **kw)
+    for nm, a, b_, L, blk in zip(("dQ", "dK", "dV"), grads, grads_r, (T, S, S), (BLOCK_Q, BLOCK_K, BLOCK_K)):
+        out += slices(f"{tag} bwd {nm}", a, b_, B, L, H, DH, blk, **kw)
+    return out
+
+
+# ---- the raw ABI: explicit batch strides, a workspace of the caller's size, poison around everything -------------------------------
+SENT16, SENT32 = 0x5A5B, 0x5A5B5C5D      # what outputs, gaps and guards hold before a call: finite as bf16 and as fp32 (~1.5e16)
+GAP_Q, GAP_K, GUARD_ROWS, GUARD_LSE, PAD_COLS, WS_EXCESS = 3, 5, 128, 64, 8, 1024
+
+
+class _Operand:
+    """B batches of L rows x d columns at column c0 of a row-major bf16 buffer [rows][width], batch b starting at row b * (L + gap)"""
+
+    def __init__(self, buf, B, L, gap, c0, d):
+        self.buf, self.c0, self.d, self.ld, self.bstride = buf, c0, d, buf.stride(0), (L + gap) * buf.stride(0)
+        ar = lambda n: torch.arange(n, device=buf.device)
+        self.idx = (ar(B)[:, None] * (L + gap) + ar(L)[None, :]).reshape(-1)
+        self.ptr = buf.data_ptr() + 2 * c0
+
+    def put(self, t):
+        self.buf[self.idx, self.c0:self.c0 + self.d] = t[:, : self.d]
+        return self
+
+    def get(self):
+        return self.buf[self.idx, self.c0:self.c0 + self.d]
+
+
+def _sentinel_buf(rows, width, dev):
+    return torch.full((rows, width), SENT16, dtype=torch.int16, device=dev).view(bf16)
+
+
+def _changed_outside(buf, operands):
+    """elements of an output buffer outside its operands' valid rows x columns that no longer hold the sentinel"""
+    chk = buf.view(torch.int16).clone()
+    for op in operands:
+        chk[op.idx, op.c0:op.c0 + op.d] = SENT16
+    return int((chk != SENT16).sum())
+
+
+class RawAttention:
+    """e4t_attention_fwd / e4t_attention_bwd / e4t_attention_bwd_ws through ctypes, on buffers laid out here.  gaps=False: dense batch strides
+    (T * ld, S * ld), as e4t.ops passes them.  gaps=True: Q / O / dO / dQ have GAP_Q rows between batches and K / V / dK / dV GAP_K, GUARD_ROWS
+    rows follow the last batch, PAD_COLS columns lie beside the operands' own, GUARD_LSE floats behind the LSE; every input element outside the
+    operands is bf16 NaN and every output element a sentinel.  q | k | v share one buffer when T == S (the self-attention layout), else k | v do.
+    The workspace is WS_EXCESS floats longer than the size offered to the library, sentinel throughout."""
+
+    def __init__(self, hip, q, k, v, B, H, T, S, DH, scale, causal=False, gaps=False):
+        self.lib, self.shape, self.scale, self.causal, self.dev = hip.lib, (B, H, T, S, DH), float(scale), int(bool(causal)), q.device
+        d = H * DH
+        self.d, self.fused = d, T == S
+        self.gq, self.gk, self.guard, self.guard_lse, pad = (GAP_Q, GAP_K, GUARD_ROWS, GUARD_LSE, PAD_COLS) if gaps else (0, 0, 0, 0, 0)
+        rq, rk = B * (T + self.gq) + self.guard, B * (S + self.gk) + self.guard
+        self.shapes = [(max(rq, rk), 3 * d + pad)] if self.fused else [(rq, d + pad), (rk, 2 * d + pad)]
+        self.o_shape = (rq, d + pad)
+        self.inputs = self._operands([torch.full(s, float("nan"), dtype=bf16, device=self.dev) for s in self.shapes])
+        for op, t in zip(self.inputs, (q, k, v)):
+            op.put(t)
+
+    def _operands(self, bufs):
+        (B, H, T, S, DH), d = self.shape, self.d
+        if self.fused:
+            return [_Operand(bufs[0], B, T, self.gq, 0, d), _Operand(bufs[0], B, S, self.gk, d, d), _Operand(bufs[0], B, S, self.gk, 2 * d, d)]
+        return [_Operand(bufs[0], B, T, self.gq, 0, d), _Operand(bufs[1], B, S, self.gk, 0, d), _Operand(bufs[1], B, S, self.gk, d, d)]
+
+    def _tail(self, o_op):
+        from e4t.ops import _stream
+        B, H, T, S, DH = self.shape
+        q, k, v = self.inputs
+        return [B, H, T, S, DH, q.ld, k.ld, v.ld, o_op.ld, q.bstride, k.bstride, v.bstride, o_op.bstride, self.scale, self.causal, _stream()]
+
+    def forward(self, need_lse=True):
+        """-> dict(o [B*T, d], lse [B, H, T] | None, changed = sentinel elements overwritten, nan = NaN elements in O / LSE)"""
+        from e4t import _C
+        B, H, T, S, DH = self.shape
+        o_op = _Operand(_sentinel_buf(*self.o_shape, self.dev), B, T, self.gq, 0, self.d)
+        lse = torch.full((B * H * T + self.guard_lse,), SENT32, dtype=torch.int32, device=self.dev).view(f32)
+        q, k, v = self.inputs
+        _C.check(self.lib.e4t_attention_fwd(q.ptr, k.ptr, v.ptr, o_op.ptr, lse.data_ptr() if need_lse else None, *self._tail(o_op)), "e4t_attention_fwd")
+        o, L = o_op.get(), lse[: B * H * T].reshape(B, H, T)
+        changed = _changed_outside(o_op.buf, [o_op]) + int((lse.view(torch.int32)[B * H * T if need_lse else 0:] != SENT32).sum())
+        nan = int(torch.isnan(o).sum()) + (int(torch.isnan(L).sum()) if need_lse else 0)
+        return dict(o=o, lse=L.clone() if need_lse else None, changed=changed, nan=nan)
+
+    def backward(self, o, do, lse, ws="full", entry="ws"):
+        """-> dict(dq, dk, dv [B*T | B*S, d], changed = sentinel elements overwritten (gradient buffers and the workspace behind the offer), nan)"""
+        from e4t import _C
+        B, H, T, S, DH = self.shape
+        nan16 = lambda: torch.full(self.o_shape, float("nan"), dtype=bf16, device=self.dev)
+        o_op, do_op = _Operand(nan16(), B, T, self.gq, 0, self.d).put(o), _Operand(nan16(), B, T, self.gq, 0, self.d).put(do)
+        L = torch.full((B * H * T + self.guard_lse,), float("nan"), dtype=f32, device=self.dev)
+        L[: B * H * T] = lse.reshape(-1)
+        gbufs = [_sentinel_buf(*s, self.dev) for s in self.shapes]
+        grads = self._operands(gbufs)
+        full = self.lib.e4t_attention_bwd_workspace_floats(B, H, T, S, DH)
+        offer = {"full": full, "delta": B * H * T, "short": full - 1}[ws]
+        wsb = torch.full((offer + WS_EXCESS,), SENT32, dtype=torch.int32, device=self.dev)
+        q, k, v = self.inputs
+        head = [q.ptr, k.ptr, v.ptr, o_op.ptr, do_op.ptr, L.data_ptr(), wsb.data_ptr()]
+        out = [g.ptr for g in grads]
+        if entry == "plain":
+            assert ws == "delta", "e4t_attention_bwd takes no workspace size: it is B * H * T floats"
+            _C.check(self.lib.e4t_attention_bwd(*head, *out, *self._tail(o_op)), "e4t_attention_bwd")
+        else:
+            _C.check(self.lib.e4t_attention_bwd_ws(*head, offer, *out, *self._tail(o_op)), "e4t_attention_bwd_ws")
+        res = [g.get() for g in grads]
+        changed = sum(_changed_outside(b_, [g for g in grads if g.buf is b_]) for b_ in gbufs) + int((wsb[offer:] != SENT32).sum())
+        return dict(dq=res[0], dk=res[1], dv=res[2], changed=changed, nan=sum(int(torch.isnan(t).sum()) for t in res))
+
+
+def _neq(a, b):
+    """elements that differ bitwise (bf16 / fp32 tensors of one dtype)"""
+    it = torch.int16 if a.dtype == bf16 else torch.int32
+    return int((a.contiguous().view(it) != b.contiguous().view(it)).sum())
+
+
+def attention_gap_rows(hip, tag, q, k, v, o, lse, do, grads, B, H, T, S, DH, scale, causal, ws="full", entry="ws"):
+    """Forward and backward once more with batch strides beyond dense, NaN in every input gap and guard and sentinels in every output gap
+    and guard (RawAttention, gaps=True), against o / lse / grads = what the dense-stride call made of the same inputs.  The kernels mask
+    nothing: they rely on bounds-checked loads returning zeros behind a batch's last row, on L = +inf for query rows beyond T and on key
+    lanes beyond S polluting only their own, never stored, column — a NaN that leaks in anywhere shows here.  The arithmetic of the two
+    calls is the same (same kernels, same grid, same order), so the results must agree bitwise."""
+    raw = RawAttention(hip, q, k, v, B, H, T, S, DH, scale, causal, gaps=True)
+    f = raw.forward()
+    b = raw.backward(o, do, lse, ws=ws, entry=entry)
+    diff = _neq(f["o"], o) + _neq(f["lse"], lse) + sum(_neq(b[n], g) for n, g in zip(("dq", "dk", "dv"), grads))
+    tag = f"{tag} gaps {GAP_Q} | {GAP_K} rows" + ("" if ws == "full" else f" ws={ws}")
+    return [(tag + ": sentinel elements overwritten (O, LSE guard; dQ | dK | dV buffers, workspace excess)", float(f["changed"] + b["changed"]), 0.0),
+            (tag + ": NaN in O, LSE, dQ, dK, dV", float(f["nan"] + b["nan"]), 0.0),
+            (tag + ": elements differing bitwise from the dense-stride call", float(diff), 0.0)]
+
+
+def _attention_inputs(g, B, H, T, S, DH, dev):
+    """q, k, v as column slices of fused buffers (self-attn layout) when T == S, separate otherwise; gradient views of the same layout, twice"""
+    d = H * DH
+    if T == S:
+        qkv = rnd(g, B * T, 3 * d, dev=dev)
+        q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
+        dqkv_h = torch.zeros_like(qkv); dqkv_e = torch.zeros_like(qkv)
+        gh = (dqkv_h[:, :d], dqkv_h[:, d:2 * d], dqkv_h[:, 2 * d:])
+        ge = (dqkv_e[:, :d], dqkv_e[:, d:2 * d], dqkv_e[:, 2 * d:])
+    else:
+        q = rnd(g, B * T, d, dev=dev)
+        kv = rnd(g, B * S, 2 * d, dev=dev)
+        k, v = kv[:, :d], kv[:, d:]
+        dq_h, dq_e = torch.zeros_like(q), torch.zeros_like(q)
+        dkv_h, dkv_e = torch.zeros_like(kv), torch.zeros_like(kv)
+        gh = (dq_h, dkv_h[:, :d], dkv_h[:, d:]); ge = (dq_e, dkv_e[:, :d], dkv_e[:, d:])
+    return q, k, v, gh, ge
+
+
+def _attention_tag(case):
+    B, H, T, S, DH = case[:5]
+    return f"attn B{B} H{H} T{T} S{S} dh{DH}" + (" causal" if len(case) > 5 and case[5] else "")
+
+
 def check_attention(hip, emu, dev):
     out = []
-    cases = [  # B, H, T, S, DH (, causal)
-        (2, 2, 64, 64, 32), (2, 3, 200, 200, 40), (1, 2, 128, 77, 40), (2, 2, 96, 77, 80), (1, 2, 64, 64, 160),
-        (1, 2, 257, 257, 80), (2, 2, 130, 33, 64), (1, 8, 1024, 1024, 40),
-        (3, 5, 300, 300, 40), (2, 8, 4096, 4096, 40),        # 45 workgroups (XCD re-deal with a remainder); the step's own 64 x 64 self-attention
-        # S >= 2048, ragged tiles: dh 40 on the LDS-DMA kernels, dh 64 on attn_bwd_dkv_kernel<64, 2> with the query range cut in 7 (which kernel
-        # every case here gets: tests/test_gemm_dispatch.py; none reaches the three-workgroups-per-CU instantiation attn_bwd_dkv_kernel<40, 3>)
-        (1, 2, 300, 2100, 40), (1, 1, 2050, 2050, 64),
-        (3, 12, 77, 77, 64, True), (2, 3, 200, 200, 40, True), (1, 2, 128, 128, 80, True),      # causal: CLIP text encoder
-        # few key blocks, long query range: the dK/dV kernel cuts T into chunks + fp32 partial reduce (round 4) — the step's own
-        # cross-attention shape at a smaller batch, a ragged T (3 chunks of 384 / 384 / 232), dh 80 / 64, a short self-attention
-        (2, 8, 4096, 77, 40), (1, 2, 1000, 77, 40), (2, 2, 1024, 77, 80), (1, 2, 600, 33, 64), (1, 4, 1024, 1024, 40),
-        # round 6: the 64-queries-per-wave forward (dh 40, S >= 512): last tile of 8 keys (its second sub-tile fully masked), of 33
-        # keys, ragged T inside a 256-query block, exactly one tile pair
-        (1, 2, 520, 520, 40), (2, 3, 700, 545, 40), (1, 1, 40, 512, 40), (2, 2, 256, 640, 40),
-        # ... and the 64-keys-per-wave dK/dV kernel + 64-queries-per-wave dQ kernel (dh 40, enough key blocks that the query range is
-        # not split): ragged T (last tile of 24 / 12 queries) and ragged S (last workgroup with 208 / 42 keys)
-        (4, 8, 600, 2000, 40), (2, 16, 1100, 2090, 40),
-    ]
-    for i, case in enumerate(cases):
+    for i, case in enumerate(ATTENTION_CASES):
         (B, H, T, S, DH), causal = case[:5], (len(case) > 5 and case[5])
         g = gen(90 + i, dev)
-        d = H * DH
-        # q, k, v as column slices of fused buffers (self-attn layout) when T == S, separate otherwise
-        if T == S:
-            qkv = rnd(g, B * T, 3 * d, dev=dev)
-            q, k, v = qkv[:, :d], qkv[:, d:2 * d], qkv[:, 2 * d:]
-            dqkv_h = torch.zeros_like(qkv); dqkv_e = torch.zeros_like(qkv)
-            gh = (dqkv_h[:, :d], dqkv_h[:, d:2 * d], dqkv_h[:, 2 * d:])
-            ge = (dqkv_e[:, :d], dqkv_e[:, d:2 * d], dqkv_e[:, 2 * d:])
-        else:
-            q = rnd(g, B * T, d, dev=dev)
-            kv = rnd(g, B * S, 2 * d, dev=dev)
-            k, v = kv[:, :d], kv[:, d:]
-            dq_h, dq_e = torch.zeros_like(q), torch.zeros_like(q)
-            dkv_h, dkv_e = torch.zeros_like(kv), torch.zeros_like(kv)
-            gh = (dq_h, dkv_h[:, :d], dkv_h[:, d:]); ge = (dq_e, dkv_e[:, :d], dkv_e[:, d:])
+        q, k, v, gh, ge = _attention_inputs(g, B, H, T, S, DH, dev)
         scale = DH ** -0.5
         o, lse = hip.attention_fwd(q, k, v, B, H, T, S, DH, scale, causal=causal)
         o_r, lse_r = emu.attention_fwd(q, k, v, B, H, T, S, DH, scale, causal=causal)
-        tag = f"attn B{B} H{H} T{T} S{S} dh{DH}" + (" causal" if causal else "")
+        tag = _attention_tag(case)
         out.append((tag + " fwd O", rel(o, o_r), TOL2))
         out.append((tag + " fwd LSE", rel(lse, lse_r), 1e-3))
-        do = rnd(g, B * T, d, dev=dev)
+        do = rnd(g, B * T, H * DH, dev=dev)
         hip.attention_bwd(q, k, v, o, do, lse, gh[0], gh[1], gh[2], B, H, T, S, DH, scale, causal=causal)
         emu.attention_bwd(q, k, v, o_r, do, lse_r, ge[0], ge[1], ge[2], B, H, T, S, DH, scale, causal=causal)
         for nm, a, b in zip(("dQ", "dK", "dV"), gh, ge):
             out.append((tag + " bwd " + nm, rel(a, b), TOL2))
+        # per (batch, head), and the ragged last tiles the shapes were chosen for, on their own (B * T >= 8192: per head only)
+        out += attention_slices(tag, B, H, T, S, DH, o, o_r, lse, lse_r, gh, ge, blocks=B * T < 8192)
+        if case in ATTENTION_NEW_CASES or case in ATTENTION_GAP_CASES:
+            out += attention_gap_rows(hip, tag, q, k, v, o, lse, do, gh, B, H, T, S, DH, scale, causal)
+        if case in ATTENTION_NULL_LSE_CASES:      # the sampling path: no LSE wanted
+            o_n, _ = hip.attention_fwd(q, k, v, B, H, T, S, DH, scale, need_lse=False, causal=causal)
+            out.append((tag + " fwd O without LSE: elements differing bitwise from O with it", float(_neq(o_n, o)), 0.0))
+        del q, k, v, gh, ge, o, o_r, lse, lse_r, do
+    out += _check_attention_determinism(hip, emu, dev)
+    out += _check_attention_small_workspace(hip, emu, dev)
+    out += _check_attention_peaked(hip, emu, dev)
+    return out
+
+
+def _check_attention_small_workspace(hip, emu, dev):
+    """ATTENTION_WS_CASES: the backward through e4t_attention_bwd / e4t_attention_bwd_ws with a workspace that holds Delta only (or is one float
+    short of the stated size).  The library then runs one query chunk instead of the split and leaves no {L, Delta} pairs, hence the
+    register-staged dK/dV kernel behind a dQ kernel with LD == nullptr (which plan: tests/test_gemm_dispatch.py).  Against the emu backward,
+    as every other case; against the full-workspace result of the same inputs to rounding (other kernels run: both sides carry their own bf16
+    output rounding, rms 2^-9 / sqrt(3) = 1.1e-3 each, and P / dS rounded at other values — TOL1, as for single-rounding kernels); no float
+    behind the offered size may change; and once more with gaps and poison."""
+    out = []
+    for j, (case, labels, entry) in enumerate(ATTENTION_WS_CASES):
+        (B, H, T, S, DH), causal = case[:5], (len(case) > 5 and case[5])
+        g = gen(600 + j, dev)
+        q, k, v, gh, ge = _attention_inputs(g, B, H, T, S, DH, dev)
+        scale = DH ** -0.5
+        o, lse = hip.attention_fwd(q, k, v, B, H, T, S, DH, scale, causal=causal)
+        o_r, lse_r = emu.attention_fwd(q, k, v, B, H, T, S, DH, scale, causal=causal)
+        do = rnd(g, B * T, H * DH, dev=dev)
+        hip.attention_bwd(q, k, v, o, do, lse, gh[0], gh[1], gh[2], B, H, T, S, DH, scale, causal=causal)
+        emu.attention_bwd(q, k, v, o_r, do, lse_r, ge[0], ge[1], ge[2], B, H, T, S, DH, scale, causal=causal)
+        raw = RawAttention(hip, q, k, v, B, H, T, S, DH, scale, causal)
+        for ws in labels:
+            tag = f"{_attention_tag(case)} ws={ws}" + (" (e4t_attention_bwd)" if entry == "plain" else "")
+            r = raw.backward(o, do, lse, ws=ws, entry=entry)
+            got = (r["dq"], r["dk"], r["dv"])
+            for nm, a, b, f in zip(("dQ", "dK", "dV"), got, ge, gh):
+                out.append((f"{tag} bwd {nm}", rel(a, b), TOL2))
+                out.append((f"{tag} bwd {nm} ~ the full-workspace result", rel(a, f), TOL1))
+            out += attention_slices(tag, B, H, T, S, DH, None, None, None, None, got, ge)
+            out.append((tag + ": workspace floats behind the offered size overwritten", float(r["changed"]), 0.0))
+            out.append((tag + ": NaN in dQ, dK, dV", float(r["nan"]), 0.0))
+            out += attention_gap_rows(hip, _attention_tag(case), q, k, v, o, lse, do, got, B, H, T, S, DH, scale, causal, ws=ws, entry=entry)
+    return out
+
+
+def _check_attention_peaked(hip, emu, dev):
+    """ATTENTION_PEAKED, forward and backward.  The backward of both sides gets the SAME O and LSE, the emu's: where the softmax is saturated
+    dP - Delta cancels, and two differently rounded O would dominate the comparison instead of the backward kernels.  Whole tensor and
+    64 / 128-row blocks only (slices())."""
+    out = []
+    for name, (_, (B, H, T, S, DH), _) in ATTENTION_PEAKED.items():
+        q, k, v, do = peaked_attention_inputs(name, dev)
+        tag = f"attn peaked-score {name} (T{T} S{S} dh{DH})"
+        o, lse = hip.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
+        o_r, lse_r = emu.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
+        out.append((tag + " fwd O", rel(o, o_r), TOL2))
+        out.append((tag + " fwd LSE", rel(lse, lse_r), 1e-3))
+        gh, ge = [torch.zeros_like(t) for t in (q, k, v)], [torch.zeros_like(t) for t in (q, k, v)]
+        hip.attention_bwd(q, k, v, o_r, do, lse_r, gh[0], gh[1], gh[2], B, H, T, S, DH, 1.0)
+        emu.attention_bwd(q, k, v, o_r, do, lse_r, ge[0], ge[1], ge[2], B, H, T, S, DH, 1.0)
+        for nm, a, b in zip(("dQ", "dK", "dV"), gh, ge):
+            out.append((tag + " bwd " + nm, rel(a, b), TOL2))
+        out += attention_slices(tag, B, H, T, S, DH, o, o_r, lse, lse_r, gh, ge, every_block=True)
+        if name == "dh40 long-key T256":      # ... and through attn_bwd_dkv_kernel<40, 2>, which a Delta-only workspace gives this shape
+            r = RawAttention(hip, q, k, v, B, H, T, S, DH, 1.0).backward(o_r, do, lse_r, ws="delta")
+            got = (r["dq"], r["dk"], r["dv"])
+            for nm, a, b in zip(("dQ", "dK", "dV"), got, ge):
+                out.append((f"{tag} ws=delta bwd {nm}", rel(a, b), TOL2))
+            out += attention_slices(tag + " ws=delta", B, H, T, S, DH, None, None, None, None, got, ge, every_block=True)
+            out.append((tag + " ws=delta: workspace floats behind the offered size overwritten", float(r["changed"]), 0.0))
+    return out
+
+
+def _check_attention_determinism(hip, emu, dev):
+    out = []
     # The step's own dh-40 self-attention at the bench batch (B16 H8 T = S = 4096: 2048-4096 workgroups = several rounds of two / three
     # resident workgroups per CU — the regime in which round 6's LDS-DMA kernels first showed a race: pad columns written into rows
     # whose DMA piece another wave still had in flight; every smaller case above ran one round and passed): outputs must be BITWISE equal
@@ -336,25 +647,6 @@ def check_attention(hip, emu, dev):
     for nm, sl_ in (("dQ", slice(0, d)), ("dK", slice(d, 2 * d)), ("dV", slice(2 * d, 3 * d))):
         out.append((f"attn B16 == 4 x B4 bwd {nm}", rel(runs[0][2][:, sl_], g4[:, sl_]), 1e-5))
     del runs, o4, g4, qkv, do
-    # peaked scores: one key dominates (exercises the online-softmax rescale with large max jumps)
-    g = gen(120, dev)
-    B, H, T, S, DH = 1, 1, 64, 160, 64
-    q, k, v = rnd(g, T, DH, dev=dev), rnd(g, S, DH, dev=dev), rnd(g, S, DH, dev=dev)
-    k[130] = (q[5].float() * 6).to(bf16)
-    o, lse = hip.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
-    o_r, lse_r = emu.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
-    out.append(("attn peaked-score fwd", rel(o, o_r), TOL2))
-    # the same on the dh-40 long-key kernel: keys that beat the running max by far in the first, a middle and the last tile (its slow
-    # path: P recomputed after the row max is raised), a row whose best key comes first, and a huge negative score
-    g = gen(121, dev)
-    B, H, T, S, DH = 1, 1, 96, 840, 40
-    q, k, v = rnd(g, T, DH, dev=dev), rnd(g, S, DH, dev=dev), rnd(g, S, DH, dev=dev)
-    for key, row, mul in ((3, 7, 8.0), (333, 40, 12.0), (834, 5, 20.0), (0, 70, 30.0), (500, 9, -30.0)):
-        k[key] = (q[row].float() * mul).to(bf16)
-    o, lse = hip.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
-    o_r, lse_r = emu.attention_fwd(q, k, v, B, H, T, S, DH, 1.0)
-    out.append(("attn peaked-score dh40 long-key fwd O", rel(o, o_r), TOL2))
-    out.append(("attn peaked-score dh40 long-key fwd LSE", rel(lse, lse_r), 1e-3))
     return out
 
 

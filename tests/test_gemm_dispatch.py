@@ -110,9 +110,9 @@ def test_step_attention_shapes_get_the_recorded_kernels(dumper):
     assert by_shape["attn B=16 H=8 T=4096 S=77 DH=40 causal=0"][:4] == ["attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "8 512"]
 
 
-# (B, H, T, S, DH[, causal]) of tests/kernel_checks.py::check_attention -> the kernels the launch log named for it, with the workspace the library asks
-# for, at the last commit before e4t_attention_plan (b388eee): which kernels the GPU suite exercises.  Not reached by any of them:
-# attn_bwd_dkv_kernel<32 | 40, 3> (S >= 2048 with T < 192, causal, or a split query range), attn_bwd_dq_dma_kernel<32>.
+# (B, H, T, S, DH[, causal]) of tests/kernel_checks.py::check_attention -> the kernels it gets with the workspace the library asks for (the
+# first 30 as the launch log named them at b388eee, the last commit before e4t_attention_plan) [, "tsplit tchunk" where the case is there for its
+# query split].  The keys are held against the check's own case lists, the kernel symbols against everything the plan can return.
 CHECK_ATTENTION_KERNELS = {
     (2, 2, 64, 64, 32): ("attn_fwd_kernel<32>", "attn_bwd_dq_kernel<32>", "attn_bwd_dkv_kernel<32, 2>"),
     (2, 3, 200, 200, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
@@ -140,14 +140,74 @@ CHECK_ATTENTION_KERNELS = {
     (2, 2, 256, 640, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
     (4, 8, 600, 2000, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
     (2, 16, 1100, 2090, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),
+    (1, 2, 130, 2100, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 3>"),
+    (1, 1, 2080, 2080, 40, True): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 3>", "7 320"),
+    (1, 2, 200, 2100, 32): ("attn_fwd_kernel<32>", "attn_bwd_dq_dma_kernel<32>", "attn_bwd_dkv_kernel<32, 3>"),
+    (2, 2, 256, 256, 32): ("attn_fwd_kernel<32>", "attn_bwd_dq_dma_kernel<32>", "attn_bwd_dkv_kernel<32, 2>"),
+    (2, 2, 256, 256, 160): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>"),
+    (1, 2, 200, 77, 160): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>"),
+    (1, 1, 300, 130, 160): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>"),
+    (1, 2, 600, 77, 160): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>", "2 320"),
+    (2, 2, 200, 233, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_dma_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),
     (16, 8, 4096, 4096, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),      # the bitwise determinism check
     (4, 8, 4096, 4096, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),       # ... and its four batch chunks
-    (1, 1, 64, 160, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),                 # peaked scores (forward only)
+    (1, 1, 64, 160, 64): ("attn_fwd_kernel<64>", "attn_bwd_dq_kernel<64>", "attn_bwd_dkv_kernel<64, 2>"),                 # peaked scores
     (1, 1, 96, 840, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),           # ... on the long-key forward
+    (1, 1, 256, 840, 40): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_dma_kernel<40>"),         # ... and the LDS-DMA dK/dV kernel
+    (1, 2, 96, 77, 80): ("attn_fwd_kernel<80>", "attn_bwd_dq_kernel<80>", "attn_bwd_dkv_kernel<80, 1>"),                  # ... the row sum in the MFMA's spare row
+    (1, 1, 96, 200, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>"),             # ... the short-key dh-40 forward
+    (2, 8, 1024, 77, 40): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "4 256"),       # the full-workspace side of a small-workspace case
 }
+
+# (case, workspace label of tools/gemm_dispatch_dump.py) -> what a workspace smaller than the stated size gives: the backward calls check_attention makes
+# through the raw ABI (kernel_checks.ATTENTION_WS_CASES, and the peaked T256 input with a Delta-only workspace).  One query chunk, no {L, Delta} pairs.
+CHECK_ATTENTION_WS_KERNELS = {
+    ((1, 2, 300, 2100, 40), "delta"): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 3>", "1 320"),
+    ((2, 3, 200, 200, 40), "delta"): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "1 256"),
+    ((2, 3, 200, 200, 40), "short"): ("attn_fwd_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "1 256"),
+    ((2, 8, 1024, 77, 40), "delta"): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "1 256"),
+    ((1, 1, 2080, 2080, 40, True), "delta"): ("attn_fwd_kernel<40>", "attn_bwd_dq_kernel<40>", "attn_bwd_dkv_kernel<40, 3>", "1 320"),
+    ((1, 2, 600, 77, 160), "delta"): ("attn_fwd_kernel<160>", "attn_bwd_dq_kernel<160>", "attn_bwd_dkv_kernel<160, 1>", "1 320"),
+    ((1, 1, 256, 840, 40), "delta"): ("attn_fwd64_kernel<40>", "attn_bwd_dq_dma_kernel<40>", "attn_bwd_dkv_kernel<40, 2>", "1 256"),
+}
+
+
+def _plan_kw(case, ws):
+    return dict(zip(("B", "H", "T", "S", "DH"), case[:5]), causal=int(len(case) > 5 and bool(case[5])), ws=ws)
+
+
+def test_the_pinned_tables_cover_exactly_what_check_attention_runs():
+    """one case list (tests/kernel_checks.py, importable without a GPU) behind the GPU check and these tables"""
+    import kernel_checks as kc
+    peaked = [shape for _, shape, _ in kc.ATTENTION_PEAKED.values()]
+    small_ws = [case for case, _, _ in kc.ATTENTION_WS_CASES]
+    assert len(set(kc.ATTENTION_CASES)) == len(kc.ATTENTION_CASES)
+    assert set(CHECK_ATTENTION_KERNELS) == set(kc.ATTENTION_CASES) | set(kc.ATTENTION_DETERMINISM_CASES) | set(peaked) | set(small_ws)
+    assert set(CHECK_ATTENTION_WS_KERNELS) == {(case, ws) for case, labels, _ in kc.ATTENTION_WS_CASES for ws in labels} | {((1, 1, 256, 840, 40), "delta")}
+    for group in (kc.ATTENTION_NEW_CASES, kc.ATTENTION_GAP_CASES, kc.ATTENTION_NULL_LSE_CASES):
+        assert set(group) <= set(kc.ATTENTION_CASES)
+    assert all(entry == "plain" or entry == "ws" for _, _, entry in kc.ATTENTION_WS_CASES) and any(entry == "plain" for _, _, entry in kc.ATTENTION_WS_CASES)
 
 
 def test_check_attention_shapes_keep_their_kernels(dumper):
     for case, kernels in CHECK_ATTENTION_KERNELS.items():
-        kw = dict(zip(("B", "H", "T", "S", "DH"), case[:5]), causal=int(len(case) > 5), ws="full")
-        assert tuple(dumper.attn_plan(kw).split(" | ")[:3]) == kernels, case
+        plan = dumper.attn_plan(_plan_kw(case, "full")).split(" | ")
+        assert tuple(plan[:len(kernels)]) == kernels, case
+    for (case, ws), kernels in CHECK_ATTENTION_WS_KERNELS.items():
+        assert tuple(dumper.attn_plan(_plan_kw(case, ws)).split(" | ")[:4]) == kernels, (case, ws)
+        assert tuple(dumper.attn_plan(_plan_kw(case, "full")).split(" | ")[:4]) != kernels, (case, ws)      # the small workspace changes the plan
+
+
+def test_check_attention_reaches_every_kernel_the_plan_can_name(dumper):
+    """the kernel symbols of the pinned full-workspace table == the symbols e4t_attention_plan returns anywhere in the `attn` corpus with the
+    workspace the library asks for: an instantiation added to the dispatch (or a threshold moved so that one is newly reached) fails here until
+    check_attention has a shape that executes it"""
+    reachable = set()
+    for item in dump.attn_corpus():
+        if item.kw["ws"] == "full":
+            reachable |= set(dumper.attn_plan(item.kw).split(" | ")[:3])
+    assert len(reachable) == 22
+    pinned = {sym for kernels in CHECK_ATTENTION_KERNELS.values() for sym in kernels[:3]}
+    assert pinned == reachable, (sorted(reachable - pinned), sorted(pinned - reachable))
+    # a smaller workspace selects among the same kernels: nothing is reachable only that way
+    assert {sym for kernels in CHECK_ATTENTION_WS_KERNELS.values() for sym in kernels[:3]} <= reachable
