@@ -31,11 +31,6 @@
 // e4t/models/unet_2d_condition.py:106-108,285-287 ; [3P open_clip] ViT linears (e4t/encoder.py:154).
 #include "gemm_common.h"
 
-#ifndef E4T_GEMM_PS_DEFAULT
-#define E4T_GEMM_PS_DEFAULT 0      // automatic choice of the persistent 256 x BN kernel (gemm_ps.hip); E4T_GEMM_PS=0/1 overrides
-#endif
-extern "C" __attribute__((visibility("hidden"))) int e4t_launch_gemm_ps(const GemmArgs* p, int conv, int bn, int general, int ncu, hipStream_t st);
-
 namespace {
 
 
@@ -253,13 +248,12 @@ __global__ __launch_bounds__(WGM * WGN * 64, (BM == 256 && KT == 32) ? 4 : (BN =
 //   counted waits are vmcnt(1) / (4) / (1) for kx = 0 / 1 / 2 (what may still be in flight behind the B tile — and strip — the sub-step
 //   needs), one barrier per sub-step as in the tile kernel.
 // ------------------------------------------------------------------------------------------------
-#ifndef CONV_STRIP
-#define CONV_STRIP 1
-#endif
 // WGN = 2: 256 x 128 tile, 8 waves, two workgroups per CU.  WGN = 4: 256 x 256 tile, 16 waves in ONE workgroup per CU — the same four waves
 // per SIMD, a strip now feeds 256 output channels (half the A-side fill per flop again), and the waves split the issue work: waves 0-7
 // stage the strips (3 pieces each per strip), waves 8-15 the 256 x 32 B tiles (2 pieces each per sub-step), each group with its own
-// counted wait (vmcnt(0) once per strip / vmcnt(2) per sub-step).
+// counted wait (vmcnt(0) once per strip / vmcnt(2) per sub-step).  Only WGN = 2 is instantiated: WGN = 4 measured equal to the ping-pong kernel it would
+// replace (the LDS read port).  Its branches stay in the source: written out for 8 waves alone, conv_strip_kernel<2> compiles to a different instruction
+// stream.  They go with the next change to this kernel that carries its own measurement.
 template <int WGN>
 __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
   constexpr int BN = 64 * WGN, KT = 32, WM = 64, WN = 64, FM = 2, FN = 2;
@@ -409,7 +403,7 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
 }
 // may a 256 x 128 x 32 (WGN = 2) / 256 x 256 (WGN = 4, in place of the ping-pong kernel) conv launch go to conv_strip_kernel?
 static bool conv_strip_ok(const GemmArgs& p, int splitk, int batch) {
-  static const bool on = CONV_STRIP && getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
+  static const bool on = getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
   const bool rows = p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0);      // row segments, or whole rows per tile
   return on && p.mode == E4T_CONV_S1 && p.chan_major && splitk == 1 && batch == 1 && rows && p.Wout == p.Win && p.Hout == p.Hin &&
          p.Cin % 32 == 0 && p.K == 9 * p.Cin;
@@ -453,12 +447,6 @@ __device__ unsigned long long g_pp_trace[2 * 6 * 64];
 #endif
 #else
 #define PP_STAMP(slot) do { } while (0)
-#endif
-// timing ablations of the debug trace build (results are garbage): -DPP_NOREAD skips the fragment reads, -DPP_NOWAIT the vmcnt waits
-#ifdef PP_NOREAD
-#define PP_LDSREAD(ptr) bf16x8{}
-#else
-#define PP_LDSREAD(ptr) (*(const bf16x8*)(ptr))
 #endif
 // CM (round 5): the channel-chunk-major K order of the stride-1 3x3 convs is a compile-time property of the instantiation, and the K loop
 // runs its steady state — every quarter issue unconditional — apart from the last tiles.  As a runtime flag (round 3) both walks lived in
@@ -672,12 +660,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks) af[i][ks] = PP_LDSREAD(qa + a_off[mh * 2 + i][ks]);
+      for (int ks = 0; ks < 2; ++ks) af[i][ks] = *(const bf16x8*)(qa + a_off[mh * 2 + i][ks]);
     if (mh == 0) {
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) bfr[j][ks] = PP_LDSREAD(qb + b_off[j][ks]);
+        for (int ks = 0; ks < 2; ++ks) bfr[j][ks] = *(const bf16x8*)(qb + b_off[j][ks]);
     }
     bool staged;
     if (ph == 0)      { staged = ALL || kt + 1 < kt_end; if (staged) issue_b(kt + 1, true, other + 3 * QUART); }
@@ -685,9 +673,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
     else if (ph == 2) { staged = ALL || kt + 2 < kt_end; if (staged) issue_b(kt + 2, false, buf + 1 * QUART); }
     else              { staged = ALL || kt + 2 < kt_end; if (staged) issue_a(kt + 2, false, buf + 0 * QUART); }
     PP_STAMP(1);
-#ifndef PP_NOWAIT
     if (ALL || staged) wait_vmcnt<8>(); else wait_vmcnt<0>();
-#endif
     PP_STAMP(2);
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -764,9 +750,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
 // Requires: E4T_CONV_S1, chan_major, Cin % 64 == 0, W % 256 == 0 or (256 % W == 0, W >= 16, H % (256 / W) == 0), a K range per split that
 // starts and ends on a kernel row (ktiles_per_split % 3 == 0).  Results differ from gemm_pp_kernel's in nothing (same K order, same MFMAs).
 // ------------------------------------------------------------------------------------------------
-#ifndef PPS_SPREAD
-#define PPS_SPREAD 1      // 1: the next strip goes out one piece of each half per phase g = 1, 3, 5 (0: both halves as bursts of three in g = 1 / 3 — 1-2 % slower)
-#endif
 template <bool GENERAL>
 __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
   constexpr int BM = 256, BN = 256, HK = 32;
@@ -846,7 +829,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
       buf_dma16(rs_a, a_vo[i] | (unsigned)__builtin_amdgcn_sbfe(a_inv[i], (unsigned)a_ky, 1u), so, dst + (wave + 8 * i) * 512);
     if (hi && ++a_ky == 3) { a_ky = 0; a_chb += BK * 2; }
   };
-  // PPS_SPREAD: piece i of BOTH halves of the next strip per call (three calls per strip, in phase 1 of the kx = 0, 1, 2 tiles... see phase())
+  // piece i of BOTH halves of the next strip per call (three calls per strip, in phase 1 of the kx = 0, 1, 2 tiles... see phase())
   auto issue_strip_piece = [&](auto Ic, bool last, bf16_t* dst_lo) __attribute__((always_inline)) {
     constexpr int i = decltype(Ic)::value;
     const int iy = y + a_ky - 1;
@@ -915,18 +898,12 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
     bool staged = true;              // phases that issue nothing by design keep the pattern's count
     if (ph == 0)      { staged = ALL || kt + 1 < kt_end; if (staged) issue_b(true, Bq + (2 * (bb ^ 1) + 1) * QUART); }
     else if (ph == 2) { staged = ALL || kt + 2 < kt_end; if (staged) issue_b(false, Bq + (2 * bb + 0) * QUART); }
-#if PPS_SPREAD
     // one piece of each half of the next strip in phases g = 1, 3, 5 of the strip's twelve (both halves land >= 5 events before their first read at g = 12 / 14)
     else if (4 * KX + ph == 1) { staged = ALL || kt + 3 < kt_end; if (staged) issue_strip_piece(I0{}, false, smem + 2 * (SP ^ 1) * HSTRIP); }
     else if (4 * KX + ph == 3) { staged = ALL || kt + 3 < kt_end; if (staged) issue_strip_piece(I1{}, false, smem + 2 * (SP ^ 1) * HSTRIP); }
     else if (4 * KX + ph == 5) { staged = ALL || kt + 2 < kt_end; if (staged) issue_strip_piece(I2{}, true, smem + 2 * (SP ^ 1) * HSTRIP); }
     constexpr int G_ = 4 * KX + ph;
     constexpr int NW_ = G_ == 0 ? 4 : G_ <= 2 ? 6 : G_ <= 6 ? 8 : G_ <= 8 ? 6 : 4;
-#else
-    else if (KX == 0) { staged = ALL || kt + 3 < kt_end; if (staged) issue_strip(ph == 3, smem + (2 * (SP ^ 1) + kh) * HSTRIP); }
-    // at most the pieces of the last four issue events outstanding (2 per B quarter, 3 per half-strip, 0 where nothing is issued)
-    constexpr int NW_ = KX == 0 ? (ph == 0 ? 4 : ph == 3 ? 10 : 7) : KX == 1 ? (ph == 0 ? 10 : ph == 3 ? 4 : 7) : 4;
-#endif
     if (ALL || staged) wait_vmcnt<NW_>(); else wait_vmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
@@ -969,7 +946,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
 }
 // may a 256 x 256 ping-pong conv launch go to gemm_pps_kernel?
 static bool conv_pps_ok(const GemmArgs& p, int /*splitk*/, int batch) {
-  static const bool on = CONV_STRIP && getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
+  static const bool on = getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
   const bool rows = p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0);
   return on && p.mode == E4T_CONV_S1 && p.chan_major && batch == 1 && rows && p.Wout == p.Win && p.Hout == p.Hin && p.Cin % 64 == 0 &&
          p.K == 9 * p.Cin && p.ktiles_per_split % 3 == 0 && p.M % 256 == 0;
@@ -1007,241 +984,6 @@ __global__ __launch_bounds__(512) void gemm_pq_geglu_kernel(GemmArgs p) {
   constexpr bool GENERAL = false;
 #include "gemm_pq_kernel.inc"
 }
-
-#ifdef E4T_EXPERIMENTAL
-// ------------------------------------------------------------------------------------------------
-// 512 x 128 ("tall") ping-pong tile: the same phase machine with the operand roles exchanged, for outputs that are only
-// 128 columns wide (the VAE's 128-channel 3x3 convs at 512^2: M = 4.2 M rows, N = 128 — a 256-wide tile would be half empty
-// and the 128 x 128 tile reaches 680 TF/s there).
-//   * 8 waves = 2 groups (wr, 256 rows each) x 4 row slices (wc, 64 rows), wave tile 64 x 128 (2 x 4 accumulators);
-//   * phases = (k 0-31 | 32-63) x (columns 0-63 | 64-127): B fragments are read every phase, A fragments when nh == 0;
-//   * quarters: A = 512 rows x 32 k = 32 KiB (4 DMA instructions per wave), B = 128 rows x 32 k = 8 KiB (1 instruction);
-//     two buffers x two k-halves x (A + B) = 160 KiB = the whole LDS of a CU.  Any 4 consecutive quarters are 2 A + 2 B =
-//     10 instructions per wave, hence vmcnt(10) where the square kernel has vmcnt(8).  Issue order per K-tile:
-//     A-hi(t+1), B-hi(t+1), A-lo(t+2), B-lo(t+2) in phases 0..3 — every slot is re-staged 2 phases after its last read.
-// ------------------------------------------------------------------------------------------------
-template <int MODE>
-__global__ __launch_bounds__(512) void gemm_pt_kernel(GemmArgs p) {
-  constexpr int BM = 512, BN = 128, HK = 32;
-  constexpr int QA = BM * HK, QB = BN * HK;              // elements per A / B quarter
-  constexpr int HALF = QA + QB;                          // one k-half of a buffer: [A | B]
-  constexpr int SMEM = 4 * HALF;                         // 81920 elements = 160 KiB
-  static_assert(8 * 64 * (64 + 8) <= SMEM, "epilogue staging must fit");
-  __shared__ __attribute__((aligned(16))) bf16_t smem[SMEM];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  int tile_x, tile_y;
-  xcd_tile(tile_x, tile_y, p.group_m);
-  const int m0 = tile_y * BM, n0 = tile_x * BN;
-
-  const int nkt = p.K / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split;
-  int kt_end = kt_begin + p.ktiles_per_split;
-  if (kt_end > nkt) kt_end = nkt;
-
-  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, (int)(p.A2 ? p.a2_bytes : p.a_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;
-  // DMA: one wave-instruction = 16 rows x 64 B.  A: wave w feeds quarter rows 64w + 16j + (lane >> 2), j = 0..3; B: rows 16w + (lane >> 2)
-  const int drow = lane >> 2, dslot = lane & 3;
-  long long a_base[4];
-  int a_oy[4], a_ox[4], a_kc[4];
-  bool a_ok[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int r = wave * 64 + j * 16 + drow;
-    a_kc[j] = (dslot ^ ((r >> 2) & 3)) * 8;
-    const int gr = m0 + r;
-    a_ok[j] = gr < p.M;
-    if (MODE == 0) {
-      a_base[j] = (long long)gr; a_oy[j] = a_ox[j] = 0;
-    } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[j] = rem / p.Wout;
-      a_ox[j] = rem - a_oy[j] * p.Wout;
-      a_base[j] = (long long)b * p.Hin * p.Win;
-    }
-  }
-  unsigned b_vo;
-  {
-    const int r = wave * 16 + drow;
-    const int kc = (dslot ^ ((r >> 2) & 3)) * 8;
-    const int gn = n0 + r;
-    b_vo = gn < p.N ? (unsigned)(((size_t)gn * p.ldb + kc) * 2) : OOB;
-  }
-  unsigned a_vo[4];
-  int a_so = 0, b_so = 0;
-  bool a_second = false;
-  auto place_a = [&](int k0) {
-    if (MODE == 0) {
-      int ld = p.lda, koff = k0;
-      a_second = k0 >= p.K1;
-      if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
-      a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) a_vo[j] = a_ok[j] ? (unsigned)((a_base[j] * ld + a_kc[j]) * 2) : OOB;
-    } else {
-      const int tap = k0 / p.Cin;
-      const int ci0 = k0 - tap * p.Cin;
-      const int ky = tap / 3, kx = tap - ky * 3;
-      a_so = __builtin_amdgcn_readfirstlane(ci0 * 2);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int iy, ix;
-        bool ok = a_ok[j];
-        if (p.mode == E4T_CONV_S1) {
-          iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_S2) {
-          iy = 2 * a_oy[j] + ky - 1; ix = 2 * a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
-        } else if (p.mode == E4T_CONV_UP2) {
-          iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
-          ok = ok && iy >= 0 && iy < 2 * p.Hin && ix >= 0 && ix < 2 * p.Win;
-          iy >>= 1; ix >>= 1;
-        } else if (p.mode == E4T_CONV_S2A) {
-          iy = 2 * a_oy[j] + ky; ix = 2 * a_ox[j] + kx;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        } else {
-          const int sy = a_oy[j] + ky - 1, sx = a_ox[j] + kx - 1;
-          ok = ok && sy >= 0 && sx >= 0 && !(sy & 1) && !(sx & 1);
-          iy = sy >> 1; ix = sx >> 1;
-          ok = ok && iy < p.Hin && ix < p.Win;
-        }
-        a_vo[j] = ok ? (unsigned)(((a_base[j] + (long long)iy * p.Win + ix) * p.Cin + a_kc[j]) * 2) : OOB;
-      }
-    }
-  };
-  auto issue_a = [&](int kt, bool hi, bf16_t* dst) __attribute__((always_inline)) {
-    const int k0 = kt * BK;
-    const bool fresh = !hi && (kt == kt_begin || (MODE == 0 ? k0 == p.K1 : (k0 % p.Cin) == 0));
-    if (fresh) place_a(k0);
-    else a_so = __builtin_amdgcn_readfirstlane(a_so + HK * 2);
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-      buf_dma16(a_second ? rs_a2 : rs_a, a_vo[j], a_so, dst + (wave * 64 + j * 16) * HK);
-  };
-  auto issue_b = [&](int kt, bool hi, bf16_t* dst) __attribute__((always_inline)) {
-    if (!hi && kt == kt_begin) b_so = kt * BK * 2;
-    else b_so = __builtin_amdgcn_readfirstlane(b_so + HK * 2);
-    buf_dma16(rs_b, b_vo, b_so, dst + (wave * 16) * HK);
-  };
-
-  f32x16 acc[2][2][2];          // [column half][row block][column block]
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[h][i][j][r] = 0.f;
-
-  const int frow = lane & 31, fhi = lane >> 5;
-  int a_off[2][2], b_off[4][2];     // fragment offsets inside a quarter (elements), [block][k-step of the half]
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const int r = wr * 256 + wc * 64 + i * 32 + frow;
-      a_off[i][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int r = j * 32 + frow;
-      b_off[j][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
-    }
-  }
-  // buffer b = smem + 2b * HALF: [lo: A | B][hi: A | B]
-  issue_a(kt_begin, false, smem);
-  issue_b(kt_begin, false, smem + QA);
-  issue_a(kt_begin, true, smem + HALF);
-  issue_b(kt_begin, true, smem + HALF + QA);
-  if (kt_begin + 1 < kt_end) {
-    issue_a(kt_begin + 1, false, smem + 2 * HALF);
-    issue_b(kt_begin + 1, false, smem + 2 * HALF + QA);
-    wait_vmcnt<10>();              // 15 issued: the two lo quarters of the first K-tile have landed
-  } else {
-    wait_vmcnt<0>();
-  }
-  __builtin_amdgcn_s_barrier();
-
-  bf16x8 af[2][2], bfr[2][2];
-  auto phase = [&](auto Bc, auto Pc, int kt) {
-    constexpr int b = decltype(Bc)::value, ph = decltype(Pc)::value;
-    constexpr int kh = ph >> 1, nh = ph & 1;
-    bf16_t* const buf = smem + b * 2 * HALF;
-    bf16_t* const other = smem + (b ^ 1) * 2 * HALF;
-    const bf16_t* const qa = buf + kh * HALF;
-    const bf16_t* const qb = qa + QA;
-    // ---- L segment ----
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) bfr[j][ks] = *(const bf16x8*)(qb + b_off[nh * 2 + j][ks]);
-    if (nh == 0) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) af[i][ks] = *(const bf16x8*)(qa + a_off[i][ks]);
-    }
-    bool staged;
-    if (ph == 0)      { staged = kt + 1 < kt_end; if (staged) issue_a(kt + 1, true, other + HALF); }
-    else if (ph == 1) { staged = kt + 1 < kt_end; if (staged) issue_b(kt + 1, true, other + HALF + QA); }
-    else if (ph == 2) { staged = kt + 2 < kt_end; if (staged) issue_a(kt + 2, false, buf); }
-    else              { staged = kt + 2 < kt_end; if (staged) issue_b(kt + 2, false, buf + QA); }
-    if (staged) wait_vmcnt<10>(); else wait_vmcnt<0>();
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- M segment ----
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[nh][i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i][ks], bfr[j][ks], acc[nh][i][j], 0, 0, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();
-    __builtin_amdgcn_sched_barrier(0);
-  };
-  using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
-  using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
-
-  if (wr == 1) __builtin_amdgcn_s_barrier();        // group 1 runs one barrier interval behind group 0
-  {
-    int kt = kt_begin;
-    for (; kt + 2 <= kt_end; kt += 2) {
-      phase(I0{}, I0{}, kt); phase(I0{}, I1{}, kt); phase(I0{}, I2{}, kt); phase(I0{}, I3{}, kt);
-      phase(I1{}, I0{}, kt + 1); phase(I1{}, I1{}, kt + 1); phase(I1{}, I2{}, kt + 1); phase(I1{}, I3{}, kt + 1);
-    }
-    if (kt < kt_end) { phase(I0{}, I0{}, kt); phase(I0{}, I1{}, kt); phase(I0{}, I2{}, kt); phase(I0{}, I3{}, kt); }
-  }
-  if (wr == 0) __builtin_amdgcn_s_barrier();
-  __syncthreads();   // every fragment read and every DMA is done before the epilogue reuses the LDS
-  write_tile<64, 64, 2, 2>(p, acc[0], wave_stage<64, 64>(smem, wave), lane, m0 + wr * 256 + wc * 64, n0);
-  __syncthreads();
-  write_tile<64, 64, 2, 2>(p, acc[1], wave_stage<64, 64>(smem, wave), lane, m0 + wr * 256 + wc * 64, n0 + 64);
-}
-
-#endif  // E4T_EXPERIMENTAL
 
 #ifdef PP_TRACE
 }  // namespace
@@ -1495,13 +1237,11 @@ enum : unsigned {
   CAP_COLSTATS = 1u << 2,    // its bf16 single-pass epilogue produces column statistics
   CAP_SPLITK = 1u << 3,      // accepts split-K (grid.z)
   CAP_WHOLE_K = 1u << 4,     // needs whole 64-wide K-tiles (of each source of a two-source A)
-  CAP_ONE_A = 1u << 5,       // no two-source A
-  CAP_WHOLE_N = 1u << 6,     // needs N % tn == 0 (ragged N is only exercised for the narrower tiles)
-  CAP_TAIL = 1u << 7,        // carries gemm_tail() (plan_gemm_tail)
-  CAP_PANELS = 1u << 8,      // carries row panels
-  CAP_ONE_PER_CU = 1u << 9,  // one 512-thread workgroup per CU: the "ping-pong" split-K rule
-  CAP_PERSISTENT = 1u << 10, // launched through e4t_launch_gemm_ps (gemm_ps.hip): at most one workgroup per CU walks all tiles
-  CAP_GEGLU = 1u << 11,      // carries the fused GEGLU epilogues (Variant::geglu; E4T_EPI_GEGLU / E4T_EPI_GEGLU_BWD)
+  CAP_WHOLE_N = 1u << 5,     // needs N % tn == 0 (ragged N is only exercised for the narrower tiles)
+  CAP_TAIL = 1u << 6,        // carries gemm_tail() (plan_gemm_tail)
+  CAP_PANELS = 1u << 7,      // carries row panels
+  CAP_ONE_PER_CU = 1u << 8,  // one 512-thread workgroup per CU: the "ping-pong" split-K rule
+  CAP_GEGLU = 1u << 9,       // carries the fused GEGLU epilogues (Variant::geglu; E4T_EPI_GEGLU / E4T_EPI_GEGLU_BWD)
   CAP_DMA = CAP_BUF | CAP_COLSTATS | CAP_SPLITK,
 };
 // A conv launch of the row goes to a strip-staged kernel instead when ok(p, splitk, batch) holds at launch time.
@@ -1510,36 +1250,9 @@ struct Variant {
   int tile, kt, stages, tm, tn;      // the public tile code is `tile`, 1000 * stages + tile for 3 / 4 stages of a CAP_STAGED tile, 5000 + tile for kt == 32
   unsigned caps;
   KernelEntry gemm[2], conv[2], conv_cm[2];      // [GENERAL]; conv_cm: channel-major K order as a template argument (else a run-time flag)
-  StripAlt alt[2];
+  StripAlt alt;
   KernelEntry geglu[2];      // [EPI_GEGLU - 1], [EPI_GEGLU_BWD - 1]: dense GEMM with the GEGLU in the store phase (CAP_GEGLU)
 };
-
-// ---- hooks of the measured-and-rejected variants (csrc/build.sh: E4T_EXPERIMENTAL=1); the product build answers "no" -----------------
-#ifdef E4T_EXPERIMENTAL
-#define XKERNEL(...) KERNEL(__VA_ARGS__)
-bool auto_256() { static const bool on = getenv("E4T_GEMM_AUTO256") != nullptr; return on; }      // measured: 128x128/2-stage >= 256x128/3-stage on every E4T shape
-bool auto_pt() { static const bool on = getenv("E4T_GEMM_PT") != nullptr; return on; }
-int auto_ps() { static const int on = getenv("E4T_GEMM_PS") ? atoi(getenv("E4T_GEMM_PS")) : E4T_GEMM_PS_DEFAULT; return on; }
-// measured and rejected (round 6): the 16-wave 256 x 256 strip kernel EQUALS the ping-pong kernel on every conv shape of the step (1072 / 1007 /
-// 526 / 254 / 126 us against 1046-1082 / 995-1011 / 515-531 / 253 / 125-128) although it fills a third of the A bytes — with 64 x 64 wave tiles
-// it needs one fragment ds_read per MFMA, 125 B/clk/CU of LDS reads at the MFMA peak against the LDS's 128
-bool strip256_ok(const GemmArgs& p, int splitk, int batch) {
-  static const bool on = getenv("E4T_CONV_STRIP256") != nullptr && atoi(getenv("E4T_CONV_STRIP256")) != 0;
-  return on && conv_strip_ok(p, splitk, batch);
-}
-int launch_persistent(GemmArgs& p, const Variant& v, bool conv, bool general, hipStream_t st) {
-  static const bool ps_pre = getenv("E4T_PS_PRE") == nullptr || atoi(getenv("E4T_PS_PRE")) != 0;      // A/B switch
-  p.ps_pre = ps_pre && p.fast_epi && cdiv(p.K, BK) >= 2 && (!p.rowbias || p.rows_per_batch % 256 == 0);
-  return e4t_launch_gemm_ps(&p, conv ? 1 : 0, v.tn, general ? 1 : 0, device_cu_count(), st);
-}
-#else
-#define XKERNEL(...) NO_KERNEL
-bool auto_256() { return false; }
-bool auto_pt() { return false; }
-int auto_ps() { return 0; }
-bool strip256_ok(const GemmArgs&, int, int) { return false; }
-int launch_persistent(GemmArgs&, const Variant&, bool, bool, hipStream_t) { E4T_FAIL(-22, "gemm: the persistent kernels are not built"); }
-#endif
 
 // ---- the variant table.  How to add a variant: (1) write its kernel above, signature void(GemmArgs); (2) add ONE row here — tile code, tile shape, what it can
 // do, its instantiations; (3) add the rule that chooses it to choose_tile() with the measurement that justifies it.  Everything else
@@ -1553,8 +1266,6 @@ int launch_persistent(GemmArgs&, const Variant&, bool, bool, hipStream_t) { E4T_
 #define DMA_GEGLU(nt, bm, bn, wgm, wgn, st, kt) {KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 1), KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 2)}
 #define DMA_GEGLU_F(nt, bm, bn, wgm, wgn, st, kt) {KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 1), NO_KERNEL}
 #define DMA_GEGLU_B(nt, bm, bn, wgm, wgn, st, kt) {NO_KERNEL, KERNEL(nt, gemm_dma_geglu_kernel, bm, bn, wgm, wgn, st, kt, 2)}
-#define PS_TEXT(mode, bn, general) {nullptr, "gemm_ps_kernel<" #mode ", " #bn ", " #general ">", 512}
-#define PS_FN(bn) {PS_TEXT(0, bn, false), PS_TEXT(0, bn, true)}, {PS_TEXT(1, bn, false), PS_TEXT(1, bn, true)}
 #define REG_FN(bm, bn, mode) {{&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}, {&gemm_kernel<bm, bn, 2, 2, mode>, "gemm_kernel", 256}}
 static const Variant kVariants[] = {
     // 64 / 128 / 160 tiles: 2 LDS stages and 2 workgroups per CU by default; 3 or 4 stages (one workgroup per CU, 2-3 K-tiles in flight)
@@ -1574,15 +1285,14 @@ static const Variant kVariants[] = {
     {160, 64, 3, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL | CAP_GEGLU, DMA_FN(256, 128, 160, 4, 1, 3, 64), {}, {}, DMA_GEGLU_B(256, 128, 160, 4, 1, 3, 64)},
     {160, 64, 4, 128, 160, CAP_DMA | CAP_STAGED | CAP_TAIL, DMA_FN(256, 128, 160, 4, 1, 4, 64)},
     // 5256: 256 x 128 with 32-wide K-tiles, 3 x 24 KiB stages = two workgroups per CU; stride-1 convs on conv_strip_kernel where it applies
-    {256, 32, 3, 256, 128, CAP_DMA | CAP_GEGLU, DMA_FN(512, 256, 128, 4, 2, 3, 32), {}, {{conv_strip_ok, {KERNEL(512, conv_strip_kernel, 2), NO_KERNEL}}},
+    {256, 32, 3, 256, 128, CAP_DMA | CAP_GEGLU, DMA_FN(512, 256, 128, 4, 2, 3, 32), {}, {conv_strip_ok, {KERNEL(512, conv_strip_kernel, 2), NO_KERNEL}},
      DMA_GEGLU(512, 256, 128, 4, 2, 3, 32)},
     // 512: 256 x 256 ping-pong; stride-1 convs on gemm_pps_kernel where it applies
     {512, 64, 2, 256, 256, CAP_DMA | CAP_WHOLE_K | CAP_TAIL | CAP_ONE_PER_CU,
      {KERNEL(512, gemm_pp_kernel, 0, false, false), KERNEL(512, gemm_pp_kernel, 0, true, false)},
      {KERNEL(512, gemm_pp_kernel, 1, false, false), KERNEL(512, gemm_pp_kernel, 1, true, false)},
      {KERNEL(512, gemm_pp_kernel, 1, false, true), KERNEL(512, gemm_pp_kernel, 1, true, true)},
-     {{conv_pps_ok, {KERNEL(512, gemm_pps_kernel, false), KERNEL(512, gemm_pps_kernel, true)}},
-      {strip256_ok, {XKERNEL(1024, conv_strip_kernel, 4), NO_KERNEL}}}},
+     {conv_pps_ok, {KERNEL(512, gemm_pps_kernel, false), KERNEL(512, gemm_pps_kernel, true)}}},
     // 2320: 256 x 320 ping-pong (the GENERAL instantiation exists for GEMMs only)
     {2320, 64, 2, 256, 320, CAP_DMA | CAP_WHOLE_K | CAP_WHOLE_N | CAP_TAIL | CAP_PANELS | CAP_ONE_PER_CU | CAP_GEGLU,
      {KERNEL(512, gemm_pq_kernel, 0, 320, false), KERNEL(512, gemm_pq_kernel, 0, 320, true)}, {KERNEL(512, gemm_pq_kernel, 1, 320, false), NO_KERNEL},
@@ -1590,20 +1300,9 @@ static const Variant kVariants[] = {
     // the register-staged fallback (operands beyond 4 GB, E4T_GEMM_REGSTAGE), logged as bare "gemm_kernel", GENERAL at run time
     {128, 64, 2, 128, 128, CAP_SPLITK, REG_FN(128, 128, 0), REG_FN(128, 128, 1)},
     {64, 64, 2, 64, 64, CAP_SPLITK, REG_FN(64, 64, 0), REG_FN(64, 64, 1)},
-#ifdef E4T_EXPERIMENTAL
-    // measured and rejected: 32-wide K-tiles on the 64 / 128 tiles (5064 / 5128), the 64-wide 256 x 128 tile (256), the 512 x 128 ping-pong
-    // tile (640), the persistent streaming kernels (1128 / 1160).  Those are instantiated in gemm_ps.hip, out of KERNEL()'s reach: their
-    // entries have no pointer, launch_persistent() hands e4t_launch_gemm_ps the (mode, tn, GENERAL) triple that PS_FN spells into the text.
-    {64, 32, 4, 64, 64, CAP_DMA, DMA_FN(256, 64, 64, 2, 2, 4, 32)},
-    {128, 32, 4, 128, 128, CAP_DMA, DMA_FN(512, 128, 128, 4, 2, 4, 32)},
-    {256, 64, 2, 256, 128, CAP_DMA, DMA_FN(512, 256, 128, 4, 2, 3, 64)},
-    {640, 64, 2, 512, 128, CAP_DMA | CAP_WHOLE_K | CAP_ONE_A, {KERNEL(512, gemm_pt_kernel, 0), NO_KERNEL}, {KERNEL(512, gemm_pt_kernel, 1), NO_KERNEL}},
-    {1128, 64, 2, 256, 128, CAP_BUF | CAP_COLSTATS | CAP_WHOLE_K | CAP_PERSISTENT, PS_FN(128)},
-    {1160, 64, 2, 256, 160, CAP_BUF | CAP_COLSTATS | CAP_WHOLE_K | CAP_PERSISTENT, PS_FN(160)},
-#endif
 };
 // The row of (tile, K-tile width, stages) — stages select only among CAP_STAGED rows — among the LDS-DMA rows or (!dma) the register-staged
-// ones; nullptr if this build carries none.
+// ones; nullptr if there is none.
 const Variant* find_variant(int tile, bool kt32, int stages, bool dma = true) {
   for (const Variant& v : kVariants)
     if (!(v.caps & CAP_BUF) == !dma && v.tile == tile && v.kt == (kt32 ? 32 : 64) && (!(v.caps & CAP_STAGED) || v.stages == stages)) return &v;
@@ -1612,16 +1311,9 @@ const Variant* find_variant(int tile, bool kt32, int stages, bool dma = true) {
 const KernelEntry& kernel_of(const Variant& v, bool conv, bool general) { return (conv ? v.conv : v.gemm)[general]; }
 // The ONE place that turns a planned row into a kernel entry: launch and launch log both ask it.
 const KernelEntry& select_entry(const Variant& v, const GemmArgs& p, bool conv, bool general, int splitk, int batch) {
-  if (conv)
-    for (const StripAlt& a : v.alt)
-      if (a.ok && a.k[general].text && a.ok(p, splitk, batch)) return a.k[general];
+  if (conv && v.alt.ok && v.alt.k[general].text && v.alt.ok(p, splitk, batch)) return v.alt.k[general];
   if (conv && p.chan_major && v.conv_cm[general].text) return v.conv_cm[general];
   return kernel_of(v, conv, general);
-}
-
-// The persistent 256 x BN kernel (gemm_ps.hip) pays when its one-workgroup-per-CU rounds are (nearly) full.
-bool ps_rounds_ok(long long units, int ncu) {
-  return units >= ncu && units * 100 >= cdivl(units, ncu) * ncu * 85;
 }
 
 // ---- cost model of one launch of the 64 x 64 / 128 x 128 / 128 x 160 DMA tiles (round 4) ---------------------------------------------
@@ -1687,7 +1379,7 @@ struct Planner : GemmPlan {
   const GemmArgs& p;
   const bool conv;
   const int splitk_req, batch, nkt;
-  const bool whole_k, ps_ok, dma;      // ps_ok: what gemm_ps_kernel accepts; dma: no E4T_GEMM_REGSTAGE
+  const bool whole_k, dma;             // dma: no E4T_GEMM_REGSTAGE
   int model_splitk;                    // > 0: split-K chosen together with the tile by small_grid_plan
   bool decode_hint(int hint);      // the four stages, in the order plan_gemm() runs them
   void choose_tile();
@@ -1702,24 +1394,23 @@ struct Planner : GemmPlan {
 };
 
 // --- stage 1: a tile hint -> (tile, stages, K-tile width).  64 | 128 | 160 (128 x 160) | 512 (256 x 256 ping-pong) | 2320 (256 x 320
-// ping-pong); 3000 / 4000 + tile: 3 / 4 LDS stages of the 64 / 128 / 160 tiles; 5000 + tile: 32-wide K-tiles.  Anything else (0): automatic.
-// The product library carries the tiles the planner chooses (64 / 128 / 160 with 2 - 4 LDS stages, 5256, 512, 2320) and nothing else: the
-// measured-and-rejected variants (5064 / 5128, 256, 640, 1128 / 1160: see their rows) are built only with -DE4T_EXPERIMENTAL.  A hint whose
-// row is absent gets the nearest product tile: a stage / K-tile prefix the tile has no row for is dropped, then `substitute` applies.
+// ping-pong); 3000 / 4000 + tile: 3 / 4 LDS stages of the 64 / 128 / 160 tiles; 5256: 256 x 128 with 32-wide K-tiles.  Anything else (0): automatic.
+// The codes of the variants that were measured, rejected and removed stay valid as aliases of the tile that answered them while
+// their kernels were kept out of the library: 256 (64-wide 256 x 128), 640 (512 x 128 ping-pong), 1128 / 1160 (persistent streaming kernels),
+// 5064 / 5128 (32-wide K-tiles on the 64 / 128 tiles) — and so do the stage / K-tile prefixes on a tile that never had such a row.
 bool Planner::decode_hint(int hint) {      // false: the hint names no tile
-  static const struct { int tile, product, stages; bool kt32; } substitute[] = {{256, 256, 3, true}, {640, 128, 2, false}, {1128, 128, 2, false}, {1160, 160, 2, false}};
+  static const struct { int hint, alias; } aliases[] = {
+      {256, 5256}, {640, 128}, {1128, 128}, {1160, 160}, {5064, 64}, {5128, 128},                           // the retired codes
+      {3256, 5256}, {4256, 5256}, {3640, 128}, {4640, 128}, {5640, 128}, {5160, 160}, {5512, 512}};        // a prefix on a tile without such a row
+  for (const auto& a : aliases)
+    if (hint == a.hint) { hint = a.alias; break; }
   tile = hint; stages = 2; kt32 = false;
   if (hint >= 3000 && hint < 5000) { stages = hint / 1000; tile = hint % 1000; }
   else if (hint >= 5000 && hint < 6000) { kt32 = true; stages = 4; tile = hint % 1000; }
   const Variant* v = find_variant(tile, kt32, stages);
-  if (!v) {
-    stages = 2; kt32 = false;
-    v = find_variant(tile, false, 2);
-    for (const auto& s : substitute)
-      if (!v && s.tile == tile) { tile = s.product; stages = s.stages; kt32 = s.kt32; v = find_variant(tile, kt32, stages); }
-  }
-  if (v && !(v->caps & CAP_STAGED)) stages = v->stages;
-  return v != nullptr;
+  if (!v) { stages = 2; kt32 = false; return false; }      // choose_tile() starts from the defaults
+  if (!(v->caps & CAP_STAGED)) stages = v->stages;
+  return true;
 }
 
 // --- stage 2: the automatic choice — the measured rules decide WHETHER one of the big tiles runs, then the cost model arbitrates the 64 / 128 /
@@ -1727,10 +1418,9 @@ bool Planner::decode_hint(int hint) {      // false: the hint names no tile
 void Planner::choose_tile() {
   // fill >= ~1.5 waves of the 256 CUs with 128x128 tiles, else drop to 64x64.  Measured on MI355X (tools/sweep_small.py): 128x128 wins
   // from one full round of the 256 CUs, and already from a quarter round when K is long (3x3 convs at the 16x16 / 8x8 levels) if
-  // split-K fills the chip
-  const long long t256 = (long long)cdiv(p.M, 256) * cdiv(p.N, 128) * batch;
+  // split-K fills the chip.  (A 64-wide 256 x 128 tile never beat the 2-stage 128 x 128 tile on an E4T shape: DESIGN §2.1.)
   const long long t128 = (long long)cdiv(p.M, 128) * cdiv(p.N, 128) * batch;
-  tile = (dma && auto_256() && t256 >= 256) ? 256 : (t128 >= 256 || (nkt >= 32 && t128 >= 64)) ? 128 : 64;
+  tile = (t128 >= 256 || (nkt >= 32 && t128 >= 64)) ? 128 : 64;
   // every channel count of the SD UNets is a multiple of 160 but 320 / 640 / 960 are not multiples of 128: a 128x160
   // tile has no N padding there (conv 640->640 @32x32: 863 vs 589 TF)
   if (dma && tile == 128 && p.N % 160 == 0 && p.N <= 960 && (long long)cdiv(p.M, 128) * (p.N / 160) * batch >= 128) tile = 160;
@@ -1746,12 +1436,7 @@ void Planner::choose_tile() {
   // one (nearly) full round of ping-pong tiles, K >= 1280: the ViT's qkv projection M4112 N3840 (255 tiles) 44.9 vs 49.5 us,
   // M4096 N3840 42.7 vs 48.3 us
   if (dma && tile == 128 && p.N % 256 == 0 && whole_k && nkt >= 20 && tpp >= 224 && tpp <= 256) tile = 512;
-  // The 512 x 128 variant of the same machine (tile code 640) is NOT chosen automatically: on the shapes it was built for
-  // (the VAE's 128-channel convs, K = 1152 = 18 K-tiles) it measured 526 vs 588 TF/s for the 128 x 128 tile — one 160-KiB
-  // workgroup per CU leaves nothing to overlap its (large) epilogue and prologue with, and 18 K-tiles do not amortise
-  // them (tools/ab_pt.py).  E4T_GEMM_PT=1 turns the automatic choice on for experiments.
-  if (auto_pt() && dma && tile == 128 && p.N % 128 == 0 && p.N % 256 != 0 && p.K % BK == 0 && nkt >= 16 && !p.A2 &&
-      (long long)cdiv(p.M, 512) * (p.N / 128) * batch >= 512) tile = 640;
+  // (a 512 x 128 variant of the same machine lost to the 128 x 128 tile on the shapes it was built for, 526 vs 588 TF/s: DESIGN §2.1)
   // Round 3 (tools/sweep_ps.py on the step's own shapes, cold operands):
   //  * the 128 x 160 tile also for N > 960 when K is deep and the grid is large — conv 640->1920 M16384 350 vs 378 us, conv
   //    1280->1280 M16384 454 vs 482 (ping-pong) / 492 (128 x 128), GEMM M4096 N5120 K1280 60 vs 64 us; on short K it loses
@@ -1779,15 +1464,7 @@ void Planner::choose_tile() {
       tile = 2320; kt32 = false; stages = 2;
     }
   }
-  // The persistent 256 x 160 / 256 x 128 streaming kernel (gemm_ps.hip).  NOT chosen automatically: correct, but slower than the
-  // tiles above on every shape of the step (its ping-pong phases are bound by the DMA-issue / fragment-read segment).
-  // E4T_GEMM_PS=1 turns the automatic choice on for experiments.
-  if (auto_ps() && ps_ok && (tile == 128 || tile == 160)) {
-    const int ncu = device_cu_count();
-    const long long rows = cdiv(p.M, 256);
-    if (p.N % 160 == 0 && ps_rounds_ok(rows * (p.N / 160), ncu)) tile = 1160;
-    else if ((p.N % 128 == 0 || p.N < 128) && ps_rounds_ok(rows * cdiv(p.N, 128), ncu)) tile = 1128;
-  }
+  // (persistent 256 x 160 / 256 x 128 streaming kernels were slower than the tiles above on every shape of the step: DESIGN §2.1)
   // Round 4: the 64 / 128 / 160 tiles, their LDS depth and split-K are arbitrated by a cost model of the launch (small_grid_plan above)
   // instead of the rules that chose among them until round 3; the rules above still decide WHETHER one of the big tiles runs.
   // (The round-3 rules instead of the cost model: C5 B = 1 44.4 vs 39.8 ms, profiles/r04_ab/r04s_*.)
@@ -1802,7 +1479,7 @@ void Planner::choose_tile() {
 void Planner::apply_capabilities() {
   auto narrower = [&](const Variant* v) { return v && v->tn % 160 == 0 && p.N % 160 == 0 ? 160 : 128; };
   // epilogues with the exact GELU or a per-row row-bias lookup run the GENERAL instantiation, built for the 2-stage 64 / 128 / 160 tiles (and
-  // the 3-stage 64 tile), the 256 x 256 / 256 x 320 (GEMM only) ping-pong kernels and the persistent kernels; no 32-wide-K kernel has it
+  // the 3-stage 64 tile), the 256 x 256 / 256 x 320 (GEMM only) ping-pong kernels; no 32-wide-K kernel has it
   if (general_epi) {
     kt32 = false;
     const Variant* v = find_variant(tile, false, stages);
@@ -1811,11 +1488,8 @@ void Planner::apply_capabilities() {
   }
   const Variant* v = row();
   auto fall = [&](int t) { tile = t; v = row(); };
-  // E4T_GEMM_REGSTAGE: only the tiles the register-staged kernel is built for.  PRESERVED OVERSIGHT: a persistent hint is exempt, the next
-  // rule may give it the 128 x 160 tile, which has no register-staged row: plan_gemm() then runs the 64 x 64 kernel on a 128 x 160 grid.
-  if (!dma && !(v->caps & CAP_PERSISTENT) && !find_variant(tile, false, 2, false)) fall(128);
-  if ((v->caps & CAP_PERSISTENT) && !ps_ok) fall(narrower(v));
-  if ((v->caps & CAP_ONE_A) && p.A2) fall(128);
+  // E4T_GEMM_REGSTAGE: only the tiles the register-staged kernel is built for
+  if (!dma && !find_variant(tile, false, 2, false)) fall(128);
   // row panels: the row that carries them, where the problem meets its other needs
   if (p.panel_rows && !(v->caps & CAP_PANELS))
     for (const Variant& w : kVariants)
@@ -1869,12 +1543,12 @@ int Planner::choose_splitk() const {
 
 GemmPlan plan_gemm(const GemmArgs& p, bool conv, int tile_hint, int splitk_req, int batch) {
   const bool whole_k = p.K % BK == 0 && (!p.A2 || p.K1 % BK == 0), dma = dma_allowed();
-  Planner s = {{}, p, conv, splitk_req, batch, cdiv(p.K, BK), whole_k, dma && whole_k && batch == 1 && !p.reduce_batch && splitk_req <= 1, dma, 0};
+  Planner s = {{}, p, conv, splitk_req, batch, cdiv(p.K, BK), whole_k, dma, 0};
   s.general_epi = (p.flags & E4T_ACT_GELU) || (p.rowbias && p.rows_per_batch % 32 != 0);
   if (!s.decode_hint(tile_hint)) s.choose_tile();
   s.apply_capabilities();
   s.shape = s.row();
-  // the register-staged row of the tile; PRESERVED OVERSIGHT (see apply_capabilities): a tile without one runs the 64 x 64 row
+  // the register-staged row of the tile (E4T_GEMM_REGSTAGE with row panels keeps the 256 x 320 tile, which has none: the 64 x 64 row, refused at launch)
   const Variant* reg = find_variant(s.tile, false, 2, false);
   s.run = dma && s.buf_ok ? s.shape : reg ? reg : find_variant(64, false, 2, false);
   s.gx = cdiv(p.N, s.shape->tn); s.gy = cdiv(p.M, s.shape->tm);
@@ -2015,8 +1689,7 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
   }
   if (p.panel_rows && !((v.caps & CAP_PANELS) && splitk == 1 && !p.ws))
     E4T_FAIL(-22, "gemm: row panels need the 256 x 320 ping-pong tile (N %% 320 == 0, K %% 64 == 0, no split-K); the plan chose tile %d", pl.tile);
-  if (!(v.caps & CAP_PERSISTENT)) hipLaunchKernelGGL(k.fn, dim3(pl.gx, pl.gy, splitk * batch), dim3(k.threads), 0, st, p);
-  else if (const int rc = launch_persistent(p, v, conv, pl.general_epi, st); rc < 0) return rc;
+  hipLaunchKernelGGL(k.fn, dim3(pl.gx, pl.gy, splitk * batch), dim3(k.threads), 0, st, p);
   E4T_CHECK_LAUNCH("gemm_kernel");
   if (const int rc = p.ws ? launch_splitk_reduce(p, nz, p.reduce_batch ? 1 : batch, vec8, st) : 0; rc < 0) return rc;
   return stats_written;

@@ -1,5 +1,5 @@
-// Pieces shared by the GEMM translation units (gemm.hip, gemm_ps.hip): argument block, fused epilogue, LDS-DMA helpers,
-// XCD-aware tile raster.  Everything lives in an anonymous namespace: each translation unit gets its own copy.
+// Pieces of gemm.hip that its kernels share: argument block, fused epilogue, LDS-DMA helpers, XCD-aware tile raster.
+// Everything but the argument block lives in an anonymous namespace.
 #pragma once
 #include "common.h"
 #include "../../include/e4t_hip.h"
@@ -36,7 +36,8 @@ struct GemmArgs {
   int reduce_batch; // partials of all (batch, split) pairs are summed into ONE C
   int fast_epi;     // bf16 C, 16-byte aligned rows: LDS-staged vectorised epilogue
   int fast_f32;     // fp32 C (+ fp32 residual), no accumulate, no row bias: direct line-wide stores from the accumulator layout
-  int ps_pre;       // persistent kernel: bias / row bias prefetched into LDS by DMA (write_tile<..., PRE>)
+  int ps_pre;       // unused (always 0) since the persistent kernels left.  Kept because dropping it moves every later field and regroups the scalar
+                    // loads of all kernels: it goes with the next change to this block, which then carries its own measurement
   int chan_major;   // stride-1 3x3 conv: K walked channel-chunk-major (cm_step) instead of tap-major
   int xcd3;         // TN kernel with split-K: workgroups re-dealt over (split, tile) so one XCD owns whole K-slices (xcd_tile3)
   // Row panels (gemm_pq_kernel only): logical row r of A / C / residual lives at physical row (r / panel_rows) * panel_stride + panel_off +
@@ -104,11 +105,6 @@ __device__ __forceinline__ bf16_t* wave_stage(bf16_t* smem, int wave) { return s
 // 32).  It is a separate INSTANTIATION, not a branch: inlined next to the plain path its erff expansion over 16 x FM x FN
 // elements set the register allocation of the whole kernel (288 instead of 208 registers in the 128 x 160 tile = one
 // workgroup per CU instead of two).  The launcher picks the variant (launch_gemm).
-// PRE (persistent kernel, gemm_ps.hip): bias and row bias of the tile's columns were brought into LDS ahead of time (pre_bias /
-// pre_rb point at the entry of column nw; one row-bias row per tile) and the staging barrier is a raw s_barrier: no global load
-// and no compiler-placed vmcnt(0) sits between the K loop and the staging writes, so the operand DMA of the NEXT tile, in flight
-// at this point, is not drained in front of the epilogue (vmcnt is an in-order counter: waiting for a load issued here means
-// waiting for every DMA issued before it).
 // EPI (fast bf16 path only; the launcher admits nothing else): the staging is the plain one — bf16(acc * alpha + bias), so the fused results
 // are bitwise those of the plain GEMM followed by the standalone GEGLU kernel (same helper, common.h) — and the STORE phase differs:
 //   EPI_GEGLU      (nw = wave-tile origin in the tile raster of width 2H; value columns nw/2 .., see geglu_col): per row, the staged value
@@ -116,9 +112,9 @@ __device__ __forceinline__ bf16_t* wave_stage(bf16_t* smem, int wave) { return s
 //                  values after the accumulators are dead, to aux[:, nw/2 ..];
 //   EPI_GEGLU_BWD  (N = H; the staged tile is dh, which is never stored): per 16-byte chunk of dh at column j the chunks of u = aux at j and
 //                  H + j are loaded (unconditionally, RB at a time, like the residual) and du[:, j], du[:, H + j] are written to C.
-template <int WM, int WN, int FM, int FN, bool GENERAL = false, bool PRE = false, int EPI = EPI_PLAIN>
+template <int WM, int WN, int FM, int FN, bool GENERAL = false, int EPI = EPI_PLAIN>
 __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][FN], bf16_t* stage, int lane, int mw, int nw,
-                                           unsigned long long* dt_ptr = nullptr, const float* pre_bias = nullptr, const float* pre_rb = nullptr) {
+                                           unsigned long long* dt_ptr = nullptr) {
   const int frow = lane & 31, fhi = lane >> 5;
   // ---- epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ----
   const bool partial = p.ws != nullptr;
@@ -135,31 +131,21 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
     // (85 in the 128 x 160 conv tile), one per 16-byte residual chunk (10) — in the epilogue of EVERY workgroup (ISA, round 2).
     float bv[FN], rbv[FM][FN];
     const bool rb_blocked = p.rowbias && (p.rows_per_batch % 32 == 0);        // a 32-row fragment lies inside one batch entry
-    if constexpr (PRE) {
 #pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        bv[j] = pre_bias[j * 32 + frow];
-        const float rb = pre_rb[j * 32 + frow];
+    for (int j = 0; j < FN; ++j) {
+      const int col = min(EPI == EPI_GEGLU ? geglu_col<WN>(nw, j * 32 + frow, p.N) : nw + j * 32 + frow, p.N - 1);
+      bv[j] = p.bias ? p.bias[col] : 0.f;
 #pragma unroll
-        for (int i = 0; i < FM; ++i) rbv[i][j] = rb;
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < FN; ++j) {
-        const int col = min(EPI == EPI_GEGLU ? geglu_col<WN>(nw, j * 32 + frow, p.N) : nw + j * 32 + frow, p.N - 1);
-        bv[j] = p.bias ? p.bias[col] : 0.f;
-#pragma unroll
-        for (int i = 0; i < FM; ++i) {
-          const int row = min(mw + i * 32, p.M - 1);
-          rbv[i][j] = rb_blocked ? p.rowbias[(size_t)(row / p.rows_per_batch) * p.ldrb + col] : 0.f;
-        }
+      for (int i = 0; i < FM; ++i) {
+        const int row = min(mw + i * 32, p.M - 1);
+        rbv[i][j] = rb_blocked ? p.rowbias[(size_t)(row / p.rows_per_batch) * p.ldrb + col] : 0.f;
       }
     }
     WT_STAMP(13);
     // The uniform special cases (GELU epilogue, per-row row-bias lookup) are decided ONCE, outside the 16 x FM x FN element loop: as
     // per-element `if`s they were two scalar branches per element — the staging of a 32 x 160 wave tile took 8300 of the
     // workgroup's 32000 cycles on the K = 320 projections (cycle stamps, tools/dma_trace.sh), 1400 without them.
-    const bool rb_slow = !PRE && p.rowbias && !rb_blocked;
+    const bool rb_slow = p.rowbias && !rb_blocked;
     if constexpr (!GENERAL) {
 #pragma unroll
       for (int i = 0; i < FM; ++i)
@@ -200,8 +186,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
     }
     WT_STAMP(14);
     // (a wave only reads back its own region; the barrier orders the LDS traffic)
-    if constexpr (PRE) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
-    else __syncthreads();
+    __syncthreads();
     WT_STAMP(15);
     if constexpr (EPI == EPI_GEGLU) {
       static_assert(WN % 16 == 0, "value / gate halves of whole 16-byte chunks");
@@ -273,15 +258,13 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
     // residual chunks are fetched RB at a time ahead of their use (all loads of a batch back to back); RB = 4 keeps the 128 x 160
     // kernel at 2 waves per SIMD (10 chunks in flight at once cost 40 VGPRs and one of the two resident workgroups per CU)
     constexpr int RB = NIT < 4 ? NIT : 4;
-    // RES: a residual is added.  PRE splits the two cases into separate bodies (a uniform branch): in ONE body the compiler waits
-    // for the conditional residual loads unconditionally (vmcnt(0) at the join) and the residual-free GEMMs would drain the next
-    // tile's DMA in front of their first C store.
-    auto store_rows = [&](auto RESc) {
-      constexpr bool RES = decltype(RESc)::value;
+    // (a lambda called once, not a plain block: written inline the same statements schedule differently in 45 of the 59 kernels; it
+    // becomes a block with the next change to this epilogue that carries its own measurement)
+    auto store_rows = [&] {
 #pragma unroll
       for (int it0 = 0; it0 < NIT; it0 += RB) {
         uint4 rres[RB];
-        if (RES && Rb) {
+        if (Rb) {
 #pragma unroll
           for (int u = 0; u < RB; ++u) {
             const int idx = min((it0 + u) * 64 + lane, WM * CPR - 1);
@@ -299,7 +282,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
           const int row = mw + rl, col = nw + cch * 8;
           if (idx < WM * CPR && row < p.M && col < p.N) {
             uint4 v = *(const uint4*)(stage + rl * ELD + cch * 8);
-            if (RES && Rb) {
+            if (Rb) {
               float a[8], b[8];
               unpack8(v, a);
               unpack8(rres[u], b);
@@ -313,12 +296,7 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
         }
       }
     };
-    if constexpr (PRE) {
-      if (Rb) store_rows(std::true_type{});
-      else store_rows(std::false_type{});
-    } else {
-      store_rows(std::true_type{});
-    }
+    store_rows();
     if (p.colstats) {
       // Per-column (sum, sum of squares) of this wave's output rows, one record per 32-row block: the GroupNorm that consumes
       // this tensor reduces these few floats instead of re-reading the whole activation (norm.hip, gn_finalize_cols_kernel).

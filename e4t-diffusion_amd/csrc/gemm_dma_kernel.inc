@@ -276,17 +276,17 @@
   __syncthreads();   // all fragment reads done before the epilogue reuses the LDS
   DT(11);
 #ifdef DMA_TRACE
-  write_tile<WM, WN, FM, FN, GENERAL, false, EPI>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN, dt_on ? g_dma_trace + dt_wg * 16 : nullptr);
+  write_tile<WM, WN, FM, FN, GENERAL, EPI>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN, dt_on ? g_dma_trace + dt_wg * 16 : nullptr);
 #else
   if constexpr (NW * WM * (WN + 8) > NSTAGE * TILE || WM >= 128) {
     // tall wave tiles (the 4-wave 256-row variants): two row halves, so that the staging fits the operand buffers and the
     // (fully unrolled) epilogue stays at the size of the other kernels'
     static_assert(FM % 2 == 0 && NW * (WM / 2) * (WN + 8) <= NSTAGE * TILE, "epilogue staging must fit");
-    write_tile<WM / 2, WN, FM / 2, FN, GENERAL, false, EPI>(p, *(f32x16(*)[FM / 2][FN])(acc + 0), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
+    write_tile<WM / 2, WN, FM / 2, FN, GENERAL, EPI>(p, *(f32x16(*)[FM / 2][FN])(acc + 0), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
     __syncthreads();
-    write_tile<WM / 2, WN, FM / 2, FN, GENERAL, false, EPI>(p, *(f32x16(*)[FM / 2][FN])(acc + FM / 2), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM + WM / 2, n0 + wn * WN);
+    write_tile<WM / 2, WN, FM / 2, FN, GENERAL, EPI>(p, *(f32x16(*)[FM / 2][FN])(acc + FM / 2), wave_stage<WM / 2, WN>(smem, wave), lane, m0 + wm * WM + WM / 2, n0 + wn * WN);
   } else {
-    write_tile<WM, WN, FM, FN, GENERAL, false, EPI>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
+    write_tile<WM, WN, FM, FN, GENERAL, EPI>(p, acc, wave_stage<WM, WN>(smem, wave), lane, m0 + wm * WM, n0 + wn * WN);
   }
   // tail rows: only in the 128 x 160 instantiations (and the ping-pong kernels), which have the registers for its 16 loads in flight — inlined
   // into the 64 / 128 / 256 x 128 tiles it cost them an occupancy step (92 -> 162 VGPRs on the 128 x 128 tile); the planner knows (plan_gemm_tail)

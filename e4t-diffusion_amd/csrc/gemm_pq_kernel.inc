@@ -257,7 +257,7 @@
   // through HBM cost ~55 us per tile in the first version of this kernel)
   auto slice = [&](auto Ic) {
     constexpr int i = decltype(Ic)::value;
-    write_tile<32, WN, 1, FN, GENERAL, false, EPI>(p, *(f32x16(*)[1][FN])(&acc[i][0]), wave_stage<32, WN>(smem, wave), lane, m0 + wr * WM + i * 32, n0 + wc * WN);
+    write_tile<32, WN, 1, FN, GENERAL, EPI>(p, *(f32x16(*)[1][FN])(&acc[i][0]), wave_stage<32, WN>(smem, wave), lane, m0 + wr * WM + i * 32, n0 + wc * WN);
   };
   slice(I0{});
   __syncthreads();

@@ -60,7 +60,6 @@ class WODesc(C.Structure):
 # (tests/test_abi.py checks the header against this table and against the built library).
 SIGNATURES = {
     "e4t_version": (i32, []),
-    "e4t_build_flags": (i32, []),
     "e4t_last_error": (C.c_char_p, []),
     "e4t_device_info": (i32, [C.c_char_p, i32, C.POINTER(i32)]),
     "e4t_set_launch_log": (i32, [C.c_char_p]),

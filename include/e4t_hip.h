@@ -27,10 +27,6 @@ extern "C" {
 typedef void* e4t_stream; /* hipStream_t */
 
 int e4t_version(void);
-/* bit set of how the library was built: E4T_BUILD_EXPERIMENTAL = the measured-and-rejected GEMM tile variants (codes 3xxx / 4xxx, 5064,
- * 5128, 256 with 64-wide K-tiles, 640, 1128 / 1160) are compiled in; the default build answers 0 and maps those codes to product tiles */
-#define E4T_BUILD_EXPERIMENTAL 1
-int e4t_build_flags(void);
 const char* e4t_last_error(void);
 /* device sanity: returns 0 and fills arch name (e.g. "gfx950"), CU count */
 int e4t_device_info(char* arch, int arch_len, int* cu_count);
@@ -76,13 +72,13 @@ typedef struct {
   int lda, lda2, ldb, ldc, ldr;
   int rows_per_batch;
   int flags;
-  int tile;            /* 0 = auto; 64, 128, 160 (= 128x160), 256 (= 256x128), 512 (= 256x256 ping-pong), 640 (= 512x128),
-                          1128 / 1160 (= persistent streaming 256x128 / 256x160, gemm_ps.hip; needs K % 64 == 0, batch 1, no split-K);
-                          + 3000 / 4000 forces 3 / 4 LDS stages on the 64 / 128 / 160 tiles (e.g. 3128); 5064 / 5128 / 5256 = the 64 / 128 /
-                          256x128 tiles with 32-wide K-tiles (5256: three 24-KiB stages, two workgroups per CU — the automatic choice
-                          for tall outputs with N % 128 == 0); 2320 = 256x320 ping-pong with k-step phases (gemm_pq_kernel: N % 320 == 0,
-                          K % 64 == 0, plain bias / row-bias / residual epilogue — the automatic choice where its rounds are full).
-                          An unsupported code for the shape falls back to the nearest tile that fits; e4t_gemm_plan reports the choice. */
+  int tile;            /* 0 = auto; 64, 128, 160 (= 128x160), 512 (= 256x256 ping-pong); + 3000 / 4000 forces 3 / 4 LDS stages on the
+                          64 / 128 / 160 tiles (e.g. 3128); 5256 = 256x128 with 32-wide K-tiles (three 24-KiB stages, two workgroups per
+                          CU — the automatic choice for tall outputs with N % 128 == 0); 2320 = 256x320 ping-pong with k-step phases
+                          (gemm_pq_kernel: N % 320 == 0, K % 64 == 0, plain bias / row-bias / residual epilogue — the automatic choice
+                          where its rounds are full).  The codes of removed variants are aliases: 256 = 5256, 640 = 128, 1128 = 128,
+                          1160 = 160, 5064 = 64, 5128 = 128.  A code the shape does not support falls back to the nearest tile that
+                          fits; e4t_gemm_plan reports the choice. */
   int splitk;          /* 0 = auto, >= 1 forced */
   int batch;           /* >= 1; operand base pointers advance by the strides below (elements) */
   long long strideA, strideB, strideC, strideBias;

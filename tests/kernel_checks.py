@@ -48,16 +48,6 @@ def check_probe(hip, emu, dev):
     return [("mfma32 row map", rel(rows, exp_rows), 0.0), ("mfma32 col map", rel(cols, exp_cols), 0.0)]
 
 
-def _product_tile(hip, code):
-    """False for the tile codes of the measured-and-rejected GEMM variants, which only an E4T_EXPERIMENTAL=1 build of the library
-    carries (32-wide-K 64 / 128 tiles, 512 x 128 ping-pong, persistent streaming kernels): the default library maps them to product
-    tiles, so checking them there would re-check those tiles under another label.  (The 3 / 4-stage 64 / 128 / 160 tiles are product
-    code since round 4: the planner picks them for grids under one round.)"""
-    if hip.lib.e4t_build_flags() & 1:
-        return True
-    return code not in (640, 1128, 1160, 5064, 5128)
-
-
 def check_gemm(hip, emu, dev):
     out = []
     cases = [  # M, N, K, tile, splitk
@@ -67,19 +57,12 @@ def check_gemm(hip, emu, dev):
         (512, 512, 512, 512, 1), (700, 520, 256, 512, 1), (300, 256, 64, 512, 1), (1000, 300, 128, 512, 1), (513, 1000, 1152, 512, 2),
         (2048, 1280, 1920, 512, 0), (257, 64, 192, 512, 1),
         (4096, 1280, 10240, 0, 0), (4096, 2560, 8192, 0, 0),       # auto: K-deep, 64-255 tiles of 256 x 256 -> ping-pong + split-K (3 | 1)
-        (1024, 128, 512, 640, 1), (700, 128, 1152, 640, 1), (1300, 384, 256, 640, 1), (513, 100, 64, 640, 1), (2048, 128, 2048, 640, 0), (4096, 128, 4096, 640, 3),
-        # persistent streaming tiles (gemm_ps.hip): 256 x 160 / 256 x 128; ragged M / N, one K-tile, several units per workgroup
-        (1000, 320, 320, 1160, 1), (513, 200, 128, 1128, 1), (4096, 640, 2560, 1160, 0), (70000, 320, 320, 1160, 1), (33000, 256, 192, 1128, 1),
-        (300, 480, 128, 1160, 1), (2048, 128, 64, 1128, 1), (256, 160, 64, 1160, 1), (66000, 100, 64, 1128, 1), (4112, 1280, 1280, 1160, 1),
-        (1000, 256, 328, 1128, 1),                                   # K % 64 != 0: falls back to the 128 x 128 tile
-        (900, 384, 512, 5256, 1), (5000, 640, 320, 5256, 1),         # experimental: 256 x 128, 32-wide K-tiles
+        (900, 384, 512, 5256, 1), (5000, 640, 320, 5256, 1),         # 256 x 128 with 32-wide K-tiles: ragged M, N one and a half / five column tiles
         # k-step-phased ping-pong tile (gemm_pq_kernel): 256 x 320 (wave tile 64 x 160); ragged M / N, one K-tile, split-K
         (1000, 320, 320, 2320, 1), (700, 640, 256, 2320, 1), (300, 200, 64, 2320, 1), (4096, 1280, 2560, 2320, 0), (513, 1000, 1152, 2320, 2),
         (65536, 320, 320, 2320, 1), (16384, 640, 640, 2320, 0),
     ]
     for i, (M, N, K, tile, sk) in enumerate(cases):
-        if not _product_tile(hip, tile):
-            continue
         g = gen(10 + i, dev)
         a, b = rnd(g, M, K, dev=dev), rnd(g, N, K, scale=K ** -0.5, dev=dev)
         bias = rnd(g, N, dtype=f32, dev=dev)
@@ -103,7 +86,7 @@ def check_gemm(hip, emu, dev):
     out.append(("gemm_tn into a column slice", rel(wide, wide2), TOLF * 50))
     # column statistics left by the epilogue for the consuming GroupNorm (all tile variants; with / without residual)
     for i, (M, N, K, tile) in enumerate([(256, 128, 128, 0), (4096, 320, 320, 160), (1024, 640, 1280, 128), (2048, 512, 2304, 512), (192, 72, 64, 64),
-                                         (4096, 320, 320, 1160), (8192, 256, 128, 1128), (66560, 640, 192, 1160), (34816, 128, 64, 1128),
+                                         (4096, 320, 320, 160), (8192, 256, 128, 128), (66560, 640, 192, 160), (34816, 128, 64, 128),      # more than 65536 rows, K = 192, one K-tile
                                          (4096, 320, 320, 2320), (8192, 640, 640, 2320)]):
         g = gen(60 + i, dev)
         a, b = rnd(g, M, K, dev=dev), rnd(g, N, K, scale=K ** -0.5, dev=dev)
@@ -122,7 +105,7 @@ def check_gemm(hip, emu, dev):
     out.append(("gemm gelu fp32-out t512", rel(hip.gemm(a1, b[:, :K1].contiguous(), gelu=True, out_dtype=f32, tile=512),
                                                 emu.gemm(a1, b[:, :K1].contiguous(), gelu=True, out_dtype=f32)), TOLF * 50))
     out.append(("gemm gelu", rel(hip.gemm(a1, b[:, :K1].contiguous(), gelu=True), emu.gemm(a1, b[:, :K1].contiguous(), gelu=True)), TOL1))
-    for t in [t for t in (3064, 512, 2320, 1128, 1160) if _product_tile(hip, t)]:      # the GENERAL epilogue instantiations of the 3-stage 64 tile, the ping-pong (/ persistent) kernels
+    for t in (3064, 512, 2320):      # the GENERAL epilogue instantiations of the 3-stage 64 tile and the ping-pong kernels
         out.append((f"gemm gelu t{t}", rel(hip.gemm(a1, b[:, :K1].contiguous(), gelu=True, tile=t), emu.gemm(a1, b[:, :K1].contiguous(), gelu=True)), TOL1))
         out.append((f"gemm two-source A t{t}", rel(hip.gemm(a1, b, a2=a2, tile=t), emu.gemm(a1, b, a2=a2)), TOL1))
     c0 = rnd(g, M, N, dtype=f32, dev=dev)
@@ -156,10 +139,8 @@ def check_gemm(hip, emu, dev):
             out.append((f"gemm {Mt}x{Nt}x{Kt} tail{r}: the last tile rows in front of the tail", rel(y[Mt - r - 64:Mt - r], yr[Mt - r - 64:Mt - r]), tol))
     # fp32 C + fp32 residual (the CLIP-ViT's fp32 residual stream): the line-wide direct-store epilogue, every kernel family
     gv = gen(33, dev)
-    for (Mv, Nv, Kv, t) in [(4112, 1280, 1280, 0), (4112, 1280, 5120, 0), (1000, 1280, 320, 160), (700, 512, 256, 512), (513, 200, 64, 64), (2048, 256, 128, 1128), (900, 384, 96, 5256),
+    for (Mv, Nv, Kv, t) in [(4112, 1280, 1280, 0), (4112, 1280, 5120, 0), (1000, 1280, 320, 160), (700, 512, 256, 512), (513, 200, 64, 64), (900, 384, 96, 5256),
                              (1000, 640, 320, 2320)]:
-        if not _product_tile(hip, t):
-            continue
         av, bw = rnd(gv, Mv, Kv, dev=dev), rnd(gv, Nv, Kv, scale=Kv ** -0.5, dev=dev)
         r32, bi = rnd(gv, Mv, Nv, dtype=f32, dev=dev), rnd(gv, Nv, dtype=f32, dev=dev)
         out.append((f"gemm {Mv}x{Nv}x{Kv} t{t} fp32 out + fp32 residual", rel(hip.gemm(av, bw, bias=bi, residual=r32, out_dtype=f32, tile=t),
@@ -188,10 +169,6 @@ def check_gemm(hip, emu, dev):
     rb = rnd(g, M // 96, N, dtype=f32, dev=dev)
     out.append(("gemm rowbias", rel(hip.gemm(a1, b[:, :K1].contiguous(), rowbias=rb, rows_per_batch=96),
                                     emu.gemm(a1, b[:, :K1].contiguous(), rowbias=rb, rows_per_batch=96)), TOL1))
-    for t in [t for t in (1128, 1160) if _product_tile(hip, t)]:
-        out.append((f"gemm rowbias t{t}", rel(hip.gemm(a1, b[:, :K1].contiguous(), rowbias=rb, rows_per_batch=96, tile=t),
-                                              emu.gemm(a1, b[:, :K1].contiguous(), rowbias=rb, rows_per_batch=96)), TOL1))
-        out.append((f"gemm strided A view t{t}", rel(hip.gemm(a1[:, 64:], b[:, :64].contiguous(), tile=t), emu.gemm(a1[:, 64:], b[:, :64].contiguous())), TOL1))
     # strided views (column slices of a wider buffer)
     wide = rnd(g, M, 3 * K1, dev=dev)
     out.append(("gemm strided A view", rel(hip.gemm(wide[:, K1:2 * K1], b[:, :K1].contiguous()), emu.gemm(wide[:, K1:2 * K1], b[:, :K1].contiguous())), TOL1))
@@ -218,14 +195,8 @@ def check_conv(hip, emu, dev):
         (3, 24, 24, 64, 320, CONV_S1, 24, 24, 512, 1), (2, 32, 32, 128, 256, CONV_S1, 32, 32, 512, 1), (2, 16, 16, 256, 512, CONV_S1, 16, 16, 512, 2),
         (3, 16, 16, 64, 128, CONV_S2, 8, 8, 512, 1), (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 512, 1), (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 512, 1),
         (1, 64, 64, 128, 128, 5, 32, 32, 512, 1),
-        (2, 32, 32, 128, 128, CONV_S1, 32, 32, 640, 1), (1, 48, 40, 64, 128, CONV_S1, 48, 40, 640, 1), (3, 16, 16, 128, 384, CONV_S1, 16, 16, 640, 2),
-        (1, 64, 64, 128, 128, 5, 32, 32, 640, 1), (2, 16, 16, 128, 128, CONV_UP2, 32, 32, 640, 1), (2, 32, 32, 128, 128, CONV_S2, 16, 16, 640, 1),
-        # persistent streaming tiles: every gather mode; B16 64x64 = 256 row panels x 2 column tiles = two units per workgroup
-        (4, 32, 32, 320, 320, CONV_S1, 32, 32, 1160, 1), (2, 64, 64, 128, 128, CONV_S1, 64, 64, 1128, 1), (16, 64, 64, 64, 320, CONV_S1, 64, 64, 1160, 1),
-        (3, 24, 24, 64, 192, CONV_S1, 24, 24, 1128, 1), (3, 16, 16, 64, 128, CONV_S2, 8, 8, 1128, 1), (2, 8, 8, 64, 160, CONV_UP2, 16, 16, 1160, 1),
-        (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 1128, 1), (1, 64, 64, 128, 128, 5, 32, 32, 1128, 1), (18, 64, 64, 128, 128, CONV_S1, 64, 64, 1128, 1),
         (2, 48, 40, 64, 320, CONV_S1, 48, 40, 5256, 1),
-        (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5256, 1), (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5128, 2), (1, 7, 9, 192, 64, CONV_S1, 7, 9, 5064, 1),   # channel-chunk-major K order with 32-wide chunks
+        (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5256, 1),   # channel-chunk-major K order with 32-wide chunks
         (4, 32, 32, 320, 320, CONV_S1, 32, 32, 2320, 1), (2, 16, 16, 256, 640, CONV_S1, 16, 16, 2320, 2), (2, 8, 8, 128, 320, CONV_S2T, 16, 16, 2320, 1),
         (3, 16, 16, 64, 320, CONV_S2, 8, 8, 2320, 1), (2, 8, 8, 64, 320, CONV_UP2, 16, 16, 2320, 1),
         (16, 64, 64, 64, 320, CONV_S1, 64, 64, 2320, 1),
@@ -238,8 +209,6 @@ def check_conv(hip, emu, dev):
         (2, 16, 16, 192, 256, CONV_S1, 16, 16, 512, 3), (3, 128, 128, 64, 128, CONV_S1, 128, 128, 512, 1),
     ]
     for i, (B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk) in enumerate(cases):
-        if not _product_tile(hip, tile):
-            continue
         g = gen(50 + i, dev)
         x = rnd(g, B * Hin * Win, Cin, dev=dev)
         w = rnd(g, Cout, 9 * Cin, scale=(9 * Cin) ** -0.5, dev=dev)
@@ -902,9 +871,7 @@ def check_gemm_races(hip, emu, dev):
         want = emu.gemm(a, w)
         ref = hip.gemm(a, w, tile=128)
         out.append((f"race-check reference {M}x{N}x{K}", rel(ref, want), TOL1))
-        for code in (64, 3064, 4064, 128, 3128, 4128, 160, 3160, 4160, 1128, 1160, 5256, 512, 2320):
-            if not _product_tile(hip, code):
-                continue
+        for code in (64, 3064, 4064, 128, 3128, 4128, 160, 3160, 4160, 5256, 512, 2320):
             if code % 1000 == 160 and N % 160:
                 continue
             if code == 512 and N % 256:
@@ -917,14 +884,12 @@ def check_gemm_races(hip, emu, dev):
             out.append((f"gemm {M}x{N}x{K} tile code {code}: launches (of 12) differing from the reference", float(differing), 0.0))
     x, w = rnd(g, 16 * 32 * 32, 640, dev=dev), rnd(g, 640, 9 * 640, dev=dev)
     ref = hip.conv3x3(x, w, 16, 32, 32, 32, 32, CONV_S1, tile=128)
-    for code in (128, 3128, 160, 4160, 64, 3064, 1128, 1160, 2320, 512, 5256):
-        if not _product_tile(hip, code):
-            continue
+    for code in (128, 3128, 160, 4160, 64, 3064, 2320, 512, 5256):
         sk = 1 if code in (2320, 512) else 0          # (its automatic split-K would change the summation order, not a race)
         run = lambda: hip.conv3x3(x, w, 16, 32, 32, 32, 32, CONV_S1, tile=code, splitk=sk)
-        # the persistent kernels walk K tap-major, every other DMA kernel channel-chunk-major (gemm_common.h, cm_step): a different
-        # fp32 summation order, so their bitwise reference is their own first launch (checked against `ref` to tolerance)
-        own = code in (1128, 1160, 5256)        # (5256: 32-wide channel chunks = another fp32 summation order than the 64-wide tiles)
+        # 5256 walks 32-wide channel chunks: another fp32 summation order than the 64-wide tiles, so its bitwise reference is its own first
+        # launch (checked against `ref` to tolerance)
+        own = code == 5256
         r = run() if own else ref
         if own:
             out.append((f"conv 32x32 640->640 tile code {code} vs the channel-major kernels", rel(r, ref), TOL2))

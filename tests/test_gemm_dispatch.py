@@ -54,15 +54,6 @@ def dumper():
     d.close()
 
 
-def _checked_groups(groups):
-    if _C.load().e4t_build_flags() == 0:
-        return sorted(groups)
-    # an E4T_EXPERIMENTAL=1 library answers the experimental tile codes with kernels the default build does not carry
-    skipped = {"%s t%d" % (k, t) for k in ("gemm", "conv") for t in dump.EXPERIMENTAL_HINTS}
-    print("experimental library: checking only the groups whose hint is a product code (not %s)" % sorted(skipped))
-    return sorted(set(groups) - skipped)
-
-
 def test_record_covers_the_corpus():
     groups, step, attn = _record()
     want = {"%s t%d" % (k, t) for k in ("gemm", "conv") for t in dump.HINTS} | {"tn", "attn"}
@@ -75,11 +66,40 @@ def test_record_covers_the_corpus():
 
 def test_plans_match_the_record(dumper):
     groups, _, _ = _record()
-    checked = _checked_groups(groups)
-    got, _ = dump.plan_digests(dumper, only_groups=set(checked))
-    bad = [g for g in checked if got.get(g) != groups[g]]
+    got, _ = dump.plan_digests(dumper)
+    bad = [g for g in sorted(groups) if got.get(g) != groups[g]]
     assert not bad, ("the planner decides differently for corpus group(s) %s: compare `python tools/gemm_dispatch_dump.py --plans --group '%s'` of this "
                      "library and of the one the record was made from (E4T_LIB=...), or re-record an intentional change with --record" % (bad, bad[0]))
+
+
+# the tile codes of the variants that were measured, rejected and removed -> the tile that answers them (gemm.hip, decode_hint)
+RETIRED_HINTS = {256: 5256, 640: 128, 1128: 128, 1160: 160, 5064: 64, 5128: 128}
+# a stage (3xxx / 4xxx) or K-tile (5xxx) prefix on a tile that never had such a row: accepted, and answered like this, as long as those codes existed
+PREFIXED_HINTS = {3256: 5256, 4256: 5256, 3640: 128, 4640: 128, 5640: 128, 5160: 160, 5512: 512}
+
+
+def test_retired_hints_plan_as_their_product_tile(dumper):
+    """a retired code is an alias: over its whole corpus group, GEMM and conv, the plan is that of the same descriptor with the alias as the hint"""
+    assert set(RETIRED_HINTS) <= set(dump.HINTS)
+    groups = {"%s t%d" % (k, t) for k in ("gemm", "conv") for t in RETIRED_HINTS}
+    n = 0
+    for item in dump.corpus():
+        if item.group in groups:
+            alias = dump.Item(item.group, item.kind, dict(item.kw, tile=RETIRED_HINTS[item.kw["tile"]]))
+            assert dumper.plan(item) == dumper.plan(alias), dump.describe(item.kw)
+            n += 1
+    assert n == sum(_record()[0][g][0] for g in groups)      # every line of the twelve groups
+    # the prefixed spellings are in no corpus group: the training step's GEMM / conv shapes and the first 500 descriptors of two groups
+    some = [it for it in dump.step_items() if it.kind != "tn"]
+    for g in ("gemm t0", "conv t0"):
+        some += [it for it, _ in zip((it for it in dump.corpus() if it.group == g), range(500))]
+    for hint, alias in PREFIXED_HINTS.items():
+        for item in some:
+            assert dumper.plan(dump.Item("x", item.kind, dict(item.kw, tile=hint))) == dumper.plan(dump.Item("x", item.kind, dict(item.kw, tile=alias))), (hint, dump.describe(item.kw))
+    # ... and none of them means "automatic" (what an unknown code gets) on a shape whose automatic tile is another one
+    auto = dump.Item("x", "gemm", dict(M=65536, N=320, K=1280))
+    assert dumper.plan(auto).split()[0] == "2320"
+    assert all(dumper.plan(dump.Item("x", "gemm", dict(auto.kw, tile=h))).split()[0] == str(a) for h, a in PREFIXED_HINTS.items())
 
 
 def test_step_shapes_get_the_recorded_plans(dumper):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Static resource report of every kernel of libe4t_hip.so (no GPU needed: hipcc cross-compiles): VGPRs / AGPRs / scratch bytes per
 # lane / occupancy / LDS per workgroup from -Rpass-analysis=kernel-resource-usage, plus the two ISA pathologies found in round 3,
-# (product build: gemm_ps.hip and the other E4T_EXPERIMENTAL variants are not part of it) counted per kernel from the assembly: scratch spills inside loops and "waterfall" loops around buffer_load ... lds (a scalar
+# counted per kernel from the assembly: scratch spills inside loops and "waterfall" loops around buffer_load ... lds (a scalar
 # offset the compiler could not prove uniform).  usage: tools/check_isa.sh [out]   (default profiles/rNN_isa_resources.txt)
 cd "$(dirname "$0")/../e4t-diffusion_amd/csrc"
 OUT=${1:-../../profiles/r04_isa_resources.txt}

@@ -43,8 +43,8 @@ STEP_CSV = os.path.join(R, "profiles", "r06_roofline_per_shape.csv")
 RECORD = os.path.join(R, "tests", "gemm_dispatch_record.txt")
 FAKE = 1 << 24                       # a non-NULL, 16-byte aligned "pointer": never dereferenced by host code
 OUT_F32, RES_F32, ACT_GELU, ACCUM, REDUCE_BATCH = 1, 2, 4, 8, 16
-HINTS = [0, 64, 128, 160, 256, 512, 640, 1128, 1160, 2320, 3064, 3128, 3160, 4064, 4128, 4160, 5064, 5128, 5256, 7]      # 7: not a tile code
-EXPERIMENTAL_HINTS = (256, 640, 1128, 1160, 5064, 5128)      # an E4T_EXPERIMENTAL=1 library answers these with other kernels
+# 256, 640, 1128, 1160, 5064, 5128: codes of removed variants, kept as aliases (gemm.hip, decode_hint); 7: not a tile code
+HINTS = [0, 64, 128, 160, 256, 512, 640, 1128, 1160, 2320, 3064, 3128, 3160, 4064, 4128, 4160, 5064, 5128, 5256, 7]
 Item = collections.namedtuple("Item", "group kind kw")
 
 
@@ -272,12 +272,10 @@ def gpu_visible(lib):
     return lib.e4t_device_info(None, 0, C.byref(n)) == 0
 
 
-def plan_digests(dumper, only_groups=None):
+def plan_digests(dumper):
     """{group: (lines, sha256 of the plan half)} in corpus order, and the plan lines of the 'step' group"""
     h, n, step = collections.OrderedDict(), collections.Counter(), []
     for item in corpus():
-        if only_groups is not None and item.group not in only_groups:
-            continue
         s = "%s %s -> %s" % (item.kind, describe(item.kw), dumper.plan(item))
         h.setdefault(item.group, hashlib.sha256()).update((s + "\n").encode())
         n[item.group] += 1
@@ -378,8 +376,6 @@ def main():
     d = Dumper(launches)
     try:
         if args.record:
-            if lib.e4t_build_flags() != 0:
-                sys.exit("--record is for the default build (e4t_build_flags() == 0)")
             write_record(d, RECORD)
             print("wrote", RECORD)
             return 0
@@ -394,7 +390,6 @@ def main():
             return 0
         if args.attn_check:
             return 1 if attn_check(d, args.attn_check) else 0
-        print("# build_flags %d %s" % (lib.e4t_build_flags(), " ".join("%s=%s" % (k, os.environ[k]) for k in sorted(os.environ) if k.startswith("E4T_") and k != "E4T_LIB")))
         for item in corpus():
             if args.group and item.group not in args.group:
                 continue

@@ -1,5 +1,6 @@
-"""GPU: the persistent 256 x BN streaming kernel (gemm_ps.hip, tile codes 1128 / 1160) against the tiles launch_gemm() picks
+"""GPU: every tile code (128, 160, 512, 5256, 2320; with and without an explicit single pass) against the tile launch_gemm() picks
 today, on the training step's own GEMM / conv shapes with cold operands (a pool larger than the Infinity Cache is cycled).
+(Written in round 3 for the persistent streaming kernels, codes 1128 / 1160, since removed: DESIGN.md §2.1.)
 Reads the shape strings of profiles/r02_roofline_per_shape.csv; prints one line per shape + a weighted total.
 usage: python tools/sweep_ps.py [csv] [top_n]"""
 import csv
@@ -48,7 +49,7 @@ for x in rows:
 todo = todo[:top]
 CODES = ((0, 0), (128, 0), (160, 0), (512, 0), (512, 1), (5256, 0), (2320, 0), (2320, 1))
 tot = {c: 0.0 for c in CODES}
-tot_best = tot_bestps = 0.0
+tot_best = 0.0
 for x in todo:
     shape, launches = x[1], int(x[2]) // 8
     m = re.match(r"gemm M(\d+) N(\d+) K(\d+) batch1 splitk(\d+) flags(\d+)", shape)
@@ -79,9 +80,7 @@ for x in todo:
             continue
         if tile == 512 and (N % 256 or K % 64):
             continue
-        if tile in (1128, 5256) and N % 128 and N > 128:
-            continue
-        if 1000 <= tile < 5000 and K % 64:
+        if tile == 5256 and N % 128 and N > 128:
             continue
         t = pool_time(make, lambda a: call(a, tile, sk), nbytes)
         if t is not None:

@@ -11,7 +11,6 @@ hip = ops.HipBackend()
 dev = torch.device("cuda:0")
 bf16 = torch.bfloat16
 r = lambda *s: (torch.randn(*s, device=dev) * 0.5).to(bf16)
-EXP = bool(hip.lib.e4t_build_flags() & 1)
 
 
 def pool_time(make, run, nbytes, iters=24):
@@ -56,7 +55,7 @@ for M, N, K in (only or shapes):
     for tile in (64, 128, 160, 5256, 512, 2320):
         if (tile == 160 and N % 160) or (tile == 512 and N % 256) or (tile == 2320 and N % 320) or (tile == 5256 and N % 128):
             continue
-        for st in ((2, 3, 4) + ((5,) if EXP else ())) if tile < 1000 else (2,):       # 5 = 32-wide K-tiles, 4 stages (experimental build only)
+        for st in (2, 3, 4) if tile < 1000 else (2,):
             code = tile if st == 2 else st * 1000 + tile
             for sk in (1, 2, 3, 4, 6, 8):
                 if sk > 1 and (nkt // sk < 2 or M * N * sk > 64e6):
