@@ -1633,14 +1633,11 @@ const char* geglu_refusal(const GemmPlan& pl, const GemmArgs& p, int tail, int b
         E4T_FAIL(E4T_ERR_NO_FUSED, "gemm: fused GEGLU M=%d N=%d K=%d not run (plan: tile %d, split-K %d): %s", p.M, p.N, p.K, pl.tile, pl.splitk, why); \
   } while (0)
 
-int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
-  int tail = 0;
-  const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
-  const Variant& v = *pl.run;
-  const int epi = conv ? EPI_PLAIN : epi_kind(p);
-  E4T_REFUSE_FUSED(pl, p, tail, batch);
-  const int m_all = p.M;                 // (launch log: the caller's shape)
-  if (tail) { p.M -= tail; p.tail_row0 = p.M; p.tail_rows = tail; }      // the tile grid covers [0, M - tail); gemm_tail() the rest
+// What a plan becomes at launch time, in ONE place that launch_gemm() and e4t_conv3x3_kernel() both call: the split-K that really runs (the
+// automatic choice falls back to one pass when the workspace is missing or short; an explicit one fails with -12), the K-tiles per split, the
+// operand extents, the channel-major K order of stride-1 convs and, from those, the kernel entry.  Fills these fields of p and dereferences
+// nothing.  Returns the split-K, or a negative error code with the message set.
+int resolve_launch(const GemmPlan& pl, GemmArgs& p, bool conv, int epi, size_t ws_bytes, int splitk_req, int batch, const KernelEntry*& entry) {
   int splitk = pl.splitk;
   p.ktiles_per_split = pl.ktiles_per_split;
   p.a_bytes = pl.a_bytes; p.a2_bytes = pl.a2_bytes; p.b_bytes = pl.b_bytes;
@@ -1658,6 +1655,24 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
   }
   if (!(splitk > 1 || p.reduce_batch)) p.ws = nullptr;
   p.splitk = splitk;
+  const KernelEntry& k = epi != EPI_PLAIN ? pl.run->geglu[epi - 1] : select_entry(*pl.run, p, conv, pl.general_epi, splitk, batch);
+  if (!k.text) E4T_FAIL(-22, "gemm: no kernel is built for tile %d (%s, GENERAL %d)", pl.tile, conv ? "conv" : "gemm", (int)pl.general_epi);
+  entry = &k;
+  return splitk;
+}
+
+int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
+  int tail = 0;
+  const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
+  const Variant& v = *pl.run;
+  const int epi = conv ? EPI_PLAIN : epi_kind(p);
+  E4T_REFUSE_FUSED(pl, p, tail, batch);
+  const int m_all = p.M;                 // (launch log: the caller's shape)
+  if (tail) { p.M -= tail; p.tail_row0 = p.M; p.tail_rows = tail; }      // the tile grid covers [0, M - tail); gemm_tail() the rest
+  const KernelEntry* entry = nullptr;
+  const int splitk = resolve_launch(pl, p, conv, epi, ws_bytes, splitk_req, batch, entry);
+  if (splitk < 0) return splitk;
+  const KernelEntry& k = *entry;
   p.group_m = 8;                           // row panels per raster group (swept in round 4: profiles/r04_ab/r04f_*)
   p.fast_epi = bf16_rows_aligned16(p) && p.strideC % 8 == 0;
   p.fast_f32 = (p.flags & E4T_OUT_F32) && !(p.flags & E4T_ACCUM) && !p.rowbias && (!p.residual || (p.flags & E4T_RES_F32)) &&
@@ -1669,8 +1684,6 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
                     (!p.bias || (((uintptr_t)p.bias & 15) == 0 && p.strideBias % 4 == 0)) &&
                     (!p.rowbias || (((uintptr_t)p.rowbias & 15) == 0 && p.ldrb % 4 == 0)) && ((uintptr_t)p.ws & 15) == 0;
   const int nz = p.reduce_batch ? splitk * batch : splitk;
-  const KernelEntry& k = epi != EPI_PLAIN ? v.geglu[epi - 1] : select_entry(v, p, conv, pl.general_epi, splitk, batch);
-  if (!k.text) E4T_FAIL(-22, "gemm: no kernel is built for tile %d (%s, GENERAL %d)", pl.tile, conv ? "conv" : "gemm", (int)pl.general_epi);
   if (e4t_launch_log_enabled()) {
     // algorithmic bytes: every operand element once (conv: the input map once, not once per tap), the output once
     const double osz = (p.flags & E4T_OUT_F32) ? 4.0 : 2.0;
@@ -1711,6 +1724,20 @@ void fill_gemm_args(const e4t_gemm_desc* d, GemmArgs& p) {
   p.colstats = d->colstats;
   p.panel_rows = d->panel_rows; p.panel_stride = d->panel_stride; p.panel_off = d->panel_off;
   p.aux = d->aux; p.ldaux = d->ldaux;
+}
+
+// the geometry a conv descriptor must have, for the launch and for the kernel query alike
+int check_conv_geometry(const e4t_conv_desc* d) {
+  const int Cin = d->Cin, Cout = d->Cout, Hin = d->Hin, Win = d->Win, Hout = d->Hout, Wout = d->Wout, mode = d->mode;
+  E4T_REQUIRE(Cin % BK == 0, "conv3x3: Cin=%d must be a multiple of 64 (pad the input channels)", Cin);
+  E4T_REQUIRE(mode >= E4T_CONV_S1 && mode <= E4T_CONV_S2A, "conv3x3: bad mode %d", mode);
+  E4T_REQUIRE(d->B > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && Cout > 0, "conv3x3: bad geometry");
+  if (mode == E4T_CONV_S1) E4T_REQUIRE(Hout == Hin && Wout == Win, "conv3x3 S1: output must equal input size");
+  if (mode == E4T_CONV_S2) E4T_REQUIRE(Hout == (Hin - 1) / 2 + 1 && Wout == (Win - 1) / 2 + 1, "conv3x3 S2: bad output size");
+  if (mode == E4T_CONV_UP2) E4T_REQUIRE(Hout == 2 * Hin && Wout == 2 * Win, "conv3x3 UP2: output must be 2x input");
+  if (mode == E4T_CONV_S2T) E4T_REQUIRE(Hin == (Hout - 1) / 2 + 1 && Win == (Wout - 1) / 2 + 1, "conv3x3 S2T: bad sizes");
+  if (mode == E4T_CONV_S2A) E4T_REQUIRE(Hout == (Hin - 2) / 2 + 1 && Wout == (Win - 2) / 2 + 1, "conv3x3 S2A: bad output size");
+  return 0;
 }
 
 void fill_conv_args(const e4t_conv_desc* d, GemmArgs& p) {
@@ -1848,16 +1875,23 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
 
 extern "C" int e4t_conv3x3(const e4t_conv_desc* d, e4t_stream stream) {
   E4T_REQUIRE(d && d->X && d->W && d->Y, "conv3x3: null operand");
-  const int Cin = d->Cin, Cout = d->Cout, Hin = d->Hin, Win = d->Win, Hout = d->Hout, Wout = d->Wout, mode = d->mode;
-  E4T_REQUIRE(Cin % BK == 0, "conv3x3: Cin=%d must be a multiple of 64 (pad the input channels)", Cin);
-  E4T_REQUIRE(mode >= E4T_CONV_S1 && mode <= E4T_CONV_S2A, "conv3x3: bad mode %d", mode);
-  E4T_REQUIRE(d->B > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0 && Cout > 0, "conv3x3: bad geometry");
-  if (mode == E4T_CONV_S1) E4T_REQUIRE(Hout == Hin && Wout == Win, "conv3x3 S1: output must equal input size");
-  if (mode == E4T_CONV_S2) E4T_REQUIRE(Hout == (Hin - 1) / 2 + 1 && Wout == (Win - 1) / 2 + 1, "conv3x3 S2: bad output size");
-  if (mode == E4T_CONV_UP2) E4T_REQUIRE(Hout == 2 * Hin && Wout == 2 * Win, "conv3x3 UP2: output must be 2x input");
-  if (mode == E4T_CONV_S2T) E4T_REQUIRE(Hin == (Hout - 1) / 2 + 1 && Win == (Wout - 1) / 2 + 1, "conv3x3 S2T: bad sizes");
-  if (mode == E4T_CONV_S2A) E4T_REQUIRE(Hout == (Hin - 2) / 2 + 1 && Wout == (Win - 2) / 2 + 1, "conv3x3 S2A: bad output size");
+  if (const int rc = check_conv_geometry(d); rc < 0) return rc;
   GemmArgs p;
   fill_conv_args(d, p);
   return launch_gemm(p, true, d->tile, d->workspace_bytes, d->splitk, 1, (hipStream_t)stream);
+}
+
+extern "C" int e4t_conv3x3_kernel(const e4t_conv_desc* d, const char** symbol, int* splitk) {
+  E4T_REQUIRE(d && symbol && splitk, "conv3x3_kernel: bad arguments");
+  if (const int rc = check_conv_geometry(d); rc < 0) return rc;
+  GemmArgs p;
+  fill_conv_args(d, p);
+  int tail = 0;
+  const GemmPlan pl = plan_gemm_tail(p, true, d->tile, d->splitk, 1, tail);
+  const KernelEntry* entry = nullptr;
+  const int sk = resolve_launch(pl, p, true, EPI_PLAIN, d->workspace_bytes, d->splitk, 1, entry);
+  if (sk < 0) return sk;
+  *symbol = entry->text;
+  *splitk = sk;
+  return 0;
 }

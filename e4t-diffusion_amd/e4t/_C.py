@@ -69,6 +69,7 @@ SIGNATURES = {
     "e4t_gemm_plan": (i32, [C.POINTER(GemmDesc), C.POINTER(GemmPlan)]),
     "e4t_gemm_tn_plan": (i32, [C.POINTER(GemmDesc), C.POINTER(GemmPlan)]),
     "e4t_conv3x3_plan": (i32, [C.POINTER(ConvDesc), C.POINTER(GemmPlan)]),
+    "e4t_conv3x3_kernel": (i32, [C.POINTER(ConvDesc), C.POINTER(C.c_char_p), C.POINTER(i32)]),
     "e4t_attention_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, f32, i32, vp]),
     "e4t_attention_bwd": (i32, [vp] * 10 + [i32] * 9 + [i64] * 4 + [f32, i32, vp]),
     "e4t_attention_bwd_workspace_floats": (sz, [i32] * 5),

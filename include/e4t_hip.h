@@ -152,6 +152,11 @@ typedef struct {
 int e4t_gemm_plan(const e4t_gemm_desc* d, e4t_gemm_plan_t* out);
 int e4t_gemm_tn_plan(const e4t_gemm_desc* d, e4t_gemm_plan_t* out);
 int e4t_conv3x3_plan(const e4t_conv_desc* d, e4t_gemm_plan_t* out);
+/* Which kernel e4t_conv3x3 will launch for a descriptor, WITHOUT launching: *symbol is the kernel's symbol text as the launch log spells it
+ * (a string owned by the library), *splitk the split-K that really runs with workspace / workspace_bytes as given, the automatic fall-back to
+ * one pass included (an explicit split-K without its workspace fails with -12, as the launch does).  Pure host code from the launcher's own
+ * decision; no pointer of the descriptor is dereferenced (NULL or not matters as for the plan; X, W, Y may be NULL). */
+int e4t_conv3x3_kernel(const e4t_conv_desc* d, const char** symbol, int* splitk);
 
 /* ---------------------------------------------------------------- attention (attention.hip) -- */
 /* O = softmax(Q K^T * scale) V ; Q/K/V/O are (B, T|S, heads*DH) bf16 matrices with row strides ld*

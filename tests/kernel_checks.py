@@ -8,7 +8,8 @@ bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumu
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
 
-Importable without a GPU: the attention case lists and slices() are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py).
+Importable without a GPU: the attention and conv case lists, slices() and conv_slices() are shared with CPU tests (test_gemm_dispatch.py,
+test_attention_slices_cpu.py, test_conv_slices_cpu.py).
 """
 from __future__ import annotations
 
@@ -184,40 +185,185 @@ def check_gemm(hip, emu, dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ 3x3 conv
+# Plain data, importable without a GPU: tests/test_gemm_dispatch.py pins the kernel symbol (and split-K) every case gets in every call form, and
+# holds the symbols x conv modes the cases reach against everything e4t_conv3x3_kernel can return; tests/test_conv_slices_cpu.py holds a
+# rounding-only model to half the tolerance on every row conv_slices() emits for them.
+CONV_S2A = 5
+# B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, splitk
+CONV_CASES = [
+    (2, 16, 16, 64, 64, CONV_S1, 16, 16, 0, 0), (2, 8, 8, 128, 192, CONV_S1, 8, 8, 64, 3),
+    (3, 16, 16, 64, 128, CONV_S2, 8, 8, 0, 0), (2, 9, 9, 64, 64, CONV_S2, 5, 5, 0, 0),
+    (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 0, 0), (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 0, 0),
+    (2, 5, 5, 64, 64, CONV_S2T, 9, 9, 0, 0), (4, 32, 32, 320, 320, CONV_S1, 32, 32, 128, 1),
+    (2, 16, 16, 64, 4, CONV_S1, 16, 16, 0, 0), (3, 24, 24, 64, 192, CONV_S1, 24, 24, 256, 1), (3, 24, 24, 64, 320, CONV_S1, 24, 24, 160, 1), (2, 16, 16, 128, 128, 5, 8, 8, 0, 0), (1, 64, 64, 128, 128, 5, 32, 32, 0, 0),
+    (3, 24, 24, 64, 320, CONV_S1, 24, 24, 512, 1), (2, 32, 32, 128, 256, CONV_S1, 32, 32, 512, 1), (2, 16, 16, 256, 512, CONV_S1, 16, 16, 512, 2),
+    (3, 16, 16, 64, 128, CONV_S2, 8, 8, 512, 1), (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 512, 1), (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 512, 1),
+    (1, 64, 64, 128, 128, 5, 32, 32, 512, 1),
+    (2, 48, 40, 64, 320, CONV_S1, 48, 40, 5256, 1),
+    (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5256, 1),   # channel-chunk-major K order with 32-wide chunks
+    (4, 32, 32, 320, 320, CONV_S1, 32, 32, 2320, 1), (2, 16, 16, 256, 640, CONV_S1, 16, 16, 2320, 2), (2, 8, 8, 128, 320, CONV_S2T, 16, 16, 2320, 1),
+    (3, 16, 16, 64, 320, CONV_S2, 8, 8, 2320, 1), (2, 8, 8, 64, 320, CONV_UP2, 16, 16, 2320, 1),
+    (16, 64, 64, 64, 320, CONV_S1, 64, 64, 2320, 1),
+    # round 6: conv_strip_kernel (stride 1, W % 256 == 0, the 256 x 128 x 32 tile): image borders in both directions, several 256-pixel
+    # segments per row, one-row images, Cout beyond one column tile, batch crossing
+    (2, 6, 256, 64, 128, CONV_S1, 6, 256, 5256, 1), (1, 3, 768, 192, 256, CONV_S1, 3, 768, 5256, 1), (3, 1, 256, 64, 128, CONV_S1, 1, 256, 5256, 1),
+    (2, 5, 512, 128, 128, CONV_S1, 5, 512, 0, 0),
+    # ... and gemm_pps_kernel (the ping-pong kernel on half-strips): whole-row tiles W = 16 / 64, row segments W = 256 / 512, split-K on kernel-row boundaries
+    (2, 64, 64, 64, 256, CONV_S1, 64, 64, 512, 1), (1, 4, 256, 128, 320, CONV_S1, 4, 256, 512, 1), (1, 2, 512, 64, 256, CONV_S1, 2, 512, 512, 1),
+    (2, 16, 16, 192, 256, CONV_S1, 16, 16, 512, 3), (3, 128, 128, 64, 128, CONV_S1, 128, 128, 512, 1),
+]
+
+
+def _reach_geometry(mode):
+    """input 9 x 9 where the mode allows odd sizes (5 x 5 for S2T, whose output is then 9 x 9): Hout * Wout % 32 != 0 in every mode, so that the
+    row bias of the full form takes the GENERAL epilogue where the tile has one; S2A drops the last input row and column"""
+    return {CONV_S1: (9, 9, 9, 9), CONV_S2: (9, 9, 5, 5), CONV_UP2: (9, 9, 18, 18), CONV_S2T: (5, 5, 9, 9), CONV_S2A: (9, 9, 4, 4)}[mode]
+
+
+# every tile code x conv mode (the mode is a run-time branch of the gather): B = 2, Cin = 64, Cout = the tile width + 8 where the tile takes a ragged N
+CONV_REACH_TILES = [(64, 72), (3064, 72), (4064, 72), (128, 136), (3128, 136), (4128, 136), (160, 168), (3160, 168), (4160, 168), (5256, 136), (512, 264), (2320, 320)]
+CONV_REACH_CASES = [(2, g[0], g[1], 64, cout, mode, g[2], g[3], tile, 1)
+                    for tile, cout in CONV_REACH_TILES for mode in (CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A) for g in [_reach_geometry(mode)]]
+# one-pixel-wide and one-pixel images (every pixel is several borders at once), odd sizes for S2A; B = 3: image boundaries in M sit inside a tile
+CONV_DEGENERATE_CASES = [
+    (3, 1, 1, 64, 64, CONV_S1, 1, 1, 0, 0), (3, 1, 7, 64, 64, CONV_S1, 1, 7, 0, 0), (3, 7, 1, 64, 64, CONV_S1, 7, 1, 0, 0), (3, 2, 2, 64, 64, CONV_S1, 2, 2, 0, 0),
+    (3, 1, 1, 64, 64, CONV_S2, 1, 1, 0, 0), (3, 2, 3, 64, 64, CONV_S2, 1, 2, 0, 0),
+    (3, 1, 1, 64, 64, CONV_UP2, 2, 2, 0, 0),
+    (3, 1, 1, 64, 64, CONV_S2T, 1, 1, 0, 0), (3, 2, 2, 64, 64, CONV_S2T, 3, 3, 0, 0),
+    (3, 9, 7, 64, 64, CONV_S2A, 4, 3, 0, 0), (3, 2, 2, 64, 64, CONV_S2A, 1, 1, 0, 0),
+]
+CONV_ALL_CASES = CONV_CASES + CONV_REACH_CASES + CONV_DEGENERATE_CASES      # check_conv runs these, each in the full and the bare form
+# The call forms: which optional operands are given (NULL or not is part of the plan) and the flags
+CONV_FORMS = {
+    "full": dict(bias=True, rowbias=True, residual=True),      # the ResBlock's first conv
+    "bare": dict(),                                            # the data-gradient convs: nothing in the epilogue
+    "colstats": dict(bias=True, colstats=True), "colstats+res": dict(bias=True, residual=True, colstats=True),
+    "f32 bias": dict(bias=True, f32=True), "f32 res32": dict(bias=True, residual=True, f32=True, res32=True), "f32 res16": dict(bias=True, residual=True, f32=True),
+    "accum16": dict(accum=True), "accum32": dict(accum=True, f32=True),
+    "rowbias slice": dict(rowbias=True),
+    "gelu": dict(bias=True, gelu=True),      # E4T_ACT_GELU: no conv of the model sets it, the ABI takes it (raw descriptor; the GENERAL epilogue)
+}
+# check_conv_forms: the smallest shape of every conv kernel family (M % 32 == 0 for the column statistics; 8 x 8 is no strip geometry, 16 x 16 is)
+CONV_FORM_CASES = {
+    "64": (2, 8, 8, 64, 64, CONV_S1, 8, 8, 64, 1), "128": (2, 8, 8, 64, 128, CONV_S1, 8, 8, 128, 1), "160": (2, 8, 8, 64, 160, CONV_S1, 8, 8, 160, 1),
+    "5256": (2, 8, 8, 64, 128, CONV_S1, 8, 8, 5256, 1), "5256 strip": (2, 16, 16, 64, 128, CONV_S1, 16, 16, 5256, 1),
+    "512": (2, 8, 8, 64, 256, CONV_S1, 8, 8, 512, 1), "512 pps": (2, 16, 16, 64, 256, CONV_S1, 16, 16, 512, 1),
+    "2320": (2, 8, 8, 64, 320, CONV_S1, 8, 8, 2320, 1),
+}
+CONV_GELU_FAMILIES = ("512", "512 pps")                                   # the GENERAL instantiations of the ping-pong kernels; nothing else reaches gemm_pps_kernel<true>
+CONV_FORM_SPLITK = 3                                                      # explicit split-K: the call reports the statistics NOT written
+CONV_OUT_CASES = [(2, 16, 16, 64, 4, CONV_S1, 16, 16, t, 0) for t in (0, 64, 128)]      # conv_out: bias only, fp32 output, Cout = 4
+# check_conv_guards: every conv kernel symbol, ragged M and (where the tile takes it) ragged Cout: the stride-1 cases (the channel-major gather, whose
+# buffer window starts in front of X) and the S2A ones (the kernels' other K order; the last input row and column are never read) of the reach list
+CONV_GUARD_CASES = [c for c in CONV_REACH_CASES if c[5] in (CONV_S1, CONV_S2A)] + [
+    (3, 16, 16, 64, 136, CONV_S1, 16, 16, 5256, 1),      # conv_strip_kernel (its geometries make M a multiple of 256): a ragged column tile
+    (2, 16, 16, 64, 264, CONV_S1, 16, 16, 512, 1),       # gemm_pps_kernel (wants M % 256 == 0): ragged Cout
+]
+
+
+def conv_tag(case):
+    B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+    return f"conv mode{mode} B{B} {Hin}x{Win} {Cin}->{Cout} t{tile} s{sk}"
+
+
+def conv_desc(case, form, splitk=None):
+    """the descriptor hip.conv3x3 hands the library for a case in a call form, with a pointer that is never dereferenced wherever one is given and
+    the workspace the plan asks for: for e4t_conv3x3_plan / e4t_conv3x3_kernel (pure host code)"""
+    from e4t import _C
+    B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+    f, fake = CONV_FORMS[form], 1 << 24
+    M = B * Hout * Wout
+    flags = (_C.OUT_F32 if f.get("f32") else 0) | (_C.RES_F32 if f.get("res32") else 0) | (_C.ACCUM if f.get("accum") else 0) | (_C.ACT_GELU if f.get("gelu") else 0)
+    ptr = lambda k: fake if f.get(k) else None
+    return _C.ConvDesc(X=fake, W=fake, Y=fake, bias=ptr("bias"), residual=ptr("residual"), rowbias=ptr("rowbias"), workspace=fake, workspace_bytes=1 << 40,
+                       B=B, Hin=Hin, Win=Win, Cin=Cin, Hout=Hout, Wout=Wout, Cout=Cout, mode=mode, flags=flags, tile=tile, splitk=sk if splitk is None else splitk,
+                       ldrb=1280 if form == "rowbias slice" else Cout if f.get("rowbias") else 0,
+                       colstats=fake if f.get("colstats") and not f.get("f32") and M % 32 == 0 else None)
+
+
+def conv_plan(case, form, splitk=None):
+    import ctypes
+    from e4t import _C
+    pl = _C.GemmPlan()
+    _C.check(_C.load().e4t_conv3x3_plan(ctypes.byref(conv_desc(case, form, splitk)), ctypes.byref(pl)), "e4t_conv3x3_plan")
+    return pl
+
+
+def conv_kernel(case, form, splitk=None):
+    """'<kernel symbol> splitk<n>' of the launch, from the library's own decision (e4t_conv3x3_kernel)"""
+    import ctypes
+    from e4t import _C
+    sym, sk = ctypes.c_char_p(), ctypes.c_int(0)
+    _C.check(_C.load().e4t_conv3x3_kernel(ctypes.byref(conv_desc(case, form, splitk)), ctypes.byref(sym), ctypes.byref(sk)), "e4t_conv3x3_kernel")
+    return "%s splitk%d" % (sym.value.decode(), sk.value)
+
+
+def conv_inputs(case, seed, dev):
+    """x, w, bias, row bias, residual of a case: unit-variance conv product, bias, row bias and residual"""
+    B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+    g = gen(seed, dev)
+    x = rnd(g, B * Hin * Win, Cin, dev=dev)
+    w = rnd(g, Cout, 9 * Cin, scale=(9 * Cin) ** -0.5, dev=dev)
+    bias = rnd(g, Cout, dtype=f32, dev=dev)
+    rb = rnd(g, B, Cout, dtype=f32, dev=dev)
+    res = rnd(g, B * Hout * Wout, Cout, dev=dev)
+    return x, w, bias, rb, res
+
+
+def conv_slices(tag, got, ref, B, Hout, Wout, plan, tol=TOL1):
+    """Result rows that a whole-tensor relative L2 dilutes: got, ref = [B * Hout * Wout, Cout].  The relative L2 of the top / bottom row, the left /
+    right column, the four corners together, the interior, the first / last image, the rows of the last, partial M-tile (M % plan.tile_m) and the
+    columns of the last, partial N-tile (Cout % plan.tile_n).  Empty regions, and a bottom row / right column / last image that is the top row / left
+    column / first image, are skipped.  The tolerance is the whole tensor's: the stated bound is per element, so it holds for any region
+    (tests/test_conv_slices_cpu.py holds a rounding-only model to half of it on every row emitted here, down to 32 values)."""
+    Cout = ref.shape[-1]
+    M = B * Hout * Wout
+    g, r = got.float().reshape(B, Hout, Wout, Cout), ref.float().reshape(B, Hout, Wout, Cout)
+    d2, r2 = (g - r) ** 2, r * r
+    out = []
+
+    def row(label, sel):
+        d, n = d2[sel], r2[sel]
+        if d.numel():
+            e = (d.sum() / (n.sum() + 1e-38)).sqrt()
+            out.append((f"{tag}: {label}", float(torch.nan_to_num(e, nan=float("inf"))), tol))
+    A = slice(None)
+    row("top row", (A, 0))
+    if Hout > 1:
+        row("bottom row", (A, Hout - 1))
+    row("left column", (A, A, 0))
+    if Wout > 1:
+        row("right column", (A, A, Wout - 1))
+    ys, xs = sorted({0, Hout - 1}), sorted({0, Wout - 1})
+    row("corners", (A, torch.tensor(ys)[:, None], torch.tensor(xs)[None, :]))
+    row("interior", (A, slice(1, Hout - 1), slice(1, Wout - 1)))
+    row("first image", (0,))
+    if B > 1:
+        row("last image", (B - 1,))
+    d2, r2 = d2.reshape(M, Cout), r2.reshape(M, Cout)
+    if M % plan.tile_m:
+        row(f"rows {M - M % plan.tile_m}-{M - 1} (the partial {plan.tile_m}-row tile)", (slice(M - M % plan.tile_m, M),))
+    if Cout % plan.tile_n:
+        row(f"columns {Cout - Cout % plan.tile_n}-{Cout - 1} (the partial {plan.tile_n}-column tile)", (A, slice(Cout - Cout % plan.tile_n, Cout)))
+    return out
+
+
 def check_conv(hip, emu, dev):
     out = []
-    cases = [  # B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, splitk
-        (2, 16, 16, 64, 64, CONV_S1, 16, 16, 0, 0), (2, 8, 8, 128, 192, CONV_S1, 8, 8, 64, 3),
-        (3, 16, 16, 64, 128, CONV_S2, 8, 8, 0, 0), (2, 9, 9, 64, 64, CONV_S2, 5, 5, 0, 0),
-        (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 0, 0), (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 0, 0),
-        (2, 5, 5, 64, 64, CONV_S2T, 9, 9, 0, 0), (4, 32, 32, 320, 320, CONV_S1, 32, 32, 128, 1),
-        (2, 16, 16, 64, 4, CONV_S1, 16, 16, 0, 0), (3, 24, 24, 64, 192, CONV_S1, 24, 24, 256, 1), (3, 24, 24, 64, 320, CONV_S1, 24, 24, 160, 1), (2, 16, 16, 128, 128, 5, 8, 8, 0, 0), (1, 64, 64, 128, 128, 5, 32, 32, 0, 0),
-        (3, 24, 24, 64, 320, CONV_S1, 24, 24, 512, 1), (2, 32, 32, 128, 256, CONV_S1, 32, 32, 512, 1), (2, 16, 16, 256, 512, CONV_S1, 16, 16, 512, 2),
-        (3, 16, 16, 64, 128, CONV_S2, 8, 8, 512, 1), (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 512, 1), (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 512, 1),
-        (1, 64, 64, 128, 128, 5, 32, 32, 512, 1),
-        (2, 48, 40, 64, 320, CONV_S1, 48, 40, 5256, 1),
-        (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5256, 1),   # channel-chunk-major K order with 32-wide chunks
-        (4, 32, 32, 320, 320, CONV_S1, 32, 32, 2320, 1), (2, 16, 16, 256, 640, CONV_S1, 16, 16, 2320, 2), (2, 8, 8, 128, 320, CONV_S2T, 16, 16, 2320, 1),
-        (3, 16, 16, 64, 320, CONV_S2, 8, 8, 2320, 1), (2, 8, 8, 64, 320, CONV_UP2, 16, 16, 2320, 1),
-        (16, 64, 64, 64, 320, CONV_S1, 64, 64, 2320, 1),
-        # round 6: conv_strip_kernel (stride 1, W % 256 == 0, the 256 x 128 x 32 tile): image borders in both directions, several 256-pixel
-        # segments per row, one-row images, Cout beyond one column tile, batch crossing
-        (2, 6, 256, 64, 128, CONV_S1, 6, 256, 5256, 1), (1, 3, 768, 192, 256, CONV_S1, 3, 768, 5256, 1), (3, 1, 256, 64, 128, CONV_S1, 1, 256, 5256, 1),
-        (2, 5, 512, 128, 128, CONV_S1, 5, 512, 0, 0),
-        # ... and gemm_pps_kernel (the ping-pong kernel on half-strips): whole-row tiles W = 16 / 64, row segments W = 256 / 512, split-K on kernel-row boundaries
-        (2, 64, 64, 64, 256, CONV_S1, 64, 64, 512, 1), (1, 4, 256, 128, 320, CONV_S1, 4, 256, 512, 1), (1, 2, 512, 64, 256, CONV_S1, 2, 512, 512, 1),
-        (2, 16, 16, 192, 256, CONV_S1, 16, 16, 512, 3), (3, 128, 128, 64, 128, CONV_S1, 128, 128, 512, 1),
-    ]
-    for i, (B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk) in enumerate(cases):
-        g = gen(50 + i, dev)
-        x = rnd(g, B * Hin * Win, Cin, dev=dev)
-        w = rnd(g, Cout, 9 * Cin, scale=(9 * Cin) ** -0.5, dev=dev)
-        bias = rnd(g, Cout, dtype=f32, dev=dev)
-        rb = rnd(g, B, Cout, dtype=f32, dev=dev)
-        res = rnd(g, B * Hout * Wout, Cout, dev=dev)
+    for i, case in enumerate(CONV_ALL_CASES):
+        B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+        x, w, bias, rb, res = conv_inputs(case, 50 + i, dev)
+        tag = conv_tag(case)
         y = hip.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode, bias=bias, rowbias=rb, residual=res, tile=tile, splitk=sk)
         yr = emu.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode, bias=bias, rowbias=rb, residual=res)
-        out.append((f"conv mode{mode} B{B} {Hin}x{Win} {Cin}->{Cout} t{tile} s{sk}", rel(y, yr), TOL1))
+        out.append((tag, rel(y, yr), TOL1))
+        out += conv_slices(tag, y, yr, B, Hout, Wout, conv_plan(case, "full"))
+        # bare: no bias, no row bias, no residual — the call form of the data-gradient convs, and the one in which nothing dilutes the conv product
+        y = hip.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode, tile=tile, splitk=sk)
+        yr = emu.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode)
+        out.append((tag + " bare", rel(y, yr), TOL1))
+        out += conv_slices(tag + " bare", y, yr, B, Hout, Wout, conv_plan(case, "bare"))
     # weight relayout + dgrad identity: conv dgrad == autograd of conv
     g = gen(70, dev)
     O, I = 96, 64
@@ -226,6 +372,111 @@ def check_conv(hip, emu, dev):
     wf2, wd2 = emu.conv_weight_prepare(w4)
     out.append(("conv_weight_prepare fwd layout", rel(wf, wf2), 0.0))
     out.append(("conv_weight_prepare dgrad layout", rel(wd, wd2), 0.0))
+    return out
+
+
+def check_conv_forms(hip, emu, dev):
+    """the call forms the model uses and check_conv does not: column statistics out of a conv (into the consuming GroupNorm), fp32 output, accumulate,
+    a row bias that is a column slice of a wider matrix — each on every conv kernel family (CONV_FORM_CASES)"""
+    import torch.nn.functional as F
+    out = []
+    for i, (fam, case) in enumerate(CONV_FORM_CASES.items()):
+        B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+        M, HW = B * Hout * Wout, Hout * Wout
+        x, w, bias, rb, res = conv_inputs(case, 300 + i, dev)
+        g = gen(320 + i, dev)
+        geo, kw = (x, w, B, Hin, Win, Hout, Wout, mode), dict(tile=tile, splitk=sk)
+        tag = f"conv family {fam} ({Hin}x{Win} {Cin}->{Cout})"
+        for form, r in (("colstats", None), ("colstats+res", res)):
+            y = hip.conv3x3(*geo, bias=bias, residual=r, colstats=True, **kw)
+            cs = getattr(y, "_e4t_colstats", None)
+            blk = y.float().reshape(M // 32, 32, Cout)
+            ref = torch.stack([blk.sum(1), (blk * blk).sum(1)], dim=-1)
+            out.append((f"{tag} {form}: reported written (1 = not)", float(cs is None), 0.0))
+            out.append((f"{tag} {form}: == the statistics of the kernel's own output", rel(cs, ref) if cs is not None else 1.0, 1e-5))
+            out.append((f"{tag} {form}: y", rel(y, emu.conv3x3(*geo, bias=bias, residual=r)), TOL1))
+        if cs is not None:      # the conv's statistics through the consuming GroupNorm == the same GroupNorm with its own statistics pass
+            gamma, beta = rnd(g, Cout, dtype=f32, dev=dev) * 0.3 + 1.0, rnd(g, Cout, dtype=f32, dev=dev) * 0.2
+            n1, st1 = hip.groupnorm_fwd(y, None, gamma, beta, B, HW, 32, 1e-5, True)
+            n2, st2 = hip.groupnorm_fwd(y.clone(), None, gamma, beta, B, HW, 32, 1e-5, True)      # (a clone carries no statistics)
+            out.append((f"{tag} colstats+res -> GroupNorm: y", rel(n1, n2), 2e-3))
+            out.append((f"{tag} colstats+res -> GroupNorm: stats", rel(st1, st2), 1e-4))
+        y = hip.conv3x3(*geo, bias=bias, colstats=True, tile=tile, splitk=CONV_FORM_SPLITK)
+        out.append((f"{tag} colstats, split-K {CONV_FORM_SPLITK}: reported written (0 = not)", float(hasattr(y, "_e4t_colstats")), 0.0))
+        out.append((f"{tag} colstats, split-K {CONV_FORM_SPLITK}: y", rel(y, emu.conv3x3(*geo, bias=bias)), TOL1))
+        res32 = rnd(g, M, Cout, dtype=f32, dev=dev)
+        for form, r in (("f32 bias", None), ("f32 res32", res32), ("f32 res16", res)):
+            y, yr = hip.conv3x3(*geo, bias=bias, residual=r, out_dtype=f32, **kw), emu.conv3x3(*geo, bias=bias, residual=r, out_dtype=f32)
+            out.append((f"{tag} {form}", rel(y, yr), TOLF * 50))
+            out += conv_slices(f"{tag} {form}", y, yr, B, Hout, Wout, conv_plan(case, form), tol=TOLF * 50)
+        for form, dt, tol in (("accum16", bf16, TOL1), ("accum32", f32, TOLF * 50)):
+            o1 = rnd(g, M, Cout, dtype=dt, dev=dev)
+            o2 = o1.clone()
+            hip.conv3x3(*geo, out=o1, accum=True, **kw); emu.conv3x3(*geo, out=o2, accum=True)
+            out.append((f"{tag} {form}", rel(o1, o2), tol))
+            out += conv_slices(f"{tag} {form}", o1, o2, B, Hout, Wout, conv_plan(case, form), tol=tol)
+        wide = rnd(g, B, 1280, dtype=f32, dev=dev)      # all ResBlocks' time-embedding projections in one matrix: this conv's is a column slice of it
+        rbs = wide[:, 320:320 + Cout]
+        y, yr = hip.conv3x3(*geo, rowbias=rbs, **kw), emu.conv3x3(*geo, rowbias=rbs)
+        out.append((f"{tag} row bias = columns 320-{320 + Cout - 1} of a [B][1280] matrix", rel(y, yr), TOL1))
+        out += conv_slices(f"{tag} row bias slice", y, yr, B, Hout, Wout, conv_plan(case, "rowbias slice"))
+    for i, fam in enumerate(CONV_GELU_FAMILIES):      # through the raw ABI: the descriptor of conv_desc() with the operands' addresses
+        import ctypes
+        from e4t import _C, ops
+        case = CONV_FORM_CASES[fam]
+        B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+        x, w, bias, _, _ = conv_inputs(case, 330 + i, dev)
+        y = torch.empty(B * Hout * Wout, Cout, dtype=bf16, device=dev)
+        d = conv_desc(case, "gelu")
+        d.X, d.W, d.Y, d.bias, d.workspace, d.workspace_bytes = x.data_ptr(), w.data_ptr(), y.data_ptr(), bias.data_ptr(), None, 0      # (one pass: sk = 1)
+        _C.check(hip.lib.e4t_conv3x3(ctypes.byref(d), ops._stream()), "e4t_conv3x3")
+        yr = emu._act(F.gelu(emu.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode, bias=bias, out_dtype=f32)))
+        out.append((f"conv family {fam} ({Hin}x{Win} {Cin}->{Cout}) gelu (raw ABI)", rel(y, yr), TOL1))
+        out += conv_slices(f"conv family {fam} gelu", y, yr, B, Hout, Wout, conv_plan(case, "gelu"))
+    for i, case in enumerate(CONV_OUT_CASES):      # conv_out: 4 output channels, bias only, fp32
+        B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+        x, w, bias, _, _ = conv_inputs(case, 340 + i, dev)
+        geo = (x, w, B, Hin, Win, Hout, Wout, mode)
+        y, yr = hip.conv3x3(*geo, bias=bias, out_dtype=f32, tile=tile, splitk=sk), emu.conv3x3(*geo, bias=bias, out_dtype=f32)
+        out.append((conv_tag(case) + " f32 bias (conv_out)", rel(y, yr), TOLF * 50))
+        out += conv_slices(conv_tag(case) + " f32 bias (conv_out)", y, yr, B, Hout, Wout, conv_plan(case, "f32 bias"), tol=TOLF * 50)
+    return out
+
+
+GUARD_ROWS_W, GUARD_ROWS_Y = 320, 256      # the widest column tile of weight rows behind Cout; the tallest row tile of sentinel rows around Y
+
+
+def guarded_conv_operands(x, w, M, Win):
+    """x, w and a bf16 y [M][Cout], each a view into ONE larger allocation, so that an out-of-range access of a wrong kernel lands in memory the test
+    owns: NaN for 2 * (Win + 1) * Cin elements in front of and behind x (the channel-major gather's buffer window starts (Win + 1) * Cin elements in
+    front of x: what lies there is read and must be masked), NaN weight rows behind Cout (a ragged column tile reads them), sentinel rows around y,
+    and y itself filled with the sentinel.  -> xg, wg, yg, the two y guards as int16 views"""
+    Cin, Cout = x.shape[-1], w.shape[0]
+    gx = 2 * (Win + 1) * Cin
+    xb = torch.full((gx + x.numel() + gx,), float("nan"), dtype=bf16, device=x.device)
+    xg = xb[gx:gx + x.numel()].view(x.shape)
+    xg.copy_(x)
+    wb = torch.full((Cout + GUARD_ROWS_W, w.shape[1]), float("nan"), dtype=bf16, device=x.device)
+    wb[:Cout].copy_(w)
+    yb = torch.full((GUARD_ROWS_Y + M + GUARD_ROWS_Y, Cout), SENT16, dtype=torch.int16, device=x.device)
+    return xg, wb[:Cout], yb[GUARD_ROWS_Y:GUARD_ROWS_Y + M].view(bf16), (yb[:GUARD_ROWS_Y], yb[GUARD_ROWS_Y + M:])
+
+
+def check_conv_guards(hip, emu, dev):
+    """every conv kernel symbol on operands with poison around them (CONV_GUARD_CASES: ragged M, ragged Cout where the tile takes it), bare and with
+    the full epilogue: bitwise the unguarded run, finite, no sentinel touched"""
+    out = []
+    for i, case in enumerate(CONV_GUARD_CASES):
+        B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, sk = case
+        x, w, bias, rb, res = conv_inputs(case, 400 + i, dev)
+        for form, epi in (("full", dict(bias=bias, rowbias=rb, residual=res)), ("bare", {})):
+            tag = f"{conv_tag(case)} {form}, guarded"
+            y0 = hip.conv3x3(x, w, B, Hin, Win, Hout, Wout, mode, tile=tile, splitk=sk, **epi)
+            xg, wg, yg, guards = guarded_conv_operands(x, w, B * Hout * Wout, Win)
+            hip.conv3x3(xg, wg, B, Hin, Win, Hout, Wout, mode, out=yg, tile=tile, splitk=sk, **epi)
+            out.append((f"{tag}: elements differing from the unguarded run", float((yg.view(torch.int16) != y0.view(torch.int16)).sum()), 0.0))
+            out.append((f"{tag}: non-finite elements", float((~torch.isfinite(yg.float())).sum()), 0.0))
+            out.append((f"{tag}: sentinel elements changed", float(sum((gd != SENT16).sum() for gd in guards)), 0.0))
     return out
 
 
@@ -914,6 +1165,8 @@ def all_checks(hip, emu, dev, ops_mod):
     yield "probe", lambda: check_probe(hip, emu, dev)
     yield "gemm", lambda: check_gemm(hip, emu, dev)
     yield "conv", lambda: check_conv(hip, emu, dev)
+    yield "conv_forms", lambda: check_conv_forms(hip, emu, dev)
+    yield "conv_guards", lambda: check_conv_guards(hip, emu, dev)
     yield "attention", lambda: check_attention(hip, emu, dev)
     yield "norms", lambda: check_norms(hip, emu, dev)
     yield "streaming", lambda: check_streaming(hip, emu, dev)

@@ -10,7 +10,11 @@ called here — pure host code, safe on any machine; the launch half of the tool
 
 The attention launchers (csrc/attention.hip: plan_fwd / plan_bwd, exported as e4t_attention_plan) are held to the same record: group `attn` hashes
 `shape ws -> forward | dQ | dK/dV kernel | tsplit tchunk | workspace_floats` over both sides of every dispatch threshold and four workspace sizes,
-and the step's attention shapes stand in clear text.  A slipped threshold passes every numeric check and only costs time; here it fails."""
+and the step's attention shapes stand in clear text.  A slipped threshold passes every numeric check and only costs time; here it fails.
+
+Which KERNEL a conv launch gets is decided after the plan (the strip predicates, the channel-major K order, the GENERAL epilogue, the automatic
+split-K fallback); e4t_conv3x3_kernel reports it from the launcher's own decision.  Every case of the conv checks stands here with its kernel symbol
+and split-K in clear text, and the symbols x conv modes the checks reach are held against everything the query returns over the corpus."""
 import ctypes as C
 import importlib.util
 import os
@@ -231,3 +235,239 @@ def test_check_attention_reaches_every_kernel_the_plan_can_name(dumper):
     assert pinned == reachable, (sorted(reachable - pinned), sorted(pinned - reachable))
     # a smaller workspace selects among the same kernels: nothing is reachable only that way
     assert {sym for kernels in CHECK_ATTENTION_WS_KERNELS.values() for sym in kernels[:3]} <= reachable
+
+
+# ---- 3x3 conv: case of tests/kernel_checks.py (B, Hin, Win, Cin, Cout, mode, Hout, Wout, tile, splitk) -> what e4t_conv3x3 launches for it, "<kernel
+# symbol> splitk<n>" as e4t_conv3x3_kernel reports it, in the full form (bias + row bias + residual) and the bare form (none of them).  The two differ
+# where Hout * Wout % 32 != 0: the row bias then needs the GENERAL epilogue, which the 3- and 4-stage 128 / 160 tiles, the 4-stage 64 tile, the
+# 32-wide-K tile and the 256 x 320 tile do not have (the plan answers with the 2-stage tile of that width).
+from kernel_checks import CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A  # noqa: E402
+
+CHECK_CONV_KERNELS = {
+    (2, 16, 16, 64, 64, CONV_S1, 16, 16, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 8, 8, 128, 192, CONV_S1, 8, 8, 64, 3): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk3", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk3"),
+    (3, 16, 16, 64, 128, CONV_S2, 8, 8, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 64, CONV_S2, 5, 5, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 5, 5, 64, 64, CONV_S2T, 9, 9, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (4, 32, 32, 320, 320, CONV_S1, 32, 32, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 16, 16, 64, 4, CONV_S1, 16, 16, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 24, 24, 64, 192, CONV_S1, 24, 24, 256, 1): ("gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (3, 24, 24, 64, 320, CONV_S1, 24, 24, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 16, 16, 128, 128, CONV_S2A, 8, 8, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (1, 64, 64, 128, 128, CONV_S2A, 32, 32, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 24, 24, 64, 320, CONV_S1, 24, 24, 512, 1): ("gemm_pp_kernel<1, false, true> splitk1", "gemm_pp_kernel<1, false, true> splitk1"),
+    (2, 32, 32, 128, 256, CONV_S1, 32, 32, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+    (2, 16, 16, 256, 512, CONV_S1, 16, 16, 512, 2): ("gemm_pps_kernel<false> splitk2", "gemm_pps_kernel<false> splitk2"),
+    (3, 16, 16, 64, 128, CONV_S2, 8, 8, 512, 1): ("gemm_pp_kernel<1, false, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 8, 8, 64, 64, CONV_UP2, 16, 16, 512, 1): ("gemm_pp_kernel<1, false, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 8, 8, 128, 64, CONV_S2T, 16, 16, 512, 1): ("gemm_pp_kernel<1, false, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (1, 64, 64, 128, 128, CONV_S2A, 32, 32, 512, 1): ("gemm_pp_kernel<1, false, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 48, 40, 64, 320, CONV_S1, 48, 40, 5256, 1): ("gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 20, 12, 192, 128, CONV_S1, 20, 12, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (4, 32, 32, 320, 320, CONV_S1, 32, 32, 2320, 1): ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 16, 16, 256, 640, CONV_S1, 16, 16, 2320, 2): ("gemm_pq_kernel<1, 320, false> splitk2", "gemm_pq_kernel<1, 320, false> splitk2"),
+    (2, 8, 8, 128, 320, CONV_S2T, 16, 16, 2320, 1): ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (3, 16, 16, 64, 320, CONV_S2, 8, 8, 2320, 1): ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 8, 8, 64, 320, CONV_UP2, 16, 16, 2320, 1): ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (16, 64, 64, 64, 320, CONV_S1, 64, 64, 2320, 1): ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 6, 256, 64, 128, CONV_S1, 6, 256, 5256, 1): ("conv_strip_kernel<2> splitk1", "conv_strip_kernel<2> splitk1"),
+    (1, 3, 768, 192, 256, CONV_S1, 3, 768, 5256, 1): ("conv_strip_kernel<2> splitk1", "conv_strip_kernel<2> splitk1"),
+    (3, 1, 256, 64, 128, CONV_S1, 1, 256, 5256, 1): ("conv_strip_kernel<2> splitk1", "conv_strip_kernel<2> splitk1"),
+    (2, 5, 512, 128, 128, CONV_S1, 5, 512, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 64, 64, 64, 256, CONV_S1, 64, 64, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+    (1, 4, 256, 128, 320, CONV_S1, 4, 256, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+    (1, 2, 512, 64, 256, CONV_S1, 2, 512, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+    (2, 16, 16, 192, 256, CONV_S1, 16, 16, 512, 3): ("gemm_pps_kernel<false> splitk3", "gemm_pps_kernel<false> splitk3"),
+    (3, 128, 128, 64, 128, CONV_S1, 128, 128, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S1, 9, 9, 64, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2, 5, 5, 64, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_UP2, 18, 18, 64, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1"),
+    (2, 5, 5, 64, 72, CONV_S2T, 9, 9, 64, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2A, 4, 4, 64, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S1, 9, 9, 3064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2, 5, 5, 3064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_UP2, 18, 18, 3064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64> splitk1"),
+    (2, 5, 5, 64, 72, CONV_S2T, 9, 9, 3064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2A, 4, 4, 3064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S1, 9, 9, 4064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2, 5, 5, 4064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_UP2, 18, 18, 4064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 5, 5, 64, 72, CONV_S2T, 9, 9, 4064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 72, CONV_S2A, 4, 4, 4064, 1): ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S1, 9, 9, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2, 5, 5, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_UP2, 18, 18, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 5, 5, 64, 136, CONV_S2T, 9, 9, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2A, 4, 4, 128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S1, 9, 9, 3128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2, 5, 5, 3128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_UP2, 18, 18, 3128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64> splitk1"),
+    (2, 5, 5, 64, 136, CONV_S2T, 9, 9, 3128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2A, 4, 4, 3128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S1, 9, 9, 4128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2, 5, 5, 4128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_UP2, 18, 18, 4128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64> splitk1"),
+    (2, 5, 5, 64, 136, CONV_S2T, 9, 9, 4128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2A, 4, 4, 4128, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S1, 9, 9, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2, 5, 5, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_UP2, 18, 18, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 5, 5, 64, 168, CONV_S2T, 9, 9, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2A, 4, 4, 160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S1, 9, 9, 3160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2, 5, 5, 3160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_UP2, 18, 18, 3160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64> splitk1"),
+    (2, 5, 5, 64, 168, CONV_S2T, 9, 9, 3160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2A, 4, 4, 3160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S1, 9, 9, 4160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2, 5, 5, 4160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_UP2, 18, 18, 4160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64> splitk1"),
+    (2, 5, 5, 64, 168, CONV_S2T, 9, 9, 4160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 168, CONV_S2A, 4, 4, 4160, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S1, 9, 9, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2, 5, 5, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 9, 9, 64, 136, CONV_UP2, 18, 18, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 5, 5, 64, 136, CONV_S2T, 9, 9, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 9, 9, 64, 136, CONV_S2A, 4, 4, 5256, 1): ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1"),
+    (2, 9, 9, 64, 264, CONV_S1, 9, 9, 512, 1): ("gemm_pp_kernel<1, true, true> splitk1", "gemm_pp_kernel<1, false, true> splitk1"),
+    (2, 9, 9, 64, 264, CONV_S2, 5, 5, 512, 1): ("gemm_pp_kernel<1, true, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 9, 9, 64, 264, CONV_UP2, 18, 18, 512, 1): ("gemm_pp_kernel<1, true, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 5, 5, 64, 264, CONV_S2T, 9, 9, 512, 1): ("gemm_pp_kernel<1, true, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 9, 9, 64, 264, CONV_S2A, 4, 4, 512, 1): ("gemm_pp_kernel<1, true, false> splitk1", "gemm_pp_kernel<1, false, false> splitk1"),
+    (2, 9, 9, 64, 320, CONV_S1, 9, 9, 2320, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 9, 9, 64, 320, CONV_S2, 5, 5, 2320, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 9, 9, 64, 320, CONV_UP2, 18, 18, 2320, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 5, 5, 64, 320, CONV_S2T, 9, 9, 2320, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (2, 9, 9, 64, 320, CONV_S2A, 4, 4, 2320, 1): ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64> splitk1", "gemm_pq_kernel<1, 320, false> splitk1"),
+    (3, 1, 1, 64, 64, CONV_S1, 1, 1, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 1, 7, 64, 64, CONV_S1, 1, 7, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 7, 1, 64, 64, CONV_S1, 7, 1, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 2, 2, 64, 64, CONV_S1, 2, 2, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 1, 1, 64, 64, CONV_S2, 1, 1, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 2, 3, 64, 64, CONV_S2, 1, 2, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 1, 1, 64, 64, CONV_UP2, 2, 2, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 1, 1, 64, 64, CONV_S2T, 1, 1, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 2, 2, 64, 64, CONV_S2T, 3, 3, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 9, 7, 64, 64, CONV_S2A, 4, 3, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 2, 2, 64, 64, CONV_S2A, 1, 1, 0, 0): ("gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1"),
+    (3, 16, 16, 64, 136, CONV_S1, 16, 16, 5256, 1): ("conv_strip_kernel<2> splitk1", "conv_strip_kernel<2> splitk1"),
+    (2, 16, 16, 64, 264, CONV_S1, 16, 16, 512, 1): ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk1"),
+}
+
+# check_conv_forms: family -> the kernel of every single-pass form (colstats, fp32 output, accumulate, row-bias slice), and of the explicit split-K call
+CHECK_CONV_FORM_KERNELS = {
+    "64": ("gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1", "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk3"),
+    "128": ("gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1", "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk3"),
+    "160": ("gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk1", "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64> splitk3"),
+    "5256": ("gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk3"),
+    "5256 strip": ("conv_strip_kernel<2> splitk1", "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32> splitk3"),
+    "512": ("gemm_pp_kernel<1, false, true> splitk1", "gemm_pp_kernel<1, false, true> splitk3"),
+    "512 pps": ("gemm_pps_kernel<false> splitk1", "gemm_pps_kernel<false> splitk3"),
+    "2320": ("gemm_pq_kernel<1, 320, false> splitk1", "gemm_pq_kernel<1, 320, false> splitk3"),
+}
+# ... and with E4T_ACT_GELU through the raw ABI.  The strip geometries make Hout * Wout a multiple of 256, so a row bias never asks a strip kernel for the
+# GENERAL epilogue: the flag is the only way to gemm_pps_kernel<true>.
+CHECK_CONV_GELU_KERNELS = {"512": "gemm_pp_kernel<1, true, true> splitk1", "512 pps": "gemm_pps_kernel<true> splitk1"}
+
+CHECK_CONV_OUT_KERNELS = {
+    (2, 16, 16, 64, 4, CONV_S1, 16, 16, 0, 0): "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64> splitk1",
+    (2, 16, 16, 64, 4, CONV_S1, 16, 16, 64, 0): "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64> splitk1",
+    (2, 16, 16, 64, 4, CONV_S1, 16, 16, 128, 0): "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64> splitk1",
+}
+
+
+# Every kernel symbol e4t_conv3x3_kernel returns over the conv groups of the corpus and conv_geometry_corpus() (tools/gemm_dispatch_dump.py), with the
+# conv modes it is returned for.  The mode is a run-time branch of the gather, so symbol x mode is the unit the checks must reach.
+ALL_MODES = (CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A)
+CONV_KERNEL_MODES = {
+    "conv_strip_kernel<2>": (CONV_S1,),
+    "gemm_dma_kernel<64, 64, 2, 2, 1, 2, false, 64>": ALL_MODES, "gemm_dma_kernel<64, 64, 2, 2, 1, 2, true, 64>": ALL_MODES,
+    "gemm_dma_kernel<64, 64, 2, 2, 1, 3, false, 64>": ALL_MODES, "gemm_dma_kernel<64, 64, 2, 2, 1, 3, true, 64>": ALL_MODES,
+    "gemm_dma_kernel<64, 64, 2, 2, 1, 4, false, 64>": ALL_MODES,
+    "gemm_dma_kernel<128, 128, 4, 2, 1, 2, false, 64>": ALL_MODES, "gemm_dma_kernel<128, 128, 4, 2, 1, 2, true, 64>": ALL_MODES,
+    "gemm_dma_kernel<128, 128, 4, 2, 1, 3, false, 64>": ALL_MODES, "gemm_dma_kernel<128, 128, 4, 2, 1, 4, false, 64>": ALL_MODES,
+    "gemm_dma_kernel<128, 160, 4, 1, 1, 2, false, 64>": ALL_MODES, "gemm_dma_kernel<128, 160, 4, 1, 1, 2, true, 64>": ALL_MODES,
+    "gemm_dma_kernel<128, 160, 4, 1, 1, 3, false, 64>": ALL_MODES, "gemm_dma_kernel<128, 160, 4, 1, 1, 4, false, 64>": ALL_MODES,
+    "gemm_dma_kernel<256, 128, 4, 2, 1, 3, false, 32>": ALL_MODES,
+    "gemm_pp_kernel<1, false, false>": (CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A), "gemm_pp_kernel<1, true, false>": (CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A),
+    "gemm_pp_kernel<1, false, true>": (CONV_S1,), "gemm_pp_kernel<1, true, true>": (CONV_S1,),      # stride 1 walks K channel-major: a template argument here
+    "gemm_pps_kernel<false>": (CONV_S1,), "gemm_pps_kernel<true>": (CONV_S1,),
+    "gemm_pq_kernel<1, 320, false>": ALL_MODES,
+    "gemm_kernel": ALL_MODES,
+}
+# symbol -> why no check executes it (in any of its modes)
+CONV_KERNELS_NOT_REACHED = {
+    "gemm_kernel": "the register-staged fallback: chosen only for an input map beyond 4 GB (or under the E4T_GEMM_REGSTAGE switch, read once per process)",
+}
+
+
+def _conv_checks():
+    """(what, case, form, split-K override) -> pinned "<symbol> splitk<n>", for everything the conv checks launch"""
+    import kernel_checks as kc
+    rows = {}
+    for case, (full, bare) in CHECK_CONV_KERNELS.items():
+        rows[("case", case, "full", None)], rows[("case", case, "bare", None)] = full, bare
+    for fam, (single, split) in CHECK_CONV_FORM_KERNELS.items():
+        for form in kc.CONV_FORMS:
+            if form not in ("full", "bare", "gelu"):
+                rows[(fam, kc.CONV_FORM_CASES[fam], form, None)] = single
+        rows[(fam, kc.CONV_FORM_CASES[fam], "colstats", kc.CONV_FORM_SPLITK)] = split
+    for fam, sym in CHECK_CONV_GELU_KERNELS.items():
+        rows[(fam, kc.CONV_FORM_CASES[fam], "gelu", None)] = sym
+    for case, sym in CHECK_CONV_OUT_KERNELS.items():
+        rows[("conv_out", case, "f32 bias", None)] = sym
+    return rows
+
+
+def test_the_pinned_conv_tables_cover_exactly_what_the_conv_checks_run():
+    """one set of case lists (tests/kernel_checks.py, importable without a GPU) behind the GPU checks and these tables"""
+    import kernel_checks as kc
+    every = kc.CONV_ALL_CASES + kc.CONV_GUARD_CASES
+    assert len(set(kc.CONV_ALL_CASES)) == len(kc.CONV_ALL_CASES) == len(kc.CONV_CASES) + len(kc.CONV_REACH_CASES) + len(kc.CONV_DEGENERATE_CASES)
+    assert set(CHECK_CONV_KERNELS) == set(every)
+    assert set(CHECK_CONV_FORM_KERNELS) == set(kc.CONV_FORM_CASES)
+    assert set(CHECK_CONV_OUT_KERNELS) == set(kc.CONV_OUT_CASES) and set(CHECK_CONV_GELU_KERNELS) == set(kc.CONV_GELU_FAMILIES)
+    assert len(kc.CONV_REACH_CASES) == 5 * len(kc.CONV_REACH_TILES) and {c[8] for c in kc.CONV_REACH_CASES} == {t for t, _ in kc.CONV_REACH_TILES}
+    # the forms the model calls are all there: colstats with and without residual, three fp32 outputs, accumulate into both types, the row-bias slice
+    assert set(kc.CONV_FORMS) == {"full", "bare", "colstats", "colstats+res", "f32 bias", "f32 res32", "f32 res16", "accum16", "accum32", "rowbias slice", "gelu"}
+    assert all(c[0] * c[6] * c[7] % 32 == 0 for c in kc.CONV_FORM_CASES.values())      # column statistics need M % 32 == 0
+
+
+def test_conv_check_cases_keep_their_kernels(dumper):      # (the fixture: the tables are for 256 CUs)
+    import kernel_checks as kc
+    for (what, case, form, sk), pinned in _conv_checks().items():
+        assert kc.conv_kernel(case, form, sk) == pinned, (what, case, form, sk)
+    # the families of check_conv_forms are the eight conv kernel families, one kernel each; the strip kernel takes no split-K
+    assert len({single.split(" splitk")[0] for single, _ in CHECK_CONV_FORM_KERNELS.values()}) == 8
+    assert all(single.endswith(" splitk1") and split.endswith(" splitk%d" % kc.CONV_FORM_SPLITK) for single, split in CHECK_CONV_FORM_KERNELS.values())
+    # the automatic split-K falls back to ONE pass without a workspace, and the query says so; an explicit one is refused like the launch (-12)
+    case = (2, 8, 8, 1280, 1280, CONV_S1, 8, 8, 0, 0)
+    assert int(kc.conv_kernel(case, "bare").split(" splitk")[1]) > 1
+    d = kc.conv_desc(case, "bare")
+    d.workspace, d.workspace_bytes = None, 0
+    sym, sk = C.c_char_p(), C.c_int(0)
+    assert _C.load().e4t_conv3x3_kernel(C.byref(d), C.byref(sym), C.byref(sk)) == 0 and sk.value == 1
+    d.splitk = 3
+    assert _C.load().e4t_conv3x3_kernel(C.byref(d), C.byref(sym), C.byref(sk)) == -12
+    d.Cin = 65
+    assert _C.load().e4t_conv3x3_kernel(C.byref(d), C.byref(sym), C.byref(sk)) == -22 and b"multiple of 64" in _C.load().e4t_last_error()
+
+
+def test_conv_checks_reach_every_kernel_the_launcher_can_choose(dumper):
+    """symbol x mode over the conv corpus == the clear-text set above, and the checks execute each of them but the listed exceptions: a kernel added to
+    the variant table (or a predicate changed so that one is no longer reached) fails here until a conv check has a shape that executes it"""
+    import itertools
+    reachable = {}
+    for item in itertools.chain(dump.corpus(), dump.conv_geometry_corpus()):
+        if item.kind == "conv":
+            said = dumper.conv_kernel(item)
+            if not said.startswith("rc "):
+                reachable.setdefault(said.split(" splitk")[0], set()).add(item.kw["mode"])
+    assert {s: tuple(sorted(m)) for s, m in reachable.items()} == CONV_KERNEL_MODES
+    reached = {(pinned.split(" splitk")[0], case[5]) for (_, case, _, _), pinned in _conv_checks().items()}
+    units = {(s, m) for s, modes in CONV_KERNEL_MODES.items() for m in modes}
+    excluded = {(s, m) for s, m in units if s in CONV_KERNELS_NOT_REACHED}
+    assert set(CONV_KERNELS_NOT_REACHED) <= set(CONV_KERNEL_MODES) and not (reached & excluded)
+    assert reached | excluded == units, (sorted(units - reached - excluded), sorted(reached - units))

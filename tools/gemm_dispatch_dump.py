@@ -2,6 +2,7 @@
 """What the GEMM / 3x3-conv and the attention host code decide for a fixed corpus of descriptors, one line per descriptor:
 
     <kind> <descriptor> -> <tile tile_m tile_n splitk workspace_bytes tail_rows stages> [| rc <rc> <error text> | <launch-log lines>]
+    conv <descriptor> -> <plan as above> | <kernel symbol> splitk<n> [| rc ... | ...]      (e4t_conv3x3_kernel: what the launch will run)
     attn <shape> ws=<workspace offered> -> <forward kernel | dQ kernel | dK/dV kernel | tsplit tchunk | workspace_floats> [| rc ... | ...]
 
 Two builds of the library (E4T_LIB=<path to libe4t_hip.so> selects another one) decide alike iff their dumps are byte-identical:
@@ -19,6 +20,8 @@ E4T_CONV_NOSTRIP, ...) are read once per process: one run per setting.
     --anchor           check the 'step' group against profiles/r06_roofline_per_shape.csv: every GEMM / conv / TN launch recorded there
                        on hardware is reproduced (symbol and shape string), every split-K reduce row by a launch's second log line
     --record           rewrite tests/gemm_dispatch_record.txt (what tests/test_gemm_dispatch.py compares against) from this library
+    --conv-check       hold e4t_conv3x3_kernel against the launch log: for every conv item of the corpus and of conv_geometry_corpus() the symbol
+                       and split-K of the query equal the first field and the splitk of the log line (or both refuse with the same code)
     --attn-launches    the 'attn' group as the launch log alone tells it (kernel symbols; workspace floats from
                        e4t_attention_bwd_workspace_floats): needs no e4t_attention_plan, so E4T_LIB may be a library older than that entry point
     --attn-check FILE  hold such a dump against e4t_attention_plan of this library; prints every row that differs (the record's 'attn' group
@@ -138,6 +141,29 @@ def corpus():
     yield from attn_corpus()
 
 
+def conv_geometry_corpus():
+    """what the square images of corpus() leave out: the strip predicates' widths (16 / 64 / 256 / 512) with and without whole 256-pixel tiles of rows,
+    non-square images, a row bias over Hout * Wout % 32 != 0 pixels (the GENERAL epilogue), all five modes, every kernel family's tile hint,
+    an input map beyond 4 GB"""
+    def geo(mode, H, W):
+        (Hin, Hout), (Win, Wout) = conv_geometry(mode, H), conv_geometry(mode, W)
+        return dict(Hin=Hin, Win=Win, Hout=Hout, Wout=Wout)
+    sizes = [(H, W) for W in (16, 64, 256, 512) for H in (1, 2, 3, 4, 6, 16)] + [(8, 8), (9, 9), (9, 7), (5, 5), (20, 12), (48, 40), (24, 24), (1, 7), (7, 1), (2, 2), (1, 1)]
+    for t, mode, (H, W), B, (Cin, Cout) in itertools.product((0, 64, 3064, 4064, 128, 4128, 160, 3160, 512, 2320, 5256), (1, 2, 3, 4, 5), sizes, (1, 3),
+                                                             ((64, 64), (64, 72), (128, 256), (192, 320), (64, 4))):
+        if mode == 5 and (H < 2 or W < 2):
+            continue
+        base = dict(B=B, Cin=Cin, Cout=Cout, mode=mode, tile=t, **geo(mode, H, W))
+        yield Item("conv geometry", "conv", base)
+        yield Item("conv geometry", "conv", dict(base, rowbias=1, bias=1, residual=1))
+        yield Item("conv geometry", "conv", dict(base, splitk=1, colstats=1))
+        yield Item("conv geometry", "conv", dict(base, splitk=3))
+        yield Item("conv geometry", "conv", dict(base, ws="none"))
+        yield Item("conv geometry", "conv", dict(base, flags=OUT_F32))
+    for t, mode in itertools.product((0, 64, 128, 512, 2320), (1, 2, 3, 4, 5)):      # an input map beyond 4 GB: the register-staged fallback
+        yield Item("conv geometry", "conv", dict(B=16, Cin=512, Cout=320, mode=mode, tile=t, **geo(mode, 512, 512)))
+
+
 ATTN_WS = ("full", "delta", "delta3", "short")      # the size the library asks for | B*H*T (Delta only) | B*H*T + 3 | one float short of the first
 
 
@@ -250,6 +276,14 @@ class Dumper:
             return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
         return "%d %d %d %d %d %d %d" % (pl.tile, pl.tile_m, pl.tile_n, pl.splitk, pl.workspace_bytes, pl.tail_rows, pl.stages)
 
+    def conv_kernel(self, item, d=None):
+        """what e4t_conv3x3_kernel says the launch of a conv item will run: "<kernel symbol> splitk<n>" (pure host code, like the plan)"""
+        sym, sk = C.c_char_p(), C.c_int(0)
+        rc = self.lib.e4t_conv3x3_kernel(C.byref(d or make_desc(item)), C.byref(sym), C.byref(sk))
+        if rc != 0:
+            return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
+        return "%s splitk%d" % (sym.value.decode(), sk.value)
+
     def launch(self, item, d=None):
         """(rc, error text, [log lines])"""
         if item.kind == "attn":
@@ -261,6 +295,8 @@ class Dumper:
     def line(self, item):
         d = None if item.kind == "attn" else make_desc(item)
         s = "%s %s -> %s" % (item.kind, describe(item.kw), self.plan(item, d))
+        if item.kind == "conv" and hasattr(self.lib, "e4t_conv3x3_kernel"):
+            s += " | " + self.conv_kernel(item, d)
         if self.log:
             rc, err, lines = self.launch(item, d)
             s += " | rc %d %s | %s" % (rc, err, " ; ".join(lines))
@@ -303,6 +339,32 @@ def anchor(dumper):
     launches = sum(1 for s, _ in want if not s.startswith("splitk_reduce"))
     print("step table: %d rows (%d launches, %d reduces), %d reproduced, %d missed" % (len(want), launches, len(want) - launches, len(matched), miss))
     return matched, miss
+
+
+def conv_check(dumper):
+    """rows on which e4t_conv3x3_kernel and the launch log of e4t_conv3x3 disagree, over every conv item of the corpus and conv_geometry_corpus()"""
+    n = bad = 0
+    syms = collections.Counter()
+    for item in itertools.chain(corpus(), conv_geometry_corpus()):
+        if item.kind != "conv":
+            continue
+        d = make_desc(item)
+        said = dumper.conv_kernel(item, d)
+        rc, err, lines = dumper.launch(item, d)
+        if lines:
+            m = re.match(r"([^|]+)\|conv .* splitk(\d+)\|", lines[0])
+            ran = "%s splitk%s" % m.groups() if m else lines[0]
+        else:
+            ran = "rc %d %s" % (rc, err)
+        n += 1
+        syms[said.split(" splitk")[0] if lines else "(refused)"] += 1
+        if said != ran:
+            bad += 1
+            print("DIFF conv %s: query %s, launch %s" % (describe(item.kw), said, ran))
+    for sym, k in sorted(syms.items()):
+        print("%8d  %s" % (k, sym))
+    print("conv: %d rows, %d differ" % (n, bad))
+    return bad
 
 
 def attn_launch_lines(dumper):
@@ -365,6 +427,7 @@ def main():
     ap.add_argument("--group", action="append")
     ap.add_argument("--anchor", action="store_true")
     ap.add_argument("--record", action="store_true")
+    ap.add_argument("--conv-check", action="store_true")
     ap.add_argument("--attn-launches", action="store_true")
     ap.add_argument("--attn-check", metavar="FILE")
     args = ap.parse_args()
@@ -383,6 +446,10 @@ def main():
             if not d.log:
                 sys.exit("--anchor needs the launch half")
             return 1 if anchor(d)[1] else 0
+        if args.conv_check:
+            if not d.log:
+                sys.exit("--conv-check needs the launch half")
+            return 1 if conv_check(d) else 0
         if args.attn_launches:
             if not d.log:
                 sys.exit("--attn-launches needs the launch half")
