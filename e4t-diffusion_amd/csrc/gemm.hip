@@ -23,6 +23,7 @@
 // Host half (end of this file): one table, kVariants, has a row per kernel variant — tile code, tile shape, capabilities, entry points
 // and their symbol text.  plan_gemm() (hint -> automatic choice -> capability fallback -> split-K) picks a row, launch_gemm() launches
 // the row's entry and logs the row's text; e4t_gemm_plan / e4t_conv3x3_plan export the same plan.
+// Operand addressing the kernels share (batch entry, output pixel, LDS swizzle / fragment offsets, strip geometry): gemm_common.h.
 //
 // Reference call sites this replaces: every F.linear / nn.Linear / nn.Conv2d on the hot path —
 // e4t/models/cross_attention.py:506,516,518,534 ; e4t/models/attention.py:376,419-430 ;
@@ -53,19 +54,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
   const int wm = wave / WGN, wn = wave % WGN;
   const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;
 
-  const int nkt = (p.K + BK - 1) / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split;
-  int kt_end = kt_begin + p.ktiles_per_split;
-  if (kt_end > nkt) kt_end = nkt;
+  const KRange kr = batch_entry<BK>(p, (p.K + BK - 1) / BK);
+  const int kt_begin = kr.begin, kt_end = kr.end;
 
   // ---- per-thread chunk ownership (fixed rows across the K loop) ----
   // chunk c = tid + i*256 : row = c >> 3, kc = c & 7  (8 lanes cover one 128-B row segment)
@@ -84,12 +74,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
       a_base[i] = (long long)gr;
       a_oy[i] = a_ox[i] = 0;
     } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[i] = rem / p.Wout;
-      a_ox[i] = rem - a_oy[i] * p.Wout;
-      a_base[i] = (long long)b * p.Hin * p.Win;
+      out_pixel(p, gr, a_base[i], a_oy[i], a_ox[i]);
     }
   }
   const int kc8 = (tid & 7) * 8;  // this thread's k offset inside a tile (same for all its chunks)
@@ -116,7 +101,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         int iy, ix;
-        bool ok = a_ok[i];
+        bool ok = a_ok[i];      // written out: profiles/gemm_addressing_isa.txt
         if (p.mode == E4T_CONV_S1) {
           iy = a_oy[i] + ky - 1; ix = a_ox[i] + kx - 1;
           ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
@@ -269,12 +254,9 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
   const int m0 = tile_y * 256, n0 = tile_x * BN;
   const int hw = p.Hin * p.Win;
   const int b = m0 / hw, rem = m0 - b * hw, y = rem / p.Win, x0 = rem - y * p.Win;
-  // the tile's 256 output pixels: one 256-pixel segment of an image row (W % 256 == 0), or 256 / W whole rows (W = 16 .. 128: x0 = 0).
-  // A strip = those rows of input row y + ky - 1 (+ ry), each widened by one pixel on both sides: SW = min(W, 256) + 2 strip rows per image row
-  const int segw = p.Win < 256 ? p.Win : 256, SW = segw + 2, nrows = 256 / segw;
+  // the tile's 256 output pixels and their strips of input row y + ky - 1 (+ ry): StripGeom (whole-row tiles: x0 = 0)
+  const StripGeom sg(p.Win);
   const int ncc = p.Cin / KT, nstrip = 3 * ncc, nsub = 3 * nstrip;
-  constexpr unsigned OOB = 0xFFFF0000u;
-  auto swz = [](int r) { return (r >> 2) & 3; };
 
   const __amdgpu_buffer_rsrc_t rs_a = cm_rsrc(p);                   // base lowered by one image row + one pixel (never touched: masked lanes)
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
@@ -284,9 +266,9 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const int j = 16 * (wave + 8 * i) + (lane >> 2);
-    const int ry = j / SW, xs = j - ry * SW, ix = x0 - 1 + xs;
-    const bool ok = ry < nrows && ix >= 0 && ix < p.Win;
-    a_vo[i] = (unsigned)(((ry * p.Win + xs) * p.Cin + ((lane & 3) ^ swz(j)) * 8) * 2);
+    const int ry = j / sg.SW, xs = j - ry * sg.SW, ix = x0 - 1 + xs;      // written out: profiles/gemm_addressing_isa.txt
+    const bool ok = ry < sg.nrows && ix >= 0 && ix < p.Win;
+    a_vo[i] = (unsigned)(((ry * p.Win + xs) * p.Cin + ((lane & 3) ^ swz_slot<KT>(j)) * 8) * 2);
     int m = 0;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
@@ -301,7 +283,7 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < NBP; ++i) {
     const int r = 16 * (NBP * bw + i) + (lane >> 2);
-    b_vo[i] = (b_wave && n0 + r < p.N) ? (unsigned)((((size_t)(n0 + r)) * p.ldb + ((lane & 3) ^ swz(r)) * 8) * 2) : OOB;
+    b_vo[i] = (b_wave && n0 + r < p.N) ? (unsigned)((((size_t)(n0 + r)) * p.ldb + ((lane & 3) ^ swz_slot<KT>(r)) * 8) * 2) : OOB;
   }
   // walkers (incremental: no division per issue)
   int a_ky = 0, a_cc = 0;                        // next strip to issue
@@ -338,13 +320,13 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
         const int o = wm * WM + i * 32 + frow;                 // output pixel of the tile
-        const int r = (o / segw) * SW + o % segw + kx;         // its strip row for tap kx
-        a_off[kx][i][ks] = r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
+        const int r = sg.frag_row(o, kx);         // its strip row for tap kx
+        a_off[kx][i][ks] = frag_off<KT>(r, ks, fhi);
       }
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int r = wn * WN + j * 32 + frow;
-      b_off[j][ks] = r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
+      b_off[j][ks] = frag_off<KT>(r, ks, fhi);
     }
   }
   bf16_t* const Bs = smem + 2 * ASZ;
@@ -402,10 +384,10 @@ __global__ __launch_bounds__(256 * WGN, 4) void conv_strip_kernel(GemmArgs p) {
   }
 }
 // may a 256 x 128 x 32 (WGN = 2) / 256 x 256 (WGN = 4, in place of the ping-pong kernel) conv launch go to conv_strip_kernel?
+static bool strips_enabled() { static const bool on = getenv("E4T_CONV_NOSTRIP") == nullptr; return on; }          // A/B switch of both strip kernels
+static bool strip_rows_ok(const GemmArgs& p) { return p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0); }      // row segments, or whole rows per tile (StripGeom)
 static bool conv_strip_ok(const GemmArgs& p, int splitk, int batch) {
-  static const bool on = getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
-  const bool rows = p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0);      // row segments, or whole rows per tile
-  return on && p.mode == E4T_CONV_S1 && p.chan_major && splitk == 1 && batch == 1 && rows && p.Wout == p.Win && p.Hout == p.Hin &&
+  return strips_enabled() && p.mode == E4T_CONV_S1 && p.chan_major && splitk == 1 && batch == 1 && strip_rows_ok(p) && p.Wout == p.Win && p.Hout == p.Hin &&
          p.Cin % 32 == 0 && p.K == 9 * p.Cin;
 }
 
@@ -473,19 +455,8 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
   xcd_tile(tile_x, tile_y, p.group_m);
   const int m0 = tile_y * BM, n0 = tile_x * BN;
 
-  const int nkt = p.K / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split;
-  int kt_end = kt_begin + p.ktiles_per_split;
-  if (kt_end > nkt) kt_end = nkt;
+  const KRange kr = batch_entry<BK>(p, p.K / BK);
+  const int kt_begin = kr.begin, kt_end = kr.end;
 
   // Operands are addressed through buffer resources (buffer_load ... lds): a 32-bit per-lane byte offset that changes only
   // when the conv tap / concat source changes, plus a wave-uniform SGPR offset that walks K (+64 B per quarter).  Issuing a
@@ -495,7 +466,6 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
   const __amdgpu_buffer_rsrc_t rs_a = cm ? cm_rsrc(p) : uniform_rsrc(p.A, p.a_bytes);
   const __amdgpu_buffer_rsrc_t rs_a2 = uniform_rsrc(p.A2 ? p.A2 : p.A, p.A2 ? p.a2_bytes : p.a_bytes);
   const __amdgpu_buffer_rsrc_t rs_b = uniform_rsrc(p.B, p.b_bytes);
-  constexpr unsigned OOB = 0xFFFF0000u;          // >= every extent the launcher accepts
   // DMA: one wave-instruction = 16 rows x 64 B; wave w feeds quarter rows 32w + 16j + (lane >> 2), j = 0, 1
   const int drow = lane >> 2, dslot = lane & 3;
   long long a_base[2];
@@ -505,19 +475,14 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int r = wave * 32 + j * 16 + drow;
-    const int kc = (dslot ^ ((r >> 2) & 3)) * 8;
+    const int kc = (dslot ^ swz_slot<HK>(r)) * 8;
     const int gr = m0 + r;
     a_ok[j] = gr < p.M;
     a_kc[j] = kc;
     if (MODE == 0) {
       a_base[j] = (long long)gr; a_oy[j] = a_ox[j] = 0;
     } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[j] = rem / p.Wout;
-      a_ox[j] = rem - a_oy[j] * p.Wout;
-      a_base[j] = (long long)b * p.Hin * p.Win;
+      out_pixel(p, gr, a_base[j], a_oy[j], a_ox[j]);
     }
     const int gn = n0 + r;
     b_vo[j] = gn < p.N ? (unsigned)(((size_t)gn * p.ldb + kc) * 2) : OOB;
@@ -538,7 +503,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
   bool a_second = false;           // reading the second concat source
   auto place_a = [&](int k0) {
     if (MODE == 0) {
-      int ld = p.lda, koff = k0;
+      int ld = p.lda, koff = k0;      // written out: profiles/gemm_addressing_isa.txt
       a_second = k0 >= p.K1;
       if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
       a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
@@ -552,7 +517,7 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         int iy, ix;
-        bool ok = a_ok[j];
+        bool ok = a_ok[j];      // written out: profiles/gemm_addressing_isa.txt
         if (p.mode == E4T_CONV_S1) {
           iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
           ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
@@ -624,12 +589,12 @@ __global__ __launch_bounds__(512) void gemm_pp_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int r = wr * 128 + i * 32 + frow;
-      a_off[i][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
+      a_off[i][ks] = frag_off<HK>(r, ks, fhi);
     }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int r = wc * 64 + j * 32 + frow;
-      b_off[j][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
+      b_off[j][ks] = frag_off<HK>(r, ks, fhi);
     }
   }
   // quarter slots of buffer b: lo-A, lo-B, hi-A, hi-B at (4b + 0..3) * QUART
@@ -768,7 +733,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
   const int m0 = tile_y * BM, n0 = tile_x * BN;
 
   const int nkt = p.K / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
+  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;      // (not batch_entry(): batch == 1 here, only bias and C move)
   if (p.bias) p.bias += bz * p.strideBias;
   if (!p.reduce_batch) {
     if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
@@ -780,10 +745,9 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
 
   const int hw = p.Hin * p.Win;
   const int ib = m0 / hw, rem = m0 - ib * hw, y = rem / p.Win, x0 = rem - y * p.Win;
-  const int segw = p.Win < 256 ? p.Win : 256, SW = segw + 2, nrows = 256 / segw;
+  const StripGeom sg(p.Win);
   const __amdgpu_buffer_rsrc_t rs_a = cm_rsrc(p);
   const __amdgpu_buffer_rsrc_t rs_b = uniform_rsrc(p.B, p.b_bytes);
-  constexpr unsigned OOB = 0xFFFF0000u;
   const int drow = lane >> 2, dslot = lane & 3;
   // half-strip pieces of this wave: piece q = wave + 8 i = strip rows 16 q .. 16 q + 15
   unsigned a_vo[3];
@@ -791,9 +755,9 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
     const int j = 16 * (wave + 8 * i) + drow;
-    const int ry = j / SW, xs = j - ry * SW, ix = x0 - 1 + xs;
-    const bool ok = ry < nrows && ix >= 0 && ix < p.Win && m0 < p.M;
-    a_vo[i] = (unsigned)(((ry * p.Win + xs) * p.Cin + (dslot ^ ((j >> 2) & 3)) * 8) * 2);
+    const int ry = j / sg.SW, xs = j - ry * sg.SW, ix = x0 - 1 + xs;      // written out: profiles/gemm_addressing_isa.txt
+    const bool ok = ry < sg.nrows && ix >= 0 && ix < p.Win && m0 < p.M;
+    a_vo[i] = (unsigned)(((ry * p.Win + xs) * p.Cin + (dslot ^ ((j >> 2) & 3)) * 8) * 2);      // written out: profiles/gemm_addressing_isa.txt
     int m = 0;
 #pragma unroll
     for (int ky = 0; ky < 3; ++ky) {
@@ -857,13 +821,13 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int o = wr * 128 + i * 32 + frow;
-        const int r = (o / segw) * SW + o % segw + kx;
-        a_off[kx][i][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
+        const int r = sg.frag_row(o, kx);
+        a_off[kx][i][ks] = frag_off<HK>(r, ks, fhi);
       }
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int r = wc * 64 + j * 32 + frow;
-      b_off[j][ks] = r * HK + (((ks * 2 + fhi) ^ ((r >> 2) & 3)) * 8);
+      b_off[j][ks] = frag_off<HK>(r, ks, fhi);
     }
   }
   bf16_t* const Bq = smem + A_EL;      // B quarter (buffer bb, half kh) at Bq + (2 bb + kh) QUART; half-strip (parity sp, half kh) at smem + (2 sp + kh) HSTRIP
@@ -946,9 +910,7 @@ __global__ __launch_bounds__(512) void gemm_pps_kernel(GemmArgs p) {
 }
 // may a 256 x 256 ping-pong conv launch go to gemm_pps_kernel?
 static bool conv_pps_ok(const GemmArgs& p, int /*splitk*/, int batch) {
-  static const bool on = getenv("E4T_CONV_NOSTRIP") == nullptr;          // A/B switch
-  const bool rows = p.Win % 256 == 0 || (p.Win >= 16 && 256 % p.Win == 0 && p.Hin % (256 / p.Win) == 0);
-  return on && p.mode == E4T_CONV_S1 && p.chan_major && batch == 1 && rows && p.Wout == p.Win && p.Hout == p.Hin && p.Cin % 64 == 0 &&
+  return strips_enabled() && p.mode == E4T_CONV_S1 && p.chan_major && batch == 1 && strip_rows_ok(p) && p.Wout == p.Win && p.Hout == p.Hin && p.Cin % 64 == 0 &&
          p.K == 9 * p.Cin && p.ktiles_per_split % 3 == 0 && p.M % 256 == 0;
 }
 
@@ -1031,7 +993,6 @@ __global__ __launch_bounds__(512) void gemm_tn_kernel(GemmArgs p) {
   // beyond M / N carry an out-of-range offset and read as zero
   const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;
   // DMA: piece q = 4 tile rows; wave w feeds pieces 2w, 2w+1 of each operand.  lane -> (row in piece, physical 16-B chunk)
   const int prow = lane >> 4, pchunk = lane & 15;
   const int lchunk = (((pchunk >> 1) ^ (2 * prow)) << 1) | (pchunk & 1);      // logical chunk stored at this physical slot

@@ -473,6 +473,58 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t cm_rsrc(const GemmArgs& p) {
   return uniform_rsrc((const char*)p.A - sh, p.a_bytes + sh);
 }
 
+// ---- operand addressing shared by the kernels (gemm.hip, gemm_dma_kernel.inc, gemm_pq_kernel.inc) ---------------------------------
+// What is here either leaves every kernel's instruction stream as it was or (batch_entry) was measured against the parent kernel by kernel
+// (profiles/gemm_addressing_isa.txt, gemm_addressing_ab.txt; tools/isa_compare.py, ab_addressing.py).  The five-mode tap decode, the dense place_a, the
+// strip pieces and the accumulator zeroing stay written out in each kernel: as shared functions they changed register counts or were not measured.
+constexpr unsigned OOB = 0xFFFF0000u;          // a per-lane byte offset >= every extent the launcher accepts: the buffer load returns zeros
+
+// Output row gr of a conv -> the first pixel of its image in the input map (base) and its output position (oy, ox)
+__device__ __forceinline__ void out_pixel(const GemmArgs& p, int gr, long long& base, int& oy, int& ox) {
+  const int hw = p.Hout * p.Wout;
+  const int b = gr / hw;
+  const int rem = gr - b * hw;
+  oy = rem / p.Wout;
+  ox = rem - oy * p.Wout;
+  base = (long long)b * p.Hin * p.Win;
+}
+
+// K-tiles [begin, end) of this workgroup's split
+struct KRange { int begin, end; };
+// Batch entry and split-K slice of this workgroup (blockIdx.z = batch entry * splitk + split): moves the operand pointers of p to the batch entry and
+// returns the split's K-tiles of width KT out of nkt (the launcher counts ktiles_per_split in 64-wide tiles).
+template <int KT>
+__device__ __forceinline__ KRange batch_entry(GemmArgs& p, int nkt) {
+  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
+  p.A += bz * p.strideA;
+  if (p.A2) p.A2 += bz * p.strideA;
+  p.B += bz * p.strideB;
+  if (p.bias) p.bias += bz * p.strideBias;
+  if (!p.reduce_batch) {
+    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
+    else p.C = (bf16_t*)p.C + bz * p.strideC;
+  }
+  KRange k;
+  k.begin = sz * p.ktiles_per_split * (BK / KT);
+  k.end = k.begin + p.ktiles_per_split * (BK / KT);
+  if (k.end > nkt) k.end = nkt;
+  return k;
+}
+// Source-side XOR swizzle of the 16-byte slots of the LDS rows buf_dma16 fills (KT = 64: 128-byte rows, 8 slots; KT = 32: 64-byte rows, 4 slots):
+// slot s of row r holds logical chunk s ^ swz_slot(r).  frag_off: element offset of the fragment chunk (k step ks, lane half fhi) of row r.
+template <int KT>
+__device__ __forceinline__ int swz_slot(int r) { return KT == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); }
+template <int KT>
+__device__ __forceinline__ int frag_off(int r, int ks, int fhi) { return r * KT + (((ks * 2 + fhi) ^ swz_slot<KT>(r)) * 8); }
+
+// A strip-staged tile of 256 output pixels (conv_strip_kernel, gemm_pps_kernel): one 256-pixel segment of an image row (W % 256 == 0) or 256 / W
+// whole rows (W = 16 .. 128); a strip holds those rows of one input row per image row, each widened by one pixel on both sides.
+struct StripGeom {
+  int segw, SW, nrows;                // pixels per image row of the tile; strip rows per image row (segw + 2); image rows per tile
+  __device__ __forceinline__ explicit StripGeom(int Win) : segw(Win < 256 ? Win : 256), SW(segw + 2), nrows(256 / segw) {}
+  __device__ __forceinline__ int frag_row(int o, int kx) const { return (o / segw) * SW + o % segw + kx; }      // strip row output pixel o reads for tap kx
+};
+
 // ---- tail rows of a dense GEMM -------------------------------------------------------------------------------------------------
 // The CLIP-ViT's token matrix at B = 16 has 16 x 257 = 4112 = 32 x 128 + 16 rows.  Every tiling of 4112 rows pays a whole extra
 // round of workgroups for the last 16: measured in the step (profiles/r04_prefetch_off_roofline_per_shape.csv), the SAME N / K at

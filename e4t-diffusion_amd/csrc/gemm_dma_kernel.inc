@@ -31,19 +31,8 @@
   xcd_tile(tile_x, tile_y, p.group_m);
   const int m0 = tile_y * BM, n0 = tile_x * BN;
 
-  const int nkt = (p.K + KT - 1) / KT;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
-  p.A += bz * p.strideA;
-  if (p.A2) p.A2 += bz * p.strideA;
-  p.B += bz * p.strideB;
-  if (p.bias) p.bias += bz * p.strideBias;
-  if (!p.reduce_batch) {
-    if (p.flags & E4T_OUT_F32) p.C = (float*)p.C + bz * p.strideC;
-    else p.C = (bf16_t*)p.C + bz * p.strideC;
-  }
-  const int kt_begin = sz * p.ktiles_per_split * (BK / KT);          // the launcher counts 64-wide tiles
-  int kt_end = kt_begin + p.ktiles_per_split * (BK / KT);
-  if (kt_end > nkt) kt_end = nkt;
+  const KRange kr = batch_entry<KT>(p, (p.K + KT - 1) / KT);          // (the launcher counts 64-wide tiles)
+  const int kt_begin = kr.begin, kt_end = kr.end;
 
   // Operands are addressed through buffer resources (buffer_load ... lds): a 32-bit per-lane byte offset that changes only
   // when the tile starts a new region — the first tile, a new 3x3 tap (conv), the switch to the second concat source
@@ -54,9 +43,7 @@
   const __amdgpu_buffer_rsrc_t rs_a = cm ? cm_rsrc(p) : __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, (int)(p.A2 ? p.a2_bytes : p.a_bytes), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;          // >= every extent the launcher accepts
   const int lrow = lane / SL, lslot = lane % SL;   // position of this lane inside a 1-KiB piece
-  auto swz = [](int r) { return KT == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); };      // source-side XOR swizzle of the 16-byte slots
 
   // rows this lane feeds: piece q = wave*NA + i covers tile rows q*8 .. q*8+7
   long long a_base[NA];
@@ -67,16 +54,11 @@
     const int r = (wave * NA + i) * RPP + lrow;
     const int gr = m0 + r;
     a_ok[i] = gr < p.M;
-    a_kc[i] = (lslot ^ swz(r)) * 8;       // logical k offset (elements) this lane fetches for that row
+    a_kc[i] = (lslot ^ swz_slot<KT>(r)) * 8;       // logical k offset (elements) this lane fetches for that row
     if (MODE == 0) {
       a_base[i] = (long long)gr; a_oy[i] = a_ox[i] = 0;
     } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[i] = rem / p.Wout;
-      a_ox[i] = rem - a_oy[i] * p.Wout;
-      a_base[i] = (long long)b * p.Hin * p.Win;
+      out_pixel(p, gr, a_base[i], a_oy[i], a_ox[i]);
     }
   }
   unsigned b_row[NB];
@@ -87,7 +69,7 @@
     const int r = (wave * NB + i) * RPP + lrow;
     const int gn = EPI == EPI_GEGLU ? geglu_col<WN>(n0, r, p.N) : n0 + r;
     b_ok[i] = gn < p.N && r < BN;
-    b_kc[i] = (lslot ^ swz(r)) * 8;
+    b_kc[i] = (lslot ^ swz_slot<KT>(r)) * 8;
     b_row[i] = (unsigned)(((size_t)(b_ok[i] ? gn : 0) * p.ldb + b_kc[i]) * 2);
   }
 
@@ -96,7 +78,7 @@
   bool a_second = false;           // reading the second concat source
   auto place_a = [&](int k0) {
     if (MODE == 0) {
-      int ld = p.lda, koff = k0;
+      int ld = p.lda, koff = k0;      // written out: profiles/gemm_addressing_isa.txt
       a_second = k0 >= p.K1;
       if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
       a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
@@ -113,7 +95,7 @@
 #pragma unroll
       for (int i = 0; i < NA; ++i) {
         int iy, ix;
-        bool ok = a_ok[i];
+        bool ok = a_ok[i];      // written out: profiles/gemm_addressing_isa.txt
         if (p.mode == E4T_CONV_S1) {
           iy = a_oy[i] + ky - 1; ix = a_ox[i] + kx - 1;
           ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;
@@ -204,12 +186,12 @@
 #pragma unroll
     for (int i = 0; i < FM; ++i) {
       const int r = wm * WM + i * 32 + frow;
-      a_off[i][ks] = r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
+      a_off[i][ks] = frag_off<KT>(r, ks, fhi);
     }
 #pragma unroll
     for (int j = 0; j < FN; ++j) {
       const int r = wn * WN + j * 32 + frow;
-      b_off[j][ks] = BM * KT + r * KT + (((ks * 2 + fhi) ^ swz(r)) * 8);
+      b_off[j][ks] = BM * KT + frag_off<KT>(r, ks, fhi);
     }
   }
   // prologue: LOOK tiles in flight

@@ -26,7 +26,7 @@
   if (p.panel_rows) m0 = (m0 / p.panel_rows) * p.panel_stride + p.panel_off + m0 % p.panel_rows;      // physical first row (panel_rows % 256 == 0)
 
   const int nkt = p.K / BK;
-  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;
+  const int bz = blockIdx.z / p.splitk, sz = blockIdx.z - bz * p.splitk;      // not batch_entry(): above the parent's time with it, profiles/gemm_addressing_ab.txt
   p.A += bz * p.strideA;
   if (p.A2) p.A2 += bz * p.strideA;
   p.B += bz * p.strideB;
@@ -43,7 +43,6 @@
   const __amdgpu_buffer_rsrc_t rs_a = cm ? cm_rsrc(p) : __builtin_amdgcn_make_buffer_rsrc((void*)p.A, 0, (int)p.a_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_a2 = __builtin_amdgcn_make_buffer_rsrc((void*)(p.A2 ? p.A2 : p.A), 0, (int)(p.A2 ? p.a2_bytes : p.a_bytes), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_b = __builtin_amdgcn_make_buffer_rsrc((void*)p.B, 0, (int)p.b_bytes, 0x00020000);
-  constexpr unsigned OOB = 0xFFFF0000u;
   // DMA: one wave-instruction = 16 rows x 64 B; wave w feeds A rows 32w + 16j + (lane >> 2), j = 0, 1, and B pieces w + 8j
   const int drow = lane >> 2, dslot = lane & 3;
   long long a_base[2];
@@ -53,18 +52,13 @@
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int r = wave * 32 + j * 16 + drow;
-    a_kc[j] = (dslot ^ ((r >> 2) & 3)) * 8;
+    a_kc[j] = (dslot ^ ((r >> 2) & 3)) * 8;      // written out: profiles/gemm_addressing_isa.txt
     const int gr = m0 + r;
     a_ok[j] = r < mrows;
     if (MODE == 0) {
       a_base[j] = (long long)gr; a_oy[j] = a_ox[j] = 0;
     } else {
-      const int hw = p.Hout * p.Wout;
-      const int b = gr / hw;
-      const int rem = gr - b * hw;
-      a_oy[j] = rem / p.Wout;
-      a_ox[j] = rem - a_oy[j] * p.Wout;
-      a_base[j] = (long long)b * p.Hin * p.Win;
+      out_pixel(p, gr, a_base[j], a_oy[j], a_ox[j]);
     }
   }
 #pragma unroll
@@ -90,7 +84,7 @@
   bool a_second = false;
   auto place_a = [&](int k0) {
     if (MODE == 0) {
-      int ld = p.lda, koff = k0;
+      int ld = p.lda, koff = k0;      // written out: profiles/gemm_addressing_isa.txt
       a_second = k0 >= p.K1;
       if (a_second) { ld = p.lda2; koff = k0 - p.K1; }
       a_so = __builtin_amdgcn_readfirstlane(koff * 2);          // (wave-uniform by construction; keeps the offset in an SGPR for the compiler)
@@ -104,7 +98,7 @@
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         int iy, ix;
-        bool ok = a_ok[j];
+        bool ok = a_ok[j];      // written out: profiles/gemm_addressing_isa.txt
         if (p.mode == E4T_CONV_S1) {
           iy = a_oy[j] + ky - 1; ix = a_ox[j] + kx - 1;
           ok = ok && iy >= 0 && iy < p.Hin && ix >= 0 && ix < p.Win;

@@ -182,6 +182,17 @@ def check_gemm(hip, emu, dev):
                                                             emu.gemm(A, Bw, reduce_batch=True, alpha=1.0 / nb, out_dtype=f32)), TOLF * 50))
     Ab = A[0].unsqueeze(0).expand(nb, M, K)   # broadcast operand (stride 0)
     out.append(("gemm batched broadcast A", rel(hip.gemm(Ab, Bw), emu.gemm(Ab, Bw)), TOL1))
+    # a batch entry other than 0 on the ping-pong kernels (the hints hold for N = 320: 256 x 256 and 256 x 320 tiles), ragged M
+    A2, B2, bias2 = rnd(g, 2, 300, K, dev=dev), rnd(g, 2, 320, K, scale=0.09, dev=dev), rnd(g, 2, 320, dtype=f32, dev=dev)
+    yr = emu.gemm(A2, B2, bias=bias2)
+    for t in (512, 2320):
+        d = _Cm.GemmDesc(M=300, N=320, K=K, K1=K, lda=K, ldb=K, ldc=320, batch=2, alpha=1.0, tile=t, strideA=300 * K, strideB=320 * K, strideC=300 * 320, strideBias=320)
+        pl = _Cm.GemmPlan()
+        hip.lib.e4t_gemm_plan(_ct.byref(d), _ct.byref(pl))
+        out.append((f"gemm batched t{t}: the plan keeps the hint (got tile {pl.tile})", float(pl.tile != t), 0.0))
+        y = hip.gemm(A2, B2, bias=bias2, tile=t)
+        out.append((f"gemm batched t{t}", rel(y, yr), TOL1))
+        out.append((f"gemm batched t{t}: batch entry 1", rel(y[1], yr[1]), TOL1))
     return out
 
 
