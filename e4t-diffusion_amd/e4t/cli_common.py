@@ -241,3 +241,29 @@ def build_models(dev, base_dir: Optional[str], variant: str, seed: int, freeze_c
             checked_load(enc, f, what=f)
             print(f"Resuming from {f}")
     return unet, enc, text, vae
+
+
+# ---- token merging (e4t/tome.py): a runtime choice of the three command lines, not a property of the run ------------------------
+TOME_ARGS = ("tome_ratio", "tome_no_rand")       # utils.save_config leaves them out of config.json
+
+
+def add_tome_args(p):
+    p.add_argument("--tome_ratio", type=float, default=0.0,
+                   help="token merging (ToMe) around the UNet's self-attention at the input resolution: the share of tokens merged, "
+                        "0 = off (default), at most 0.75")
+    p.add_argument("--tome_no_rand", action="store_true", help="ToMe: the top-left token of every 2x2 cell is the dst token (no per-step draw)")
+
+
+def check_tome_args(p, args):
+    from .tome import MAX_RATIO
+    if not (0.0 <= args.tome_ratio <= MAX_RATIO):
+        p.error(f"--tome_ratio must lie in [0, {MAX_RATIO}]")
+
+
+def apply_tome_args(unet, args):
+    """--tome_ratio > 0: mark the UNet (e4t.tome.apply_tome) with a generator of ToMe's own seeded from --seed; returns the state or None"""
+    if not getattr(args, "tome_ratio", 0.0):
+        return None
+    from . import tome
+    g = torch.Generator().manual_seed(int(getattr(args, "seed", None) or 0))
+    return tome.apply_tome(unet, args.tome_ratio, use_rand=not args.tome_no_rand, generator=g)

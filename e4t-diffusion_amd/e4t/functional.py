@@ -579,6 +579,49 @@ def attention(qkv, kv, B, H, T, S, DH, scale, causal=False):
 
 
 # ----------------------------------------------------------------------------------------------
+# token merging (e4t/tome.py): y = M x and x = residual + U y for a plan of the match kernel.  The match itself
+# is no function of the graph (tome.py runs it outside autograd); the plan is data.
+# ----------------------------------------------------------------------------------------------
+class TomeMergeFn(torch.autograd.Function):
+    """y [B*T', d] = group means of the rows of x [B*T, d]; backward: every token receives its group's gradient / count"""
+
+    @staticmethod
+    def forward(ctx, x, plan):
+        ctx.plan = plan
+        return ops.backend().tome_merge(x, plan, mean=True)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.backend().tome_unmerge(dy.contiguous(), ctx.plan, scale=True), None
+
+
+class TomeUnmergeFn(torch.autograd.Function):
+    """out [B*T, d] = residual + y[map]; backward: dy = the group SUMS of dout, dresidual = dout"""
+
+    @staticmethod
+    def forward(ctx, y, residual, plan):
+        ctx.plan = plan
+        ctx.res_dtype = residual.dtype if residual is not None else None
+        return ops.backend().tome_unmerge(y, plan, residual=residual)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dy = ops.backend().tome_merge(dout.contiguous(), ctx.plan, mean=False) if ctx.needs_input_grad[0] else None
+        dres = None
+        if ctx.res_dtype is not None and ctx.needs_input_grad[1]:
+            dres = dout if dout.dtype == ctx.res_dtype else dout.to(ctx.res_dtype)
+        return dy, dres, None
+
+
+def tome_merge(x, plan):
+    return TomeMergeFn.apply(x, plan)
+
+
+def tome_unmerge(y, plan, residual=None):
+    return TomeUnmergeFn.apply(y, residual, plan)
+
+
+# ----------------------------------------------------------------------------------------------
 # streaming ops
 # ----------------------------------------------------------------------------------------------
 class GegluFn(torch.autograd.Function):

@@ -52,14 +52,25 @@ class BasicTransformerBlock(nn.Module):
         self.norm2 = nn.LayerNorm(dim)
         self.norm3 = nn.LayerNorm(dim)
 
-    def forward(self, hidden_states, encoder_hidden_states=None, prefix=None, **unused):
+    _tome = None      # e4t.tome.apply_tome puts its state object here (token merging around attn1: opt-in)
+
+    def forward(self, hidden_states, encoder_hidden_states=None, prefix=None, hw=None, **unused):
         """hidden_states: (B, T, dim) view of the token matrix; encoder_hidden_states: (B, S, ctx_dim) in ACT dtype.
         ``prefix``: the UNet's shared-prefix cache (unet_2d_condition.py) — the self-attention half of the very first
-        block does not see the text context and is computed once for the two UNet passes of a step."""
+        block does not see the text context and is computed once for the two UNet passes of a step.
+        ``hw``: the (H, W) grid the T tokens lie on (token merging needs it)."""
         B, T, d = hidden_states.shape
+        tome = self._tome if (self._tome is not None and hw is not None and self._tome.applies(T, hw[0], hw[1])) else None
 
         def self_attn_half():
             h = hidden_states.reshape(B * T, d)
+            if tome is not None:
+                # the match reads the block input (pre-norm) outside autograd; attn1 runs on the T' merged rows of LN(x) without its
+                # epilogue residual, which rides in the unmerge instead
+                plan = tome.plan_for(h, B, hw[0], hw[1])
+                n, h = Fn.layer_norm_skip(h, self.norm1.weight, self.norm1.bias, self.norm1.eps)
+                o = self.attn1(Fn.tome_merge(n, plan).view(B, plan.Tm, d))
+                return Fn.tome_unmerge(o.reshape(B * plan.Tm, d), plan, residual=h)
             n, h = Fn.layer_norm_skip(h, self.norm1.weight, self.norm1.bias, self.norm1.eps)
             return self.attn1(n.view(B, T, d), residual=h).reshape(B * T, d)
         shareable = prefix is not None and not getattr(self, "only_cross_attention", False)

@@ -44,6 +44,6 @@ class Transformer2DModel(nn.Module):
         d = h.shape[1]
         h = h.view(B, HW, d)
         for i, blk in enumerate(self.transformer_blocks):
-            h = blk(h, encoder_hidden_states=ctx, prefix=prefix if i == 0 else None)
+            h = blk(h, encoder_hidden_states=ctx, prefix=prefix if i == 0 else None, hw=(m.H, m.W))
         y = Fn.linear(h.reshape(B * HW, d), self.proj_out.weight, self.proj_out.bias, self._pout, residual=res)
         return FMap(y, B, m.H, m.W)

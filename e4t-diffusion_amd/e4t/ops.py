@@ -119,6 +119,51 @@ class WOTable:
         return max(e.col for e in self.entries)
 
 
+class TomePlan:
+    """A token-merging plan (e4t_tome_match in include/e4t_hip.h): plain int32 data for a batch of B images of T tokens of which r
+    are merged.  `buf` holds map [B][T] | row_tok [B][T'] | seg_off [B][nd+1] | seg_src [B][r] back to back (T' = T - r, nd = T/4) —
+    a buffer from the match kernel carries that kernel's scratch behind them; the fields below are views."""
+
+    def __init__(self, buf: torch.Tensor, B: int, T: int, r: int):
+        assert buf.dtype == torch.int32 and buf.dim() == 1 and buf.is_contiguous()
+        assert T % 4 == 0 and 1 <= r <= T - T // 4 and buf.numel() >= B * (2 * T + T // 4 + 1)
+        self.buf, self.B, self.T, self.r = buf, B, T, r
+        self.nd, self.Tm = T // 4, T - r
+
+    def _field(self, off, rows):
+        return self.buf[off:off + self.B * rows].view(self.B, rows)
+
+    @property
+    def map(self):
+        return self._field(0, self.T)
+
+    @property
+    def row_tok(self):
+        return self._field(self.B * self.T, self.Tm)
+
+    @property
+    def seg_off(self):
+        return self._field(self.B * (self.T + self.Tm), self.nd + 1)
+
+    @property
+    def seg_src(self):
+        return self._field(self.B * (self.T + self.Tm + self.nd + 1), self.r)
+
+    def fields(self):
+        return {"map": self.map, "row_tok": self.row_tok, "seg_off": self.seg_off, "seg_src": self.seg_src}
+
+    @classmethod
+    def from_fields(cls, map, row_tok, seg_off, seg_src):
+        B, T = map.shape
+        r = seg_src.shape[1]
+        buf = torch.cat([t.reshape(-1).to(torch.int32) for t in (map, row_tok, seg_off, seg_src)]).contiguous()
+        return cls(buf, B, T, r)
+
+    def to(self, device):
+        n = self.B * (2 * self.T + self.nd + 1)
+        return TomePlan(self.buf[:n].to(device), self.B, self.T, self.r)
+
+
 class HipBackend:
     """The one and only product backend: libe4t_hip.so on the current CUDA(HIP) device."""
 
@@ -721,6 +766,43 @@ class HipBackend:
         dev = table.entries[0].W.device
         self._pack_table(table, dev)
         _C.check(self.lib.e4t_weight_prepare(_ptr(table.dev), len(table.entries), table.max_row, table.max_col, _stream()), "e4t_weight_prepare")
+
+    # ------------------------------------------------------------------ token merging (csrc/tome.hip)
+    def tome_match(self, x, B, h, w, r, choice=None, out=None):
+        """bipartite soft matching of the rows of x [B*h*w, d] (bf16, row stride arbitrary) -> TomePlan.  choice: int32 [(h/2)*(w/2)]
+        on the device (which token of every 2x2 cell is dst) or None (top-left).  out: a plan buffer to reuse (graph replay)."""
+        _rowmajor(x, "tome_match x")
+        T, d = h * w, x.shape[1]
+        assert x.dtype == bf16 and x.shape[0] == B * T
+        assert choice is None or (choice.dtype == torch.int32 and choice.is_contiguous() and choice.numel() == T // 4)
+        n = B * self.lib.e4t_tome_plan_ints(T, r)
+        buf = out.buf if out is not None else torch.empty(max(n, 1), dtype=torch.int32, device=x.device)
+        assert buf.numel() >= n
+        self._timed("tome_match", 2.0 * B * (3 * T // 4) * (T // 4) * d, lambda: _C.check(self.lib.e4t_tome_match(
+            _ptr(x), x.stride(0), B, h, w, d, r, _ptr(choice), _ptr(buf), _stream()), "e4t_tome_match"), 2.0 * B * T * d)
+        return out if out is not None else TomePlan(buf, B, T, r)
+
+    def tome_merge(self, x, plan, mean=True):
+        """y [B*T', d] = the plan's merge of the rows of x [B*T, d]: group means (mean=True) or sums"""
+        _rowmajor(x, "tome_merge x")
+        B, T, r, d = plan.B, plan.T, plan.r, x.shape[1]
+        assert x.dtype == bf16 and x.shape[0] == B * T
+        y = torch.empty((B * (T - r), d), dtype=bf16, device=x.device)
+        self._timed("tome_merge", 0.0, lambda: _C.check(self.lib.e4t_tome_merge(
+            _ptr(x), x.stride(0), _ptr(plan.buf), _ptr(y), d, B, T, r, d, int(mean), _stream()), "e4t_tome_merge"), 2.0 * B * (2 * T - r) * d)
+        return y
+
+    def tome_unmerge(self, y, plan, residual=None, scale=False):
+        """x [B*T, d] = (residual +) y[map] (/ count when scale) for y [B*T', d]"""
+        _rowmajor(y, "tome_unmerge y")
+        B, T, r, d = plan.B, plan.T, plan.r, y.shape[1]
+        assert y.dtype == bf16 and y.shape[0] == B * (T - r)
+        assert residual is None or (residual.dtype == bf16 and residual.is_contiguous() and residual.shape == (B * T, d))
+        x = torch.empty((B * T, d), dtype=bf16, device=y.device)
+        self._timed("tome_unmerge", 0.0, lambda: _C.check(self.lib.e4t_tome_unmerge(
+            _ptr(y), y.stride(0), _ptr(plan.buf), _ptr(residual), _ptr(x), d, B, T, r, d, int(scale), _stream()), "e4t_tome_unmerge"),
+            2.0 * B * ((3 if residual is not None else 2) * T - r) * d)
+        return x
 
     def probe_mfma(self, device):
         rows = torch.zeros((64, 16), dtype=f32, device=device)

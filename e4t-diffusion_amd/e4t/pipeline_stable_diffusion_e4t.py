@@ -36,6 +36,7 @@ import numpy as np
 import torch
 
 from . import ops
+from . import tome
 from .schedulers import DDIMScheduler
 
 
@@ -272,6 +273,7 @@ class StableDiffusionE4TPipeline:
             for i in range(len(timesteps)):
                 t_buf.copy_(timesteps[i:i + 1])
                 row.copy_(table[i])
+                tome.new_step(self.unet)         # token merging (opt-in): one draw per denoising step, into its fixed buffer
                 if plan.noisy[i]:                # outside the graph, the same draw (generator, order) as the generic step()
                     bufs["noise"].copy_(sch._step_noise(latents.shape, torch.float32, device, generator))
                 if not use_graph:
@@ -292,6 +294,7 @@ class StableDiffusionE4TPipeline:
             if "generator" in accepted and generator is not None:
                 extra["generator"] = generator
             for i, t in enumerate(timesteps):
+                tome.new_step(self.unet)
                 pred = self._model_step(latents, t, s)
                 if cfg:
                     u, c = pred.chunk(2)

@@ -26,6 +26,7 @@ import torch.nn.functional as F
 
 from . import functional as Fn
 from . import ops
+from . import tome
 
 f32 = torch.float32
 
@@ -816,6 +817,7 @@ class E4TTrainer:
                     and loss_mask is None):
                 return self._graphed_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents)
             return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale, loss_mask)
+        tome.new_step(self.unet)       # token merging (opt-in): this step's draw, outside any capture; nothing for an unmarked UNet
         ts = self._training_stream()
         if ts is None or self._step_graph_on:          # (a replayed graph's branches run on the graph executor's own streams, wherever it is launched)
             return run()

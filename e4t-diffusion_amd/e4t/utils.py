@@ -42,6 +42,8 @@ def save_e4t_encoder(encoder, save_dir):
 
 
 def save_config(args_dict, save_dir):
+    from .cli_common import TOME_ARGS
+    args_dict = {k: v for k, v in args_dict.items() if k not in TOME_ARGS}      # token merging is a runtime choice, not part of the run
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "config.json"), "w") as f:
         json.dump(args_dict, f, indent=2, default=str)

@@ -362,6 +362,35 @@ int e4t_adamw_rank(float* p, float* m, float* v, const void* G, const void* Z, i
                    e4t_stream stream);
 int e4t_sumsq_partial(const float* g, long long n, float* partial, int nblocks, e4t_stream stream);                      /* tuning_e4t.py:335 grad-norm */
 
+/* ---------------------------------------------------------------- token merging (tome.hip) ---------- */
+/* Token merging (ToMe) around the self-attention of a transformer block: the reference's open TODO "Support ToMe for more efficient training"
+ * (README.md:116), at the `attn1` call of BasicTransformerBlock (e4t/models/attention.py:181-332).  Tokens are the rows of x [B][T = h*w][ldx]
+ * (bf16) on an h x w grid cut into 2 x 2 cells: one token per cell is a dst token (nd = T/4; which one: choice[(h/2)*(w/2)], values cy*2+cx,
+ * shared by the batch, NULL = top-left), the other ns = 3T/4 are src tokens, numbered in ascending token order.
+ *
+ * e4t_tome_match: x^ = bf16(x / ||x||_2) (fp32 division; ||x||^2 summed exactly), score[i][j] = x^_src[i] . x^_dst[j] (fp32 accumulation on the
+ * matrix cores, never stored), node_max / node_idx = max / argmax over j (ties: lowest j); the r src with the largest node_max (ties: lower src
+ * position) are merged into their node_idx.  The result is the PLAN, int32 in device memory, for T' = T - r merged rows per image:
+ *   map     [B][T]     merged row of every token
+ *   row_tok [B][T']    token that owns each merged row: dst token j for row j < nd, then the unmerged src tokens in ascending order
+ *   seg_off [B][nd+1]  CSR offsets into seg_src of the src tokens merged into each dst row (count of row j < nd = 1 + seg_off[j+1] - seg_off[j])
+ *   seg_src [B][r]     those src tokens, ascending within a segment
+ * laid out back to back in this order (B * (2T + nd + 1) ints: all that e4t_tome_merge / e4t_tome_unmerge read, so a plan may come from anywhere),
+ * followed by the match's own scratch: a buffer for e4t_tome_match holds B * e4t_tome_plan_ints(T, r) ints (0 for an invalid T / r).
+ * No host read, no float atomics: the plan is bitwise equal from run to run.  -22 before any launch for d % 16 != 0 (or d > 1280), odd h or w,
+ * T > 16384, r < 1, r > ns, rows not 16-byte aligned. */
+size_t e4t_tome_plan_ints(int T, int r);
+int e4t_tome_match(const void* x, int ldx, int B, int h, int w, int d, int r, const int* choice, int* plan, e4t_stream stream);
+/* y [B][T'][ldy] = M . x: row j < nd = x[dst token j] + the rows of its segment of seg_src in order (fp32 accumulation), divided by the count when
+ * mean (the forward merge; mean = 0 sums: the backward of e4t_tome_unmerge); rows of count 1 are bitwise copies of x[row_tok].  README.md:116;
+ * e4t/models/attention.py:181-332.  d % 8 == 0, 16-byte aligned rows. */
+int e4t_tome_merge(const void* x, int ldx, const int* plan, void* y, int ldy, int B, int T, int r, int d, int mean, e4t_stream stream);
+/* x_out [B][T][ldx] = (residual [B][T][ldx] +) y[map] (/ count[map], fp32 division, when scale_inv_count): the forward unmerge carries the block's
+ * skip connection and no scale; the backward of e4t_tome_merge(mean = 1) has no residual and scale_inv_count = 1.  README.md:116;
+ * e4t/models/attention.py:181-332.  16-byte accesses along d: d % 8 == 0, 16-byte aligned rows. */
+int e4t_tome_unmerge(const void* y, int ldy, const int* plan, const void* residual, void* x_out, int ldx, int B, int T, int r, int d,
+                     int scale_inv_count, e4t_stream stream);
+
 /* ---------------------------------------------------------------- data-parallel collectives (comm.hip) ---------- */
 /* An RCCL communicator owned by the library, for a host that does not bring torch.distributed: replaces the DDP reducer accelerate wraps
  * the reference's models with (pretrain_e4t.py:410-412 `accelerator.prepare`, :648 `accelerator.backward`; tuning_e4t.py:197-200, :328).

@@ -46,7 +46,11 @@ def parse_args():
     p.add_argument("--random_init", action="store_true", help="random weights + offline tokenizer (no checkpoint needed)")
     p.add_argument("--unet_variant", type=str, default="sd14", choices=["sd14", "sd21"])
     p.add_argument("--output", type=str, default="grid.png")
-    return p.parse_args()
+    from e4t import cli_common as cc
+    cc.add_tome_args(p)
+    args = p.parse_args()
+    cc.check_tome_args(p, args)
+    return args
 
 
 def setup(args, dev):
@@ -118,6 +122,7 @@ def setup(args, dev):
             checked_load(text, os.path.join(d, "text_encoder.pt"))        # written by --train_text_encoder: already holds the placeholder row
     unet.requires_grad_(False)
     enc.requires_grad_(False)
+    cc.apply_tome_args(unet, args)
     if args.enable_xformers_memory_efficient_attention:
         pipe.enable_xformers_memory_efficient_attention()
     return dict(pipe=pipe, unet=unet, enc=enc, text=text, vae=vae, tokenizer=tok, scheduler=sched, base_dir=base if not args.random_init else None)

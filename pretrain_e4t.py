@@ -77,7 +77,10 @@ def parse_args():
     p.add_argument("--train_mask_dataset", type=str, default=None, metavar="DIR[::DIR]",
                    help="loss masks for the masked diffusion loss: one directory per --train_image_dataset directory, in the same order, "
                         "holding <rel>/<stem>.png (or an image extension) for every image <rel>/<stem>.<ext>")
+    from e4t import cli_common as cc
+    cc.add_tome_args(p)
     args = p.parse_args()
+    cc.check_tome_args(p, args)
     if args.train_mask_dataset and (args.webdataset or args.iterable_dataset or args.synthetic_data):
         p.error("--train_mask_dataset needs image directories: it cannot be combined with --webdataset, --iterable_dataset or --synthetic_data")
     if args.use_8bit_adam:
@@ -146,6 +149,7 @@ def setup(args, dev, world=1, rank=0):
     prompt_templates = cc.resolve_prompt_templates(args.prompt_template)                                  # :570-581
     if args.enable_xformers_memory_efficient_attention:
         unet.enable_xformers_memory_efficient_attention()        # selects the native flash-attention processor
+    cc.apply_tome_args(unet, args)
     lr = args.learning_rate
     if args.scale_lr:                                                                                      # :354-361
         lr = args.learning_rate * args.gradient_accumulation_steps * args.train_batch_size * world

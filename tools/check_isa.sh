@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../e4t-diffusion_amd/csrc"
 OUT=${1:-../../profiles/r04_isa_resources.txt}
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result -w"
 echo "# $(git -C ../.. rev-parse --short HEAD)  hipcc $FLAGS" > $OUT
-for f in gemm attention norm wo elementwise image core; do
+for f in gemm attention norm wo elementwise image core tome; do
   EXTRA=""; [ $f = image ] && EXTRA="-ffp-contract=off"
   hipcc $FLAGS $EXTRA -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/isa_$f.o 2> /tmp/isa_$f.rpt &
   hipcc $FLAGS $EXTRA -S --cuda-device-only $f.hip -o /tmp/isa_$f.s 2> /dev/null &
@@ -17,7 +17,7 @@ python3 - "$OUT" <<'PY'
 import re, subprocess, sys
 out = open(sys.argv[1], "a")
 out.write("file,kernel,vgprs,agprs,scratch_bytes_per_lane,occupancy_waves_per_simd,lds_bytes_per_block,waterfall_loops_around_lds_dma\n")
-for f in "gemm attention norm wo elementwise image core".split():
+for f in "gemm attention norm wo elementwise image core tome".split():
     rpt = open(f"/tmp/isa_{f}.rpt").read()
     asm = open(f"/tmp/isa_{f}.s").read().split("\n")
     # waterfall loops per kernel symbol

@@ -56,7 +56,10 @@ def parse_args():
     p.add_argument("--unet_variant", type=str, default="sd14", choices=["sd14", "sd21"])
     p.add_argument("--train_mask_path", type=str, default=None, metavar="FILE",
                    help="loss mask of --train_image_path (grey image of the same size): the diffusion loss is weighted by it")
+    from e4t import cli_common as cc
+    cc.add_tome_args(p)
     a = p.parse_args()
+    cc.check_tome_args(p, a)
     if a.train_mask_path and not a.train_image_path:
         p.error("--train_mask_path needs --train_image_path")
     if a.use_8bit_adam:
@@ -99,6 +102,7 @@ def setup(args, dev):
     prompt_templates = cc.resolve_prompt_templates(args.prompt_template)
     if args.enable_xformers_memory_efficient_attention:
         unet.enable_xformers_memory_efficient_attention()
+    cc.apply_tome_args(unet, args)
     ga = args.gradient_accumulation_steps
     lr = args.learning_rate * (args.train_batch_size * ga if args.scale_lr else 1)                  # :149-156 (one process)
     tr = E4TTrainer(unet, enc, text, vae, lr=lr, domain_embed_scale=args.domain_embed_scale, reg_lambda=args.reg_lambda,
