@@ -163,7 +163,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* partial, int nchunk, int G, int BG, float inv_n, float eps,
+__global__ __launch_bounds__(256) void gn_finalize_kernel(const float* partial, int nchunk, int G, int BG, double inv_n, float eps,
                                                           float* mean_rstd) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= BG) return;
@@ -197,6 +197,23 @@ __device__ __forceinline__ void gn_block_sum_partials(const float* partial_b /* 
     }
     s = wave_sum_f64(s); q = wave_sum_f64(q);
     if (lane == 0) fin(g, s, q);
+  }
+  __syncthreads();
+}
+
+// The same walk over CENTRED partials (gn_stats_cols_kernel): partial = (s_c, M2_c = q_c - s_c^2 / n_c) per chunk of n_c values.  fin gets
+// (g, sum s_c, sum M2_c, sum s_c^2): with equal n_c the raw second moment is Q = sum M2_c + sum s_c^2 / n_c, formed in double by the caller.
+template <typename Fin>
+__device__ __forceinline__ void gn_block_sum_centred(const float* partial_b, int nchunk, int G, Fin fin) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  for (int g = wave; g < G; g += nw) {
+    double s = 0.0, m2 = 0.0, ss = 0.0;
+    for (int c = lane; c < nchunk; c += 64) {
+      const float2 pp = *(const float2*)(partial_b + ((size_t)c * G + g) * 2);
+      s += pp.x; m2 += pp.y; ss += (double)pp.x * (double)pp.x;
+    }
+    s = wave_sum_f64(s); m2 = wave_sum_f64(m2); ss = wave_sum_f64(ss);
+    if (lane == 0) fin(g, s, m2, ss);
   }
   __syncthreads();
 }
@@ -251,20 +268,25 @@ __device__ __forceinline__ void gn_apply_body(const GNSrc& s, const GNMap& m, in
 template <bool FUSED, int NS>
 __global__ __launch_bounds__(256) void gn_apply_kernel(GNSrc s, const float* mean_rstd, const float* gamma, const float* beta,
                                                        bf16_t* y, int HW, int G, int pix_per_chunk, int silu,
-                                                       const float* partial, int npart, float inv_n, float eps, float* mean_rstd_out) {
+                                                       const float* partial, int npart, double inv_n, float eps, float* mean_rstd_out,
+                                                       double centred_nc /* > 0: the partials are centred, over chunks of this many values */) {
   const int C = s.C1 + s.C2, cpg = C / G;
   const GNMap m(C);
   const int b = blockIdx.y;
   __shared__ float mr_lds[512];
   if (FUSED) {
-    gn_block_sum_partials(partial + (size_t)b * npart * G * 2, npart, G, [&](int g, double sm, double sq) {
+    auto fin = [&](int g, double sm, double sq) {
       const double mean = sm * inv_n;
       double var = sq * inv_n - mean * mean;
       if (var < 0.0) var = 0.0;
       const float mf = (float)mean, rf = (float)(1.0 / sqrt(var + (double)eps));
       mr_lds[g * 2] = mf; mr_lds[g * 2 + 1] = rf;
       if (blockIdx.x == 0) { mean_rstd_out[((size_t)b * G + g) * 2] = mf; mean_rstd_out[((size_t)b * G + g) * 2 + 1] = rf; }
-    });
+    };
+    if (centred_nc > 0.0)
+      gn_block_sum_centred(partial + (size_t)b * npart * G * 2, npart, G,
+                           [&](int g, double sm, double m2, double ss) { fin(g, sm, m2 + ss / centred_nc); });
+    else gn_block_sum_partials(partial + (size_t)b * npart * G * 2, npart, G, fin);
   } else {
     gn_stage_stats(mr_lds, mean_rstd + (size_t)b * G * 2, G);
   }
@@ -474,7 +496,7 @@ __device__ __forceinline__ double gn_slab_block_sum(double v, double* red) {    
 
 template <int NI, bool SILU>
 __global__ __launch_bounds__(256) void gn_slab_fwd_kernel(GNSrc s, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd,
-                                                          int HW, int G, float inv_n, float eps) {
+                                                          int HW, int G, double inv_n, float eps) {
   __shared__ double red[4];
   const int C = s.C1 + s.C2, cpg = C / G, q4 = cpg >> 2, items = HW * q4;
   const int b = blockIdx.y, g = blockIdx.x;
@@ -587,6 +609,11 @@ __global__ __launch_bounds__(256) void gn_slab_bwd_kernel(GNSrc s, const bf16_t*
   }
 }
 
+// 1 / n of a (batch, group) for the forward statistics, in double: it multiplies the fp64 sums in mean = S / n, var = Q / n - mean^2, and a
+// reciprocal rounded to fp32 (relative error up to 6e-8 wherever n is no power of two) comes back in var multiplied by mean^2 / var — an
+// rstd off by 1.2e-4 at mean = 64, sigma = 0.5 (tests/kernel_checks.py, the shifted-mean cases).  The backward's 1 / n scales gradients only.
+double gn_inv_n(int C, int G, int HW) { return 1.0 / ((double)(C / G) * (double)HW); }
+
 // quads per thread of the slab kernels for this shape, 0 = not eligible
 int gn_slab_ni(int C1, int C2, int HW, int G) {
   const bool off = false;
@@ -600,7 +627,7 @@ int gn_slab_ni(int C1, int C2, int HW, int G) {
 template <int NI>
 void gn_slab_fwd_launch(const GNSrc& s, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd, int Bn, int HW, int G, float eps,
                         int silu, hipStream_t st) {
-  const float inv_n = 1.f / ((float)((s.C1 + s.C2) / G) * (float)HW);
+  const double inv_n = gn_inv_n(s.C1 + s.C2, G, HW);
   if (silu) hipLaunchKernelGGL((gn_slab_fwd_kernel<NI, true>), dim3(G, Bn), dim3(256), 0, st, s, gamma, beta, y, mean_rstd, HW, G, inv_n, eps);
   else hipLaunchKernelGGL((gn_slab_fwd_kernel<NI, false>), dim3(G, Bn), dim3(256), 0, st, s, gamma, beta, y, mean_rstd, HW, G, inv_n, eps);
 }
@@ -879,7 +906,7 @@ extern "C" int e4t_groupnorm_stats(const void* x1, int C1, const void* x2, int C
   E4T_CHECK_LAUNCH("gn_stats_kernel");
   const int BG = Bn * G;
   hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(BG, 4)), dim3(256), 0, st, (const float*)workspace, ch, G, BG,
-                     1.f / ((float)(C / G) * (float)HW), eps, mean_rstd);
+                     gn_inv_n(C, G, HW), eps, mean_rstd);
   E4T_CHECK_LAUNCH("gn_finalize_kernel");
   return 0;
 }
@@ -892,9 +919,9 @@ extern "C" int e4t_groupnorm_apply(const void* x1, int C1, const void* x2, int C
   GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
   E4T_LOG_LAUNCH("gn_apply_kernel<false, %d>|B%d HW%d C%d G%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C1 + C2, G, 4.0 * Bn * (double)HW * (C1 + C2));
   if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<false, 2>), dim3(ch, Bn), dim3(256), 0, (hipStream_t)stream, s, mean_rstd, gamma, beta, (bf16_t*)y, HW, G, ppc,
-                     silu, (const float*)nullptr, 0, 0.f, 0.f, (float*)nullptr);
+                     silu, (const float*)nullptr, 0, 0.0, 0.f, (float*)nullptr, 0.0);
   else hipLaunchKernelGGL((gn_apply_kernel<false, 1>), dim3(ch, Bn), dim3(256), 0, (hipStream_t)stream, s, mean_rstd, gamma, beta, (bf16_t*)y, HW, G, ppc,
-                     silu, (const float*)nullptr, 0, 0.f, 0.f, (float*)nullptr);
+                     silu, (const float*)nullptr, 0, 0.0, 0.f, (float*)nullptr, 0.0);
   E4T_CHECK_LAUNCH("gn_apply_kernel");
   return 0;
 }
@@ -902,7 +929,8 @@ extern "C" int e4t_groupnorm_apply(const void* x1, int C1, const void* x2, int C
 // Chunk partials (the format gn_stats_kernel writes: partial[b][chunk][g][2]) from the column statistics the producing GEMM /
 // conv epilogue left behind (gemm.hip, write_tile): cs[blk][c][2] = (sum, sum of squares) of channel c over the 32 pixels of
 // block blk.  One workgroup per (chunk of 32-pixel blocks, batch entry): thread t owns columns t, t+256, ...; a few KB .. MB of
-// statistics are read instead of a pass over the whole activation.  Deterministic (fixed summation order).
+// statistics are read instead of a pass over the whole activation.  Deterministic (fixed summation order).  The second entry of a
+// partial is CENTRED here (see below): only gn_apply_kernel<true, *> with centred_nc > 0 consumes these partials.
 namespace {
 __global__ __launch_bounds__(256) void gn_stats_cols_kernel(const float* cs1, int C1, const float* cs2, int C2, int nblk_img, int blk_per_chunk,
                                                             int G, float* partial) {
@@ -922,10 +950,15 @@ __global__ __launch_bounds__(256) void gn_stats_cols_kernel(const float* cs1, in
   }
   __syncthreads();
   if ((int)threadIdx.x < G) {
-    float ta = 0.f, tb = 0.f;
+    double ta = 0.0, tb = 0.0;
     for (int c = threadIdx.x * cpg; c < (threadIdx.x + 1) * cpg; ++c) { ta += lds[c * 2]; tb += lds[c * 2 + 1]; }
+    // CENTRED: (s, M2 = q - s^2 / n_c).  A raw sum of squares stored in fp32 loses what var = Q / n - mean^2 needs once mean^2 >> var
+    // (mean 64, sigma 0.5: the partial is 1.3e6, an fp32 ulp 0.125, and the rstd came out 1.9e-4 off); M2 is of the size of n_c var.
+    const float sf = (float)ta;
+    const double nc = (double)blk_per_chunk * 32.0 * (double)cpg;
+    double m2 = tb - (double)sf * (double)sf / nc;      // (around the stored, rounded s: the consumer adds back exactly sf^2 / n_c)
     float* o = partial + (((size_t)b * gridDim.x + chunk) * G + threadIdx.x) * 2;
-    o[0] = ta; o[1] = tb;
+    o[0] = sf; o[1] = (float)m2;
   }
 }
 }  // namespace
@@ -951,9 +984,9 @@ extern "C" int e4t_groupnorm_fwd_cs(const void* x1, int C1, const float* cs1, co
   E4T_CHECK_LAUNCH("gn_stats_cols_kernel");
   E4T_LOG_LAUNCH("gn_apply_kernel<true, %d>|B%d HW%d C%d G%d silu%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, silu, 4.0 * Bn * (double)HW * C);
   if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<true, 2>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, npart, 1.f / ((float)(C / G) * (float)HW), eps, mean_rstd);
+                     (const float*)workspace, npart, gn_inv_n(C, G, HW), eps, mean_rstd, (double)(nblk / npart) * 32.0 * (double)(C / G));
   else hipLaunchKernelGGL((gn_apply_kernel<true, 1>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, npart, 1.f / ((float)(C / G) * (float)HW), eps, mean_rstd);
+                     (const float*)workspace, npart, gn_inv_n(C, G, HW), eps, mean_rstd, (double)(nblk / npart) * 32.0 * (double)(C / G));
   E4T_CHECK_LAUNCH("gn_apply_kernel");
   return 0;
 }
@@ -977,9 +1010,9 @@ extern "C" int e4t_groupnorm_fwd(const void* x1, int C1, const void* x2, int C2,
   E4T_CHECK_LAUNCH("gn_stats_kernel");
   E4T_LOG_LAUNCH("gn_apply_kernel<true, %d>|B%d HW%d C%d G%d silu%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, silu, 4.0 * Bn * (double)HW * C);
   if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<true, 2>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, ch, 1.f / ((float)(C / G) * (float)HW), eps, mean_rstd);
+                     (const float*)workspace, ch, gn_inv_n(C, G, HW), eps, mean_rstd, 0.0);
   else hipLaunchKernelGGL((gn_apply_kernel<true, 1>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, ch, 1.f / ((float)(C / G) * (float)HW), eps, mean_rstd);
+                     (const float*)workspace, ch, gn_inv_n(C, G, HW), eps, mean_rstd, 0.0);
   E4T_CHECK_LAUNCH("gn_apply_kernel");
   return 0;
 }

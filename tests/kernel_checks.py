@@ -8,12 +8,14 @@ bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumu
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
 
-Importable without a GPU: the attention and conv case lists, slices() and conv_slices() are shared with CPU tests (test_gemm_dispatch.py,
-test_attention_slices_cpu.py, test_conv_slices_cpu.py).
+Importable without a GPU: the attention, conv and norm case lists, slices(), conv_slices() and norm_slices(), norm_plan() and the fp64 norm
+references are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py, test_conv_slices_cpu.py, test_norm_slices_cpu.py,
+test_norm_plan_cpu.py).
 """
 from __future__ import annotations
 
 import math
+from collections import namedtuple
 
 import torch
 
@@ -881,80 +883,713 @@ def _check_attention_determinism(hip, emu, dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ norms
+# Plain data and host arithmetic, importable without a GPU: tests/test_norm_plan_cpu.py holds norm_plan() against a hand-written table of every
+# logged instantiation of norm.hip, tests/test_norm_slices_cpu.py holds a rounding-only model to half the tolerance on every row norm_slices()
+# emits for these cases and measures the statistics tolerance (STAT_TOL).
+f64 = torch.float64
+GNCase = namedtuple("GNCase", "B HW C1 C2 G silu eps shift adds seed new")
+GN_SLAB_MAX = 10240      # norm.hip: elements of one (batch, group) slab the one-launch kernels take
+GN_MIN_REGION = 256      # gn_slices: values in the smallest region of pixel rows it reports
+
+
+def _gn(B, HW, C1, C2, silu, G=32, eps=1e-5, shift=0.0, adds=((True, True),)):
+    adds = tuple((a1, a2 and C2 > 0) for a1, a2 in adds)
+    return GNCase(B, HW, C1, C2, G, silu, eps, shift, adds, 0, True)
+
+
+# (B, HW, C1, C2, G, silu) of the first list: the cases check_norms has always run, with their seeds (140 + i) and their shortcut gradients (add1
+# on the even ones, add2 wherever there is a second source except on case 3).  The last six take the one-launch slab kernels (HW x C/G <= 10240,
+# C/G % 4 == 0, no group straddling the concat): 3 / 5 / 10 quads per thread, two sources, with and without SiLU / shortcut gradients.
+_GN_FIRST = [(2, 64, 64, 0, 32, True), (3, 256, 320, 0, 32, True), (2, 100, 320, 640, 32, True), (2, 64, 1280, 1280, 32, False), (16, 4096, 320, 0, 32, True),
+             (2, 64, 1280, 0, 32, True), (3, 256, 1280, 0, 32, True), (2, 64, 1280, 1280, 32, True), (2, 60, 640, 0, 32, True), (1, 256, 640, 640, 32, False),
+             (2, 64, 640, 640, 32, True)]
+GN_CASES = [GNCase(B, HW, C1, C2, G, silu, 1e-5, 0.0, ((i % 2 == 0, bool(C2) and i != 3),), 140 + i, False) for i, (B, HW, C1, C2, G, silu) in enumerate(_GN_FIRST)]
+GN_NEW_CASES = [
+    _gn(2, 256, 1280, 1280, True),       # chunked, two slots, two sources: the UNet's 16 x 16 up-block concat (gn_apply<true, 2>, gn_stats<2>, colstats with cs2)
+    _gn(2, 256, 1280, 640, True, adds=((True, False), (False, True))),      # C = 1920: 240 chunk lanes, 16 idle threads; cpg = 60 straddles the concat and the 8-channel chunks
+    _gn(2, 260, 320, 0, True),           # ch = 32, ppc = 9: three empty trailing chunks, a ragged last one (8 of 9 pixels)
+    _gn(1, 257, 1280, 0, False),         # one pixel over the slab limit (HW * cpg = 10280): chunked; three empty trailing chunks, 5 of 9 pixels in the last
+    _gn(2, 16, 320, 320, False),         # slab NI = 3 without SiLU: 80 items, trips 1 and 2 fully masked (the `items - 1` clamp)
+    _gn(2, 100, 640, 640, True),         # slab NI = 5: 1000 items, ragged
+    _gn(2, 100, 1280, 1280, True),       # slab NI = 10: 2000 items, two trips fully masked, one ragged
+    _gn(2, 64, 64, 0, False, eps=1e-6),  # Transformer2DModel.norm's eps
+    _gn(48, 1024, 64, 0, True),          # ch = 21, 32 blocks of 32 pixels: 32 % 21 != 0, groupnorm_fwd falls back to the statistics pass
+    _gn(2, 1024, 320, 0, True, shift=64.0),      # mean^2 / var ~ 1.5e4: pins the fp64 finalisation of E[x^2] - mean^2 (chunked, and via column statistics)
+    _gn(2, 64, 1280, 0, True, shift=64.0),       # ... and in the slab kernel
+]
+GN_NEW_CASES = [c._replace(seed=1400 + i) for i, c in enumerate(GN_NEW_CASES)]
+GN_CASES += GN_NEW_CASES
+# (M, D).  The last three of the first eight take the several-rows-per-wave forward (4 / 2 / 2 rows for 1 / 2 / 3 chunks per lane) with a ragged last wave
+LN_CASES = [(37, 64), (1000, 320), (4112, 1280), (300, 768), (128, 1024), (8195, 320), (4101, 640), (4111, 1280),
+            (300, 1280),       # ln_fwd_kernel<3, 1, false>: D = 1280 with fewer than 2731 rows (the 16 x 16 transformer at small batch)
+            (5, 1536),         # the largest D, fewer rows than one block
+            (4101, 200)]       # D % 64 != 0 for the parameter-gradient column blocks; 25 of 64 lanes active
+LN_NEED_STATS_CASE = (300, 768)      # once more with need_stats=False (mean_rstd == NULL)
+# Worst |d mean| * rstd and |d rstd| / rstd of a (batch, group) against fp64.  tests/test_norm_slices_cpu.py measures the model of the kernels'
+# statistics (one fp32 chain per chunk or slab thread, fp64 across, fp32 store) at 6.0e-6 — the fp32 store of a mean of 64 at rstd 1.9, on the
+# shifted-mean cases; 1.05e-6 on every other case — and asserts STAT_TOL == min(4 x that, 1e-5): the cap binds.
+STAT_TOL = 1e-5
+
+
+def gn_tag(c):
+    return f"groupnorm B{c.B} HW{c.HW} C{c.C1}+{c.C2} silu{int(c.silu)}" + (f" eps{c.eps:g}" if c.eps != 1e-5 else "") + (f" shift{c.shift:g}" if c.shift else "")
+
+
+def gn_slab_ni(C1, C2, HW, G):
+    """norm.hip gn_slab_ni: quads per thread of the slab kernels, 0 = not eligible"""
+    cpg = (C1 + C2) // G
+    if cpg % 4 != 0 or (C2 > 0 and C1 % cpg != 0) or HW * cpg > GN_SLAB_MAX:
+        return 0
+    ni = -(-HW * (cpg // 4) // 256)
+    return 3 if ni <= 3 else 5 if ni <= 5 else 10
+
+
+def gn_chunks(B, HW):
+    """norm.hip gn_chunks: workgroups per batch entry of the chunked kernels"""
+    return min(max(1024 // max(B, 1), 1), max(HW // 8, 1), 256)
+
+
+def ln_rows_per_wave(M, D, xf32=False):
+    """norm.hip launch_ln_fwd: (16-byte chunks per lane, rows per wave)"""
+    ncl = -(-(D // 8) // 64)
+    return ncl, (1 if (M * ncl < 256 * 4 * 8 or xf32) else 4 if ncl == 1 else 2)
+
+
+def norm_plan(case):
+    """What the library does with a case, restated from norm.hip's dispatch (gn_slab_ni, gn_chunks, GN_TWO_SLOTS, the rpw rule of launch_ln_fwd) and
+    the colstats precondition of ops.groupnorm_fwd: calls = {call form: [launch-log symbols in launch order]}, symbols = their union, and the
+    geometry the slices need.  GroupNorm call forms: fwd, fwd_cs (column statistics attached; HW % 32 == 0 only), unfused (e4t_groupnorm_stats +
+    _apply), bwd_pg (with parameter gradients: always chunked), bwd.  LayerNorm: fwd, fwd_f32, bwd."""
+    if not isinstance(case, GNCase):
+        M, D = case
+        ncl, rpw = ln_rows_per_wave(M, D)
+        nc = min(ncl, 3)
+        calls = {"fwd": [f"ln_fwd_kernel<{nc}, {rpw}, false>"], "fwd_f32": [f"ln_fwd_kernel<{nc}, 1, true>"], "bwd": [f"ln_bwd_kernel<{nc}>"]}
+        return dict(calls=calls, symbols={s for v in calls.values() for s in v}, ncl=ncl, rpw=rpw)
+    c = case
+    C = c.C1 + c.C2
+    ns = 2 if C // 8 > 256 else 1
+    ni = gn_slab_ni(c.C1, c.C2, c.HW, c.G)
+    ch = gn_chunks(c.B, c.HW)
+    ppc = -(-c.HW // ch)
+    nblk = c.HW // 32
+    cs_ok = c.HW % 32 == 0 and nblk % min(ch, nblk) == 0
+    t = "true" if c.silu else "false"
+    two_pass = [f"gn_stats_kernel<{ns}>", f"gn_apply_kernel<true, {ns}>"]
+    bwd = [f"gn_bwd_stats_kernel<{ns}>", f"gn_bwd_apply_kernel<{ns}>"]
+    calls = {"fwd": [f"gn_slab_fwd_kernel<{ni}, {t}>"] if ni else two_pass,
+             "unfused": [f"gn_stats_kernel<{ns}>", f"gn_apply_kernel<false, {ns}>"],
+             "bwd_pg": bwd, "bwd": [f"gn_slab_bwd_kernel<{ni}, {t}>"] if ni else bwd}
+    if c.HW % 32 == 0:
+        calls["fwd_cs"] = calls["fwd"] if (ni or not cs_ok) else ["gn_stats_cols_kernel", f"gn_apply_kernel<true, {ns}>"]
+    return dict(calls=calls, symbols={s for v in calls.values() for s in v}, ns=ns, ni=ni, ch=ch, ppc=ppc, empty=ch - -(-c.HW // ppc), colstats=cs_ok)
+
+
+def gn_inputs(case, dev):
+    """x1, x2, gamma, beta, dy, add1, add2 of a case (add1 / add2: None where no backward variant of the case uses them)"""
+    c, g = case, gen(case.seed, dev)
+    n, C = c.B * c.HW, c.C1 + c.C2
+    if c.shift:      # x = shift + 0.5 randn, rounded to bf16 once
+        x1 = (torch.randn(n, c.C1, generator=g, device=dev, dtype=f32) * 0.5 + c.shift).to(bf16)
+    else:
+        x1 = rnd(g, n, c.C1, dev=dev) + 0.3
+    x2 = rnd(g, n, c.C2, scale=2.0, dev=dev) if c.C2 else None
+    gamma, beta = rnd(g, C, dtype=f32, dev=dev) * 0.3 + 1.0, rnd(g, C, dtype=f32, dev=dev) * 0.2
+    dy = rnd(g, n, C, dev=dev)
+    add1 = rnd(g, n, c.C1, dev=dev) if any(a for a, _ in c.adds) else None
+    add2 = rnd(g, n, c.C2, dev=dev) if any(a for _, a in c.adds) else None
+    return x1, x2, gamma, beta, dy, add1, add2
+
+
+def ln_inputs(case, i, dev):
+    """x, gamma, beta, dy, x32 (fp32 rows), skip (a residual gradient) of LN_CASES[i]"""
+    M, D = case
+    g = gen(160 + i, dev)
+    x = rnd(g, M, D, dev=dev) + 0.5
+    gamma, beta = rnd(g, D, dtype=f32, dev=dev) * 0.3 + 1.0, rnd(g, D, dtype=f32, dev=dev) * 0.2
+    dy = rnd(g, M, D, dev=dev)
+    x32 = (rnd(g, M, D, dtype=f32, dev=dev) + 0.5) * 3.0
+    return x, gamma, beta, dy, x32, rnd(g, M, D, dev=dev)
+
+
+def _cat64(x1, x2):
+    return x1.to(f64) if x2 is None else torch.cat([x1.to(f64), x2.to(f64)], dim=-1)
+
+
+def _silu64(z):
+    return z * torch.sigmoid(z)
+
+
+def _dsilu64(z):
+    s = torch.sigmoid(z)
+    return s * (1 + z * (1 - s))
+
+
+def gn_ref64_fwd(x1, x2, gamma, beta, B, HW, G, eps, silu):
+    """fp64 GroupNorm (+ SiLU) of the bf16 inputs, two-pass variance -> y [B * HW, C], stats [B, G, 2] = (mean, rstd), both fp64"""
+    x = _cat64(x1, x2)
+    C = x.shape[-1]
+    xg = x.reshape(B, HW, G, C // G)
+    mean = xg.mean(dim=(1, 3), keepdim=True)
+    xc = xg - mean
+    rstd = (xc.square().mean(dim=(1, 3), keepdim=True) + eps).rsqrt()
+    y = (xc * rstd).reshape(B * HW, C) * gamma.to(f64) + beta.to(f64)
+    return (_silu64(y) if silu else y), torch.stack([mean.reshape(B, G), rstd.reshape(B, G)], dim=-1)
+
+
+def gn_ref64_bwd(x1, x2, dy, stats, gamma, beta, add1, add2, B, HW, G, silu):
+    """fp64 GroupNorm backward from `stats` as the kernel receives them (the forward's fp64 statistics rounded to fp32)
+    -> dx [B * HW, C] (dx1 | dx2 side by side), dgamma, dbeta"""
+    x = _cat64(x1, x2)
+    C, C1 = x.shape[-1], x1.shape[-1]
+    cpg = C // G
+    st = stats.to(f64)
+    mean, rstd = st[..., 0].reshape(B, 1, G, 1), st[..., 1].reshape(B, 1, G, 1)
+    xh = (x.reshape(B, HW, G, cpg) - mean) * rstd
+    dz = dy.to(f64)
+    if silu:
+        dz = dz * _dsilu64(xh.reshape(B * HW, C) * gamma.to(f64) + beta.to(f64))
+    dzg = (dz * gamma.to(f64)).reshape(B, HW, G, cpg)
+    s1, s2 = dzg.mean(dim=(1, 3), keepdim=True), (dzg * xh).mean(dim=(1, 3), keepdim=True)
+    dx = (rstd * (dzg - s1 - xh * s2)).reshape(B * HW, C)
+    if add1 is not None:
+        dx[:, :C1] += add1.to(f64)
+    if add2 is not None:
+        dx[:, C1:] += add2.to(f64)
+    return dx, (dz * xh.reshape(B * HW, C)).sum(0), dz.sum(0)
+
+
+def ln_ref64_fwd(x, gamma, beta, eps):
+    """fp64 LayerNorm of bf16 / fp32 rows, two-pass variance -> y [M, D], stats [M, 2] = (mean, rstd)"""
+    xd = x.to(f64)
+    mean = xd.mean(-1, keepdim=True)
+    xc = xd - mean
+    rstd = (xc.square().mean(-1, keepdim=True) + eps).rsqrt()
+    return xc * rstd * gamma.to(f64) + beta.to(f64), torch.cat([mean, rstd], dim=-1)
+
+
+def ln_ref64_bwd(x, dy, gamma, stats, add=None):
+    """fp64 LayerNorm backward from the fp32 `stats` the kernel receives -> dx, dgamma, dbeta"""
+    st = stats.to(f64)
+    xh = (x.to(f64) - st[:, :1]) * st[:, 1:]
+    dg = dy.to(f64) * gamma.to(f64)
+    dx = st[:, 1:] * (dg - dg.mean(-1, keepdim=True) - xh * (dg * xh).mean(-1, keepdim=True))
+    if add is not None:
+        dx = dx + add.to(f64)
+    return dx, (dy.to(f64) * xh).sum(0), dy.to(f64).sum(0)
+
+
+def _region(d, n):
+    """relative L2 from sums of squared differences d and squared reference values n (tensors of one shape): the worst entry, NaN -> inf"""
+    e = (d / (n + 1e-300)).sqrt()
+    return float(torch.nan_to_num(e, nan=float("inf"), posinf=float("inf")).max())
+
+
+def gn_slices(tag, got, ref, case, chunked, tol=TOL1):
+    """Rows a whole-tensor relative L2 dilutes, each the worst of its kind: got, ref = [B * HW, C] (y, or dx1 | dx2 side by side; ref fp64).
+      - the worst (batch, group);
+      - chunked=True (the chunked kernels: pixels split into norm_plan's ch chunks of ppc): the worst first and the worst last pixel row of a chunk
+        (all C channels of one pixel — the masked tail of the `unconditional load, masked store` loop is the last).  Coarsened for C < 256 to as
+        many pixel rows as make GN_MIN_REGION = 256 values: the rounding-only model of one pixel row of 64 channels, worst of 1008, is 3.2e-3;
+      - two sources: the 8-channel chunks on either side of the concat boundary;
+      - the 8 channels of the last active thread, and the second slot's channels (2048 and up) for C > 2048;
+      - chunked=False (the slab kernels): the worst last pixel row (the last item row of every group) and the worst (batch, group) of the items
+        of the last, ragged trip of 256 quads.
+    Never finer than a whole pixel row or 170 values: the rounding-only model of a single (pixel, group) cell of 10 channels reaches 3.7e-3,
+    over half the tolerance, the worst row emitted here 2.0e-3 (tests/test_norm_slices_cpu.py)."""
+    c, pl = case, norm_plan(case)
+    B, HW, G, C = c.B, c.HW, c.G, c.C1 + c.C2
+    cpg = C // G
+    d2 = (got.to(f64) - ref.to(f64)).square().reshape(B, HW, C)
+    r2 = ref.to(f64).square().reshape(B, HW, C)
+    out = []
+
+    def row(label, d, n):
+        out.append((f"{tag}: {label}", _region(d, n), tol))
+    row("worst (batch, group)", d2.reshape(B, HW, G, cpg).sum(dim=(1, 3)), r2.reshape(B, HW, G, cpg).sum(dim=(1, 3)))
+    dp, rp = d2.sum(-1), r2.sum(-1)      # [B, HW]: whole pixel rows
+    if chunked:
+        first = torch.arange(0, HW, pl["ppc"], device=got.device)
+        last = torch.clamp(first + pl["ppc"], max=HW) - 1
+        k = min(-(-GN_MIN_REGION // C), pl["ppc"])      # pixel rows per region: 1 from C = 256 up
+        what = "pixel row" if k == 1 else f"{k} pixel rows"
+        ends = lambda sgn, t: sum(torch.where((first + j <= last), t[:, (first + j) if sgn > 0 else torch.clamp(last - j, min=0)], 0.0) for j in range(k))
+        row(f"worst first {what} of a chunk ({len(first)} chunks of {pl['ppc']})", ends(1, dp), ends(1, rp))
+        row(f"worst last {what} of a chunk (the last: pixel {int(last[-1])})", ends(-1, dp), ends(-1, rp))
+    else:
+        row(f"worst last pixel row (pixel {HW - 1}: the last item row)", dp[:, HW - 1], rp[:, HW - 1])
+        q4 = cpg // 4
+        t0 = (-(-HW * q4 // 256) - 1) * 256
+        if t0 > 0:
+            item = torch.arange(HW, device=got.device)[:, None] * q4 + torch.arange(cpg, device=got.device)[None, :] // 4
+            m = (item >= t0).to(f64)[None, :, None, :]
+            row(f"worst (batch, group) of items {t0}-{HW * q4 - 1} (the last trip)", (d2.reshape(B, HW, G, cpg) * m).sum(dim=(1, 3)), (r2.reshape(B, HW, G, cpg) * m).sum(dim=(1, 3)))
+    if c.C2:
+        row(f"channels {c.C1 - 8}-{c.C1 - 1} (the last chunk of the first source)", d2[..., c.C1 - 8:c.C1].sum(), r2[..., c.C1 - 8:c.C1].sum())
+        row(f"channels {c.C1}-{c.C1 + 7} (the first chunk of the second source)", d2[..., c.C1:c.C1 + 8].sum(), r2[..., c.C1:c.C1 + 8].sum())
+    row(f"channels {C - 8}-{C - 1} (the last active thread)", d2[..., C - 8:].sum(), r2[..., C - 8:].sum())
+    if C > 2048:
+        row(f"channels 2048-{C - 1} (the second slot)", d2[..., 2048:].sum(), r2[..., 2048:].sum())
+    return out
+
+
+def gn_stat_rows(tag, st, st64, tol=STAT_TOL):
+    """statistics [B, G, 2] = (mean, rstd) against fp64: the worst |d mean| * rstd and |d rstd| / rstd of one (batch, group)"""
+    d = (st.to(f64) - st64).abs()
+    nn = lambda t: float(torch.nan_to_num(t, nan=float("inf")).max())
+    return [(f"{tag}: worst |d mean| * rstd of a (batch, group) against fp64", nn(d[..., 0] * st64[..., 1]), tol),
+            (f"{tag}: worst |d rstd| / rstd of a (batch, group) against fp64", nn(d[..., 1] / st64[..., 1]), tol)]
+
+
+def ln_slices(tag, got, ref, rpw, tol=TOL1):
+    """LayerNorm y / dx [M, D] against fp64, each row the worst of its kind:
+      - the worst row (the rounding-only model of a single row stays under half the tolerance even at D = 64: 2.3e-3 at worst over all cases);
+      - the rows of the last wave (rpw rows per wave: the forward's 1 / 2 / 4, the backward's 1) and the rows of the last block of 4 waves: ragged
+        where M is no multiple, reported separately;
+      - the last active 16-byte chunk of a row (columns D - 8 .. D - 1) and the first chunk of each lane trip (columns 512 i .. 512 i + 7)."""
+    M, D = ref.shape
+    d2, r2 = (got.to(f64) - ref.to(f64)).square(), ref.to(f64).square()
+    dr, rr = d2.sum(1), r2.sum(1)
+    out = []
+
+    def row(label, d, n):
+        out.append((f"{tag}: {label}", _region(d, n), tol))
+    row("worst row", dr, rr)
+    w0, b0 = (M - 1) // rpw * rpw, (M - 1) // (4 * rpw) * (4 * rpw)
+    row(f"rows {w0}-{M - 1} (the last wave, {rpw} per wave)", dr[w0:].sum(), rr[w0:].sum())
+    row(f"rows {b0}-{M - 1} (the last block, {4 * rpw} per block)", dr[b0:].sum(), rr[b0:].sum())
+    row(f"columns {D - 8}-{D - 1} (the last active chunk)", d2[:, D - 8:].sum(), r2[:, D - 8:].sum())
+    for i in range(-(-D // 512)):
+        row(f"columns {512 * i}-{512 * i + 7} (the first chunk of lane trip {i})", d2[:, 512 * i:512 * i + 8].sum(), r2[:, 512 * i:512 * i + 8].sum())
+    return out
+
+
+def colblock_rows(tag, got, ref, tol=1e-3):
+    """parameter gradients [C] against fp64: the worst block of 64 columns (the column block of one colreduce workgroup; the last may be ragged)"""
+    d2, r2 = (got.to(f64) - ref.to(f64)).square(), ref.to(f64).square()
+    C = ref.numel()
+    worst = max(_region(d2[lo:lo + 64].sum(), r2[lo:lo + 64].sum()) for lo in range(0, C, 64))
+    return [(f"{tag}: worst 64-column block", worst, tol)]
+
+
+def norm_slices(tag, got, ref, case, chunked=True, rpw=1, tol=TOL1):
+    """the localised rows of one norm output, in the style of slices() and conv_slices(): gn_slices() for a GNCase, ln_slices() for (M, D)"""
+    if isinstance(case, GNCase):
+        return gn_slices(tag, got, ref, case, chunked, tol)
+    return ln_slices(tag, got, ref, rpw, tol)
+
+
+def _logged(hip, fn):
+    """run fn() with the library's launch log on -> (fn's result, [kernel symbol per logged launch])"""
+    import os
+    import tempfile
+    fd, path = tempfile.mkstemp(suffix=".launchlog")
+    os.close(fd)
+    try:
+        assert hip.lib.e4t_set_launch_log(path.encode()) == 0
+        try:
+            res = fn()
+            torch.cuda.synchronize()
+        finally:
+            hip.lib.e4t_set_launch_log(None)
+        with open(path) as f:
+            return res, [l.split("|")[0] for l in f.read().splitlines() if l]
+    finally:
+        os.unlink(path)
+
+
+def _plan_row(tag, form, logged, planned):
+    return (f"{tag}: launch log of {form} == the plan {planned}" + ("" if logged == planned else f" (logged {logged})"), float(logged != planned), 0.0)
+
+
+def _with_colstats(t):
+    """the column statistics a producing GEMM / conv epilogue would have left on t: [rows / 32][C][2] = (sum, sum of squares) per 32-row block"""
+    blk = t.float().reshape(t.shape[0] // 32, 32, t.shape[1])
+    t._e4t_colstats = torch.stack([blk.sum(1), (blk * blk).sum(1)], dim=-1).contiguous()
+    return t
+
+
+def _cat(a, b):
+    return a if b is None else torch.cat([a, b], dim=-1)
+
+
+def _check_groupnorm_case(hip, emu, dev, c):
+    out = []
+    B, HW, C1, C2, G, silu, eps = c.B, c.HW, c.C1, c.C2, c.G, c.silu, c.eps
+    pl, tag = norm_plan(c), gn_tag(c)
+    slab = pl["ni"] > 0
+    x1, x2, gamma, beta, dy, a1, a2 = gn_inputs(c, dev)
+    geo = (gamma, beta, B, HW, G, eps, silu)
+    (y, st), log = _logged(hip, lambda: hip.groupnorm_fwd(x1, x2, *geo))
+    out.append(_plan_row(tag, "fwd", log, pl["calls"]["fwd"]))
+    yr, str_ = emu.groupnorm_fwd(x1, x2, *geo)
+    y64, st64 = gn_ref64_fwd(x1, x2, *geo)
+    out.append((tag + " fwd", rel(y, yr), TOL1))
+    out.append((tag + " stats", rel(st, str_), 1e-4))
+    out += gn_slices(tag + " fwd vs fp64", y, y64, c, not slab)
+    out += gn_stat_rows(tag + " stats", st, st64)
+    if HW % 32 == 0:       # the same GroupNorm fed with the column statistics a producing GEMM would have left behind
+        x1c, x2c = _with_colstats(x1.clone()), (_with_colstats(x2.clone()) if x2 is not None else None)
+        (y3, st3), log = _logged(hip, lambda: hip.groupnorm_fwd(x1c, x2c, *geo))
+        out.append(_plan_row(tag, "fwd with column statistics", log, pl["calls"]["fwd_cs"]))
+        out.append((tag + " via column statistics: y", rel(y3, y), 2e-3))
+        out.append((tag + " via column statistics: stats", rel(st3, st), 1e-4))
+        if c.new:
+            out += gn_slices(tag + " via column statistics vs fp64", y3, y64, c, not slab)
+            out += gn_stat_rows(tag + " via column statistics: stats", st3, st64)
+    (y2, st2), log = _logged(hip, lambda: hip.groupnorm_fwd_unfused(x1, x2, *geo))
+    out.append(_plan_row(tag, "stats/finalize/apply", log, pl["calls"]["unfused"]))
+    if slab:     # one-launch kernel: same arithmetic, different summation tree
+        out.append((tag + " slab kernel ~ stats/finalize/apply entry points: y", rel(y, y2), 2e-3))
+        out.append((tag + " slab kernel ~ stats/finalize/apply entry points: stats", rel(st, st2), 1e-5))
+        out += gn_slices(tag + " stats/finalize/apply vs fp64", y2, y64, c, True)      # (their statistics: the rows of the chunked cases, bitwise the fused path's)
+    else:
+        out.append((tag + f" fused == stats/finalize/apply entry points (NS = {pl['ns']})", float((y2 != y).sum() + (st2 != st).sum()), 0.0))
+    st32 = st64.to(f32)      # what the fp64 backward and the kernel both start from
+    for add1, add2 in ((a1 if u1 else None, a2 if u2 else None) for u1, u2 in c.adds):
+        vt = tag + ("" if len(c.adds) == 1 else f" add{'1' if add1 is not None else '2'} only")
+        bw = (x1, x2, dy)
+        tail = (B, HW, G, silu)
+        dx1, dx2, dga, dbe = hip.groupnorm_bwd(*bw, str_, gamma, beta, add1, *tail, want_param_grads=True, add2=add2)
+        ex1, ex2, ega, ebe = emu.groupnorm_bwd(*bw, str_, gamma, beta, add1, *tail, want_param_grads=True, add2=add2)
+        out.append((vt + " bwd dx1", rel(dx1, ex1), TOL1))
+        if C2:
+            out.append((vt + " bwd dx2", rel(dx2, ex2), TOL1))
+        out.append((vt + " bwd dgamma", rel(dga, ega), 1e-3))
+        out.append((vt + " bwd dbeta", rel(dbe, ebe), 1e-3))
+        # frozen gamma / beta (pre-training): no parameter-gradient partials -> slab kernel where eligible
+        fx1, fx2, _, _ = hip.groupnorm_bwd(*bw, str_, gamma, beta, add1, *tail, want_param_grads=False, add2=add2)
+        out.append((vt + " bwd dx1 (no param grads)", rel(fx1, ex1), TOL1))
+        if C2:
+            out.append((vt + " bwd dx2 (no param grads)", rel(fx2, ex2), TOL1))
+        # ... and against fp64, from the fp64 statistics rounded to fp32, localised
+        d64, ga64, be64 = gn_ref64_bwd(*bw, st32, gamma, beta, add1, add2, *tail)
+        (dx1, dx2, dga, dbe), log = _logged(hip, lambda: hip.groupnorm_bwd(*bw, st32, gamma, beta, add1, *tail, want_param_grads=True, add2=add2))
+        out.append(_plan_row(vt, "bwd with parameter gradients", log, pl["calls"]["bwd_pg"]))
+        out += gn_slices(vt + " bwd dx1 | dx2 vs fp64", _cat(dx1, dx2), d64, c, True)
+        out += colblock_rows(vt + " bwd dgamma vs fp64", dga, ga64) + colblock_rows(vt + " bwd dbeta vs fp64", dbe, be64)
+        (fx1, fx2, _, _), log = _logged(hip, lambda: hip.groupnorm_bwd(*bw, st32, gamma, beta, add1, *tail, want_param_grads=False, add2=add2))
+        out.append(_plan_row(vt, "bwd", log, pl["calls"]["bwd"]))
+        out += gn_slices(vt + " bwd dx1 | dx2 (no param grads) vs fp64", _cat(fx1, fx2), d64, c, not slab)
+        if c.new:      # the file's header claims a fixed summation order: repeated launches are bitwise equal
+            differing = 0
+            for _ in range(2):
+                yb, sb = hip.groupnorm_fwd(x1, x2, *geo)
+                g1, g2, gg, gb = hip.groupnorm_bwd(*bw, st32, gamma, beta, add1, *tail, want_param_grads=True, add2=add2)
+                h1, h2, _, _ = hip.groupnorm_bwd(*bw, st32, gamma, beta, add1, *tail, want_param_grads=False, add2=add2)
+                differing += _neq(yb, y) + _neq(sb, st) + _neq(g1, dx1) + _neq(gg, dga) + _neq(gb, dbe) + _neq(h1, fx1)
+                if C2:
+                    differing += _neq(g2, dx2) + _neq(h2, fx2)
+            out.append((vt + ": elements differing bitwise between three launches (y, stats, dx, dgamma, dbeta)", float(differing), 0.0))
+    return out
+
+
+def _check_layernorm_case(hip, emu, dev, i, case):
+    out = []
+    M, D = case
+    pl, tag = norm_plan(case), f"layernorm {M}x{D}"
+    x, gamma, beta, dy, x32, skip = ln_inputs(case, i, dev)
+    (y, st), log = _logged(hip, lambda: hip.layernorm_fwd(x, gamma, beta, 1e-5))
+    out.append(_plan_row(tag, "fwd", log, pl["calls"]["fwd"]))
+    yr, str_ = emu.layernorm_fwd(x, gamma, beta, 1e-5)
+    y64, st64 = ln_ref64_fwd(x, gamma, beta, 1e-5)
+    out.append((f"{tag} fwd", rel(y, yr), TOL1))
+    out.append((f"{tag} stats", rel(st, str_), 1e-4))
+    out += ln_slices(f"{tag} fwd vs fp64", y, y64, pl["rpw"])
+    (dx, dga, dbe), log = _logged(hip, lambda: hip.layernorm_bwd(x, dy, gamma, str_, want_param_grads=True))
+    out.append(_plan_row(tag, "bwd", log, pl["calls"]["bwd"]))
+    ex, ega, ebe = emu.layernorm_bwd(x, dy, gamma, str_, want_param_grads=True)
+    out.append((f"{tag} bwd dx", rel(dx, ex), TOL1))
+    out.append((f"{tag} bwd dgamma", rel(dga, ega), 1e-3))
+    out.append((f"{tag} bwd dbeta", rel(dbe, ebe), 1e-3))
+    st32 = st64.to(f32)
+    d64, ga64, be64 = ln_ref64_bwd(x, dy, gamma, st32)
+    dx, dga, dbe = hip.layernorm_bwd(x, dy, gamma, st32, want_param_grads=True)
+    out += ln_slices(f"{tag} bwd dx vs fp64", dx, d64, 1)
+    out += colblock_rows(f"{tag} bwd dgamma vs fp64", dga, ga64) + colblock_rows(f"{tag} bwd dbeta vs fp64", dbe, be64)
+    (y32, s32), log = _logged(hip, lambda: hip.layernorm_fwd(x32, gamma, beta, 1e-5))      # fp32 rows (ViT residual stream) -> bf16 y
+    out.append(_plan_row(tag, "fwd, fp32 input", log, pl["calls"]["fwd_f32"]))
+    yr32, str32 = emu.layernorm_fwd(x32, gamma, beta, 1e-5)
+    out.append((f"{tag} fwd, fp32 input", rel(y32, yr32), TOL1))
+    out.append((f"{tag} stats, fp32 input", rel(s32, str32), 1e-4))
+    out += ln_slices(f"{tag} fwd, fp32 input vs fp64", y32, ln_ref64_fwd(x32, gamma, beta, 1e-5)[0], 1)
+    out.append((f"{tag} bwd dx + residual grad", rel(hip.layernorm_bwd(x, dy, gamma, str_, add=skip)[0], emu.layernorm_bwd(x, dy, gamma, str_, add=skip)[0]), TOL1))
+    out += ln_slices(f"{tag} bwd dx + residual grad vs fp64", hip.layernorm_bwd(x, dy, gamma, st32, add=skip)[0], ln_ref64_bwd(x, dy, gamma, st32, add=skip)[0], 1)
+    if case == LN_NEED_STATS_CASE:      # the sampling path: mean_rstd == NULL
+        yn, sn = hip.layernorm_fwd(x, gamma, beta, 1e-5, need_stats=False)
+        out.append((f"{tag} fwd without statistics: elements differing bitwise from y with them", float(_neq(yn, y) + (sn is not None)), 0.0))
+    return out
+
+
 def check_norms(hip, emu, dev):
     out = []
-    # the last six take the one-launch slab kernels (HW x C/G <= 10240, C/G % 4 == 0, no group straddling the concat): 3 / 5 / 10
-    # quads per thread, two sources, ragged item counts, with and without SiLU / shortcut gradients
-    for i, (B, HW, C1, C2, G, silu) in enumerate([(2, 64, 64, 0, 32, True), (3, 256, 320, 0, 32, True), (2, 100, 320, 640, 32, True),
-                                                  (2, 64, 1280, 1280, 32, False), (16, 4096, 320, 0, 32, True),
-                                                  (2, 64, 1280, 0, 32, True), (3, 256, 1280, 0, 32, True), (2, 64, 1280, 1280, 32, True),
-                                                  (2, 60, 640, 0, 32, True), (1, 256, 640, 640, 32, False), (2, 64, 640, 640, 32, True)]):
-        g = gen(140 + i, dev)
-        x1 = rnd(g, B * HW, C1, dev=dev) + 0.3
-        x2 = rnd(g, B * HW, C2, scale=2.0, dev=dev) if C2 else None
-        Cn = C1 + C2
-        gamma, beta = rnd(g, Cn, dtype=f32, dev=dev) * 0.3 + 1.0, rnd(g, Cn, dtype=f32, dev=dev) * 0.2
-        y, st = hip.groupnorm_fwd(x1, x2, gamma, beta, B, HW, G, 1e-5, silu)
-        yr, str_ = emu.groupnorm_fwd(x1, x2, gamma, beta, B, HW, G, 1e-5, silu)
-        tag = f"groupnorm B{B} HW{HW} C{C1}+{C2} silu{int(silu)}"
-        out.append((tag + " fwd", rel(y, yr), TOL1))
-        out.append((tag + " stats", rel(st, str_), 1e-4))
-        if HW % 32 == 0:       # the same GroupNorm fed with the column statistics a producing GEMM would have left behind
-            def with_cs(t):
-                blk = t.float().reshape(t.shape[0] // 32, 32, t.shape[1])
-                t._e4t_colstats = torch.stack([blk.sum(1), (blk * blk).sum(1)], dim=-1).contiguous()
-                return t
-            x1c, x2c = with_cs(x1.clone()), (with_cs(x2.clone()) if x2 is not None else None)
-            y3, st3 = hip.groupnorm_fwd(x1c, x2c, gamma, beta, B, HW, G, 1e-5, silu)
-            out.append((tag + " via column statistics: y", rel(y3, y), 2e-3))
-            out.append((tag + " via column statistics: stats", rel(st3, st), 1e-4))
-        y2, st2 = hip.groupnorm_fwd_unfused(x1, x2, gamma, beta, B, HW, G, 1e-5, silu)
-        cpg = Cn // G
-        slab = cpg % 4 == 0 and HW * cpg <= 10240 and (C2 == 0 or C1 % cpg == 0)
-        if slab:     # one-launch kernel: same arithmetic, different summation tree
-            out.append((tag + " slab kernel ~ stats/finalize/apply entry points: y", rel(y, y2), 2e-3))
-            out.append((tag + " slab kernel ~ stats/finalize/apply entry points: stats", rel(st, st2), 1e-5))
-        else:
-            out.append((tag + " fused == stats/finalize/apply entry points", float((y2 != y).sum() + (st2 != st).sum()), 0.0))
-        dy = rnd(g, B * HW, Cn, dev=dev)
-        add = rnd(g, B * HW, C1, dev=dev) if i % 2 == 0 else None            # gradient through the block's shortcut
-        add2 = rnd(g, B * HW, C2, dev=dev) if (C2 and i != 3) else None
-        dx1, dx2, dga, dbe = hip.groupnorm_bwd(x1, x2, dy, str_, gamma, beta, add, B, HW, G, silu, want_param_grads=True, add2=add2)
-        ex1, ex2, ega, ebe = emu.groupnorm_bwd(x1, x2, dy, str_, gamma, beta, add, B, HW, G, silu, want_param_grads=True, add2=add2)
-        out.append((tag + " bwd dx1", rel(dx1, ex1), TOL1))
-        if C2:
-            out.append((tag + " bwd dx2", rel(dx2, ex2), TOL1))
-        out.append((tag + " bwd dgamma", rel(dga, ega), 1e-3))
-        out.append((tag + " bwd dbeta", rel(dbe, ebe), 1e-3))
-        # frozen gamma / beta (pre-training): no parameter-gradient partials -> slab kernel where eligible
-        fx1, fx2, _, _ = hip.groupnorm_bwd(x1, x2, dy, str_, gamma, beta, add, B, HW, G, silu, want_param_grads=False, add2=add2)
-        out.append((tag + " bwd dx1 (no param grads)", rel(fx1, ex1), TOL1))
-        if C2:
-            out.append((tag + " bwd dx2 (no param grads)", rel(fx2, ex2), TOL1))
-    # the last three take the several-rows-per-wave forward (4 / 2 / 2 rows for 1 / 2 / 3 chunks per lane) with a ragged last wave
-    for i, (M, D) in enumerate([(37, 64), (1000, 320), (4112, 1280), (300, 768), (128, 1024), (8195, 320), (4101, 640), (4111, 1280)]):
-        g = gen(160 + i, dev)
-        x = rnd(g, M, D, dev=dev) + 0.5
-        gamma, beta = rnd(g, D, dtype=f32, dev=dev) * 0.3 + 1.0, rnd(g, D, dtype=f32, dev=dev) * 0.2
-        y, st = hip.layernorm_fwd(x, gamma, beta, 1e-5)
-        yr, str_ = emu.layernorm_fwd(x, gamma, beta, 1e-5)
-        out.append((f"layernorm {M}x{D} fwd", rel(y, yr), TOL1))
-        out.append((f"layernorm {M}x{D} stats", rel(st, str_), 1e-4))
-        dy = rnd(g, M, D, dev=dev)
-        dx, dga, dbe = hip.layernorm_bwd(x, dy, gamma, str_, want_param_grads=True)
-        ex, ega, ebe = emu.layernorm_bwd(x, dy, gamma, str_, want_param_grads=True)
-        out.append((f"layernorm {M}x{D} bwd dx", rel(dx, ex), TOL1))
-        out.append((f"layernorm {M}x{D} bwd dgamma", rel(dga, ega), 1e-3))
-        out.append((f"layernorm {M}x{D} bwd dbeta", rel(dbe, ebe), 1e-3))
-        x32 = (rnd(g, M, D, dtype=f32, dev=dev) + 0.5) * 3.0            # fp32 rows (ViT residual stream) -> bf16 y
-        y32, st32 = hip.layernorm_fwd(x32, gamma, beta, 1e-5)
-        yr32, str32 = emu.layernorm_fwd(x32, gamma, beta, 1e-5)
-        out.append((f"layernorm {M}x{D} fwd, fp32 input", rel(y32, yr32), TOL1))
-        out.append((f"layernorm {M}x{D} stats, fp32 input", rel(st32, str32), 1e-4))
-        skip = rnd(g, M, D, dev=dev)
-        out.append((f"layernorm {M}x{D} bwd dx + residual grad", rel(hip.layernorm_bwd(x, dy, gamma, str_, add=skip)[0],
-                                                                     emu.layernorm_bwd(x, dy, gamma, str_, add=skip)[0]), TOL1))
+    for c in GN_CASES:
+        out += _check_groupnorm_case(hip, emu, dev, c)
+    for i, case in enumerate(LN_CASES):
+        out += _check_layernorm_case(hip, emu, dev, i, case)
     return out
+
+
+# ---- norm_guards: the norm entry points through the raw ABI, poison around every operand ---------------------------------------------
+NORM_GUARD_ROWS = 64       # sentinel / NaN rows in front of and behind every operand
+# one chunked one-slot case (empty trailing chunks, a ragged last one), one chunked two-slot two-source case, one slab case per NI with a ragged tail
+GN_GUARD_CASES = [_gn(2, 260, 320, 0, True), _gn(2, 256, 1280, 1280, True), _gn(2, 60, 640, 0, True), _gn(2, 100, 640, 640, True), _gn(2, 100, 1280, 1280, True)]
+GN_GUARD_CASES = [c._replace(seed=1600 + i) for i, c in enumerate(GN_GUARD_CASES)]
+LN_GUARD_CASES = [(4101, 640), (300, 1280)]
+
+
+class _Rows:
+    """rows r0 .. r0 + n - 1 of a sentinel buffer, all columns: what _changed_outside() needs to know of an operand"""
+
+    def __init__(self, buf, r0, n):
+        self.idx, self.c0, self.d = torch.arange(r0, r0 + n, device=buf.device), 0, buf.shape[1]
+
+
+class _Guarded:
+    """an output [rows][width] (bf16 or fp32) carved out of a sentinel buffer with NORM_GUARD_ROWS sentinel rows on either side, itself sentinel"""
+
+    def __init__(self, rows, width, dtype, dev):
+        w16 = width * (2 if dtype == f32 else 1)
+        self.buf = _sentinel_buf(rows + 2 * NORM_GUARD_ROWS, w16, dev)
+        self.rows, self.dtype = rows, dtype
+        self.op = _Rows(self.buf, NORM_GUARD_ROWS, rows)
+        self.view = self.buf[NORM_GUARD_ROWS:NORM_GUARD_ROWS + rows].view(dtype)
+        self.ptr = self.view.data_ptr()
+
+    def outside(self):
+        """sentinel elements changed outside the output"""
+        return _changed_outside(self.buf, [self.op])
+
+    def touched(self):
+        """16-bit words of the whole buffer, output included, that no longer hold the sentinel (a rejected call must leave 0)"""
+        return int((self.buf.view(torch.int16) != SENT16).sum())
+
+
+def _nan_wrapped(t):
+    """a copy of t [rows][width] with NORM_GUARD_ROWS whole rows of NaN in front of and behind it, in one allocation"""
+    if t is None:
+        return None
+    t2 = t.reshape(t.shape[0], -1)
+    buf = torch.full((t2.shape[0] + 2 * NORM_GUARD_ROWS, t2.shape[1]), float("nan"), dtype=t.dtype, device=t.device)
+    buf[NORM_GUARD_ROWS:NORM_GUARD_ROWS + t2.shape[0]] = t2
+    return buf[NORM_GUARD_ROWS:NORM_GUARD_ROWS + t2.shape[0]].view(t.shape)
+
+
+class _Workspace:
+    """exactly nbytes of workspace with 1024 sentinel floats behind it"""
+
+    def __init__(self, nbytes, dev):
+        assert nbytes % 4 == 0
+        self.n = nbytes // 4
+        self.buf = torch.full((self.n + 1024,), SENT32, dtype=torch.int32, device=dev)
+        self.ptr, self.bytes = self.buf.data_ptr(), nbytes
+
+    def outside(self):
+        return int((self.buf[self.n:] != SENT32).sum())
+
+
+def _finite_rel(got, ref):
+    """relative L2, infinite if any element of got is not finite"""
+    return rel(got, ref) if bool(torch.isfinite(got.float()).all()) else float("inf")
+
+
+def _last_error(lib):
+    msg = lib.e4t_last_error()
+    return msg.decode() if msg else ""
+
+
+def _guard_groupnorm(hip, dev, c):
+    from e4t.ops import _stream, _ptr
+    lib, out = hip.lib, []
+    B, HW, C1, C2, G, silu = c.B, c.HW, c.C1, c.C2, c.G, c.silu
+    C, n, pl, tag = C1 + C2, c.B * c.HW, norm_plan(c), gn_tag(c) + " guarded"
+    x1, x2, gamma, beta, dy, a1, a2 = gn_inputs(c, dev)
+    y64, st64 = gn_ref64_fwd(x1, x2, gamma, beta, B, HW, G, c.eps, silu)
+    st32 = st64.to(f32)
+    d64, ga64, be64 = gn_ref64_bwd(x1, x2, dy, st32, gamma, beta, a1, a2, B, HW, G, silu)
+    x1g, x2g, dyg, a1g, a2g = (_nan_wrapped(t) for t in (x1, x2, dy, a1, a2))
+    stg = _nan_wrapped(st32.reshape(B * G, 2))
+    need = lib.e4t_groupnorm_workspace_bytes(B, HW, C, G, 0)
+    chunked = pl["ni"] == 0
+
+    def fwd_rows(form, call, ws_bytes, rejects_short):
+        y, st, ws = _Guarded(n, C, bf16, dev), _Guarded(B * G, 2, f32, dev), _Workspace(ws_bytes, dev)
+        code = call(y, st, ws, ws.bytes)
+        torch.cuda.synchronize()
+        rows = [(f"{tag} {form}: return code", float(code), 0.0),
+                (f"{tag} {form}: sentinel elements changed around y, mean_rstd, behind the workspace", float(y.outside() + st.outside() + ws.outside()), 0.0),
+                (f"{tag} {form}: y (finite, vs fp64)", _finite_rel(y.view, y64), TOL1)]
+        rows += gn_stat_rows(f"{tag} {form}: stats", st.view.reshape(B, G, 2), st64)
+        if rejects_short:      # one byte class smaller: -22, nothing written
+            y, st, ws = _Guarded(n, C, bf16, dev), _Guarded(B * G, 2, f32, dev), _Workspace(ws_bytes, dev)
+            code = call(y, st, ws, ws.bytes - 4)
+            torch.cuda.synchronize()
+            rows.append((f"{tag} {form}, workspace 4 bytes short: return code + 22", float(code + 22), 0.0))
+            rows.append((f"{tag} {form}, workspace 4 bytes short: error text missing", float("workspace" not in _last_error(lib)), 0.0))
+            rows.append((f"{tag} {form}, workspace 4 bytes short: output / workspace words changed", float(y.touched() + st.touched() + int((ws.buf != SENT32).sum())), 0.0))
+        return rows
+    out += fwd_rows("e4t_groupnorm_fwd", lambda y, st, ws, nb: lib.e4t_groupnorm_fwd(_ptr(x1g), C1, _ptr(x2g), C2, _ptr(gamma), _ptr(beta), y.ptr, st.ptr, B, HW, G,
+                                                                                     float(c.eps), int(silu), ws.ptr, nb, _stream()), need, chunked)
+    if HW % 32 == 0 and pl["colstats"]:
+        cs1 = _nan_wrapped(_with_colstats(x1.clone())._e4t_colstats.reshape(n // 32, C1 * 2))
+        cs2 = _nan_wrapped(_with_colstats(x2.clone())._e4t_colstats.reshape(n // 32, C2 * 2)) if x2 is not None else None
+        out += fwd_rows("e4t_groupnorm_fwd_cs", lambda y, st, ws, nb: lib.e4t_groupnorm_fwd_cs(_ptr(x1g), C1, _ptr(cs1), _ptr(x2g), C2, _ptr(cs2), _ptr(gamma), _ptr(beta), y.ptr,
+                                                                                               st.ptr, B, HW, G, float(c.eps), int(silu), ws.ptr, nb, _stream()), need, False)
+    # the unfused entry points: statistics into a guarded mean_rstd, then apply from it
+    st, ws, y = _Guarded(B * G, 2, f32, dev), _Workspace(need, dev), _Guarded(n, C, bf16, dev)
+    code = lib.e4t_groupnorm_stats(_ptr(x1g), C1, _ptr(x2g), C2, B, HW, G, float(c.eps), st.ptr, ws.ptr, ws.bytes, _stream())
+    code2 = lib.e4t_groupnorm_apply(_ptr(x1g), C1, _ptr(x2g), C2, st.ptr, _ptr(gamma), _ptr(beta), y.ptr, B, HW, G, int(silu), _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_groupnorm_stats + _apply: return codes", float(abs(code) + abs(code2)), 0.0))
+    out.append((f"{tag} e4t_groupnorm_stats + _apply: sentinel elements changed", float(y.outside() + st.outside() + ws.outside()), 0.0))
+    out.append((f"{tag} e4t_groupnorm_stats + _apply: y (finite, vs fp64)", _finite_rel(y.view, y64), TOL1))
+    out += gn_stat_rows(f"{tag} e4t_groupnorm_stats: stats", st.view.reshape(B, G, 2), st64)
+    st, ws = _Guarded(B * G, 2, f32, dev), _Workspace(need, dev)
+    code = lib.e4t_groupnorm_stats(_ptr(x1g), C1, _ptr(x2g), C2, B, HW, G, float(c.eps), st.ptr, ws.ptr, ws.bytes - 4, _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_groupnorm_stats, workspace 4 bytes short: return code + 22", float(code + 22), 0.0))
+    out.append((f"{tag} e4t_groupnorm_stats, workspace 4 bytes short: output / workspace words changed", float(st.touched() + int((ws.buf != SENT32).sum())), 0.0))
+    # backward: the workspace query + B * G * 8 bytes (INTEGRATION.md); with parameter-gradient partials (chunked kernels) and without
+    need_b = need + B * G * 8
+    for pg in (True, False):
+        form = "e4t_groupnorm_bwd" + (" with parameter-gradient partials" if pg else "")
+
+        def call(nb, bufs):
+            dx1, dx2, cp, ws = bufs
+            return lib.e4t_groupnorm_bwd(_ptr(x1g), C1, _ptr(x2g), C2, _ptr(dyg), stg.data_ptr(), _ptr(gamma), _ptr(beta), _ptr(a1g), _ptr(a2g), dx1.ptr,
+                                         dx2.ptr if dx2 else None, cp.ptr if cp else None, B, HW, G, int(silu), ws.ptr, nb, _stream())
+        make = lambda: (_Guarded(n, C1, bf16, dev), _Guarded(n, C2, bf16, dev) if C2 else None, _Guarded(B * pl["ch"], C * 2, f32, dev) if pg else None, _Workspace(need_b, dev))
+        bufs = make()
+        code = call(need_b, bufs)
+        torch.cuda.synchronize()
+        dx1, dx2, cp, ws = bufs
+        out.append((f"{tag} {form}: return code", float(code), 0.0))
+        out.append((f"{tag} {form}: sentinel elements changed around dx1, dx2, the partials, behind the workspace", float(sum(b.outside() for b in bufs if b is not None)), 0.0))
+        out.append((f"{tag} {form}: dx1 (finite, vs fp64)", _finite_rel(dx1.view, d64[:, :C1]), TOL1))
+        if C2:
+            out.append((f"{tag} {form}: dx2 (finite, vs fp64)", _finite_rel(dx2.view, d64[:, C1:]), TOL1))
+        if pg:
+            s = cp.view.reshape(B * pl["ch"], C, 2).sum(0)
+            out.append((f"{tag} {form}: dbeta (finite, vs fp64)", _finite_rel(s[:, 0], be64), 1e-3))
+            out.append((f"{tag} {form}: dgamma (finite, vs fp64)", _finite_rel(s[:, 1], ga64), 1e-3))
+        if pg or chunked:
+            bufs = make()
+            code = call(need_b - 4, bufs)
+            torch.cuda.synchronize()
+            out.append((f"{tag} {form}, workspace 4 bytes short: return code + 22", float(code + 22), 0.0))
+            out.append((f"{tag} {form}, workspace 4 bytes short: output / workspace words changed",
+                        float(sum(b.touched() for b in bufs[:3] if b is not None) + int((bufs[3].buf != SENT32).sum())), 0.0))
+    return out
+
+
+def _guard_layernorm(hip, dev, case):
+    from e4t.ops import _stream, _ptr
+    lib, out = hip.lib, []
+    M, D = case
+    tag = f"layernorm {M}x{D} guarded"
+    x, gamma, beta, dy, x32, skip = ln_inputs(case, LN_CASES.index(case), dev)
+    xg, dyg, x32g, skipg = (_nan_wrapped(t) for t in (x, dy, x32, skip))
+    for form, fn, xin, ref in (("e4t_layernorm_fwd", lib.e4t_layernorm_fwd, xg, x), ("e4t_layernorm_fwd_f32", lib.e4t_layernorm_fwd_f32, x32g, x32)):
+        y64, st64 = ln_ref64_fwd(ref, gamma, beta, 1e-5)
+        y, st = _Guarded(M, D, bf16, dev), _Guarded(M, 2, f32, dev)
+        code = fn(_ptr(xin), _ptr(gamma), _ptr(beta), y.ptr, st.ptr, M, D, 1e-5, _stream())
+        torch.cuda.synchronize()
+        out.append((f"{tag} {form}: return code", float(code), 0.0))
+        out.append((f"{tag} {form}: sentinel elements changed around y, mean_rstd", float(y.outside() + st.outside()), 0.0))
+        out.append((f"{tag} {form}: y (finite, vs fp64)", _finite_rel(y.view, y64), TOL1))
+        out.append((f"{tag} {form}: stats (finite, vs fp64)", _finite_rel(st.view, st64), 1e-4))
+    y64, st64 = ln_ref64_fwd(x, gamma, beta, 1e-5)
+    stg = _nan_wrapped(st64.to(f32))
+    d64, ga64, be64 = ln_ref64_bwd(x, dy, gamma, stg, add=skip)
+    dx = _Guarded(M, D, bf16, dev)
+    code = lib.e4t_layernorm_bwd(_ptr(xg), _ptr(dyg), _ptr(gamma), _ptr(stg), _ptr(skipg), dx.ptr, M, D, _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_layernorm_bwd: return code", float(code), 0.0))
+    out.append((f"{tag} e4t_layernorm_bwd: sentinel elements changed around dx", float(dx.outside()), 0.0))
+    out.append((f"{tag} e4t_layernorm_bwd: dx (finite, vs fp64)", _finite_rel(dx.view, d64), TOL1))
+    ns = lib.e4t_colreduce_splits(M)
+    dg, db, ws = _Guarded(1, D, f32, dev), _Guarded(1, D, f32, dev), _Workspace(2 * ns * D * 4, dev)
+    code = lib.e4t_layernorm_param_grad(_ptr(xg), _ptr(dyg), _ptr(stg), M, D, dg.ptr, db.ptr, 0, ws.ptr, ws.bytes, _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_layernorm_param_grad: return code", float(code), 0.0))
+    out.append((f"{tag} e4t_layernorm_param_grad: sentinel elements changed around dgamma, dbeta, behind the workspace", float(dg.outside() + db.outside() + ws.outside()), 0.0))
+    out.append((f"{tag} e4t_layernorm_param_grad: dgamma (finite, vs fp64)", _finite_rel(dg.view.reshape(-1), ga64), 1e-3))
+    out.append((f"{tag} e4t_layernorm_param_grad: dbeta (finite, vs fp64)", _finite_rel(db.view.reshape(-1), be64), 1e-3))
+    dg, db, ws = _Guarded(1, D, f32, dev), _Guarded(1, D, f32, dev), _Workspace(2 * ns * D * 4, dev)
+    code = lib.e4t_layernorm_param_grad(_ptr(xg), _ptr(dyg), _ptr(stg), M, D, dg.ptr, db.ptr, 0, ws.ptr, ws.bytes - 4, _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_layernorm_param_grad, workspace 4 bytes short: return code + 22", float(code + 22), 0.0))
+    out.append((f"{tag} e4t_layernorm_param_grad, workspace 4 bytes short: output / workspace words changed", float(dg.touched() + db.touched() + int((ws.buf != SENT32).sum())), 0.0))
+    # e4t_colsum over the same rows as a column slice of a wider matrix (ldx = D + 8), NaN in the columns beside it and the rows around it
+    wide = torch.full((M + 2 * NORM_GUARD_ROWS, D + 8), float("nan"), dtype=bf16, device=dev)
+    wide[NORM_GUARD_ROWS:NORM_GUARD_ROWS + M, :D] = x
+    o, ws = _Guarded(1, D, f32, dev), _Workspace(ns * D * 4, dev)
+    code = lib.e4t_colsum(wide[NORM_GUARD_ROWS:].data_ptr(), D + 8, M, D, o.ptr, 0, ws.ptr, ws.bytes, _stream())
+    torch.cuda.synchronize()
+    out.append((f"{tag} e4t_colsum: return code", float(code), 0.0))
+    out.append((f"{tag} e4t_colsum: sentinel elements changed around out, behind the workspace", float(o.outside() + ws.outside()), 0.0))
+    out.append((f"{tag} e4t_colsum: out (finite, vs fp64)", _finite_rel(o.view.reshape(-1), x.to(f64).sum(0)), 1e-3))
+    return out
+
+
+def _norm_rejections(hip, dev):
+    """calls the library must refuse with -22 (E4T_REQUIRE), an error text, and every output word untouched; none launches a kernel"""
+    from e4t.ops import _stream
+    lib, out = hip.lib, []
+    st = _stream()
+    src = torch.zeros(1 << 16, dtype=bf16, device=dev)            # any input: never read
+    par = torch.ones(8192, dtype=f32, device=dev)                # gamma / beta / statistics
+    X, P = src.data_ptr(), par.data_ptr()
+
+    def outs():
+        return _Guarded(64, 512, bf16, dev), _Guarded(64, 512, bf16, dev), _Guarded(64, 2, f32, dev), _Workspace(1 << 16, dev)
+
+    def row(name, fn, word):
+        y, y2, s, ws = outs()
+        code = fn(y, y2, s, ws)
+        torch.cuda.synchronize()
+        err = _last_error(lib)
+        out.append((f"rejected: {name}: return code + 22", float(code + 22), 0.0))
+        out.append((f"rejected: {name}: error text names {word!r} (got {err!r})", float(word not in err), 0.0))
+        out.append((f"rejected: {name}: output / workspace words changed", float(y.touched() + y2.touched() + s.touched() + int((ws.buf != SENT32).sum())), 0.0))
+
+    def fwd(C1, C2, G, x2=None, B=1, HW=8):
+        return lambda y, y2, s, ws: lib.e4t_groupnorm_fwd(X, C1, x2, C2, P, P, y.ptr, s.ptr, B, HW, G, 1e-5, 1, ws.ptr, ws.bytes, st)
+
+    def bwd(C1, C2, G, x2=None, add2=None, dx2=False):
+        return lambda y, y2, s, ws: lib.e4t_groupnorm_bwd(X, C1, x2, C2, X, P, P, P, None, add2, y.ptr, y2.ptr if dx2 else None, None, 1, 8, G, 1, ws.ptr, ws.bytes, st)
+    row("groupnorm C1 % 8 != 0", fwd(36, 0, 4), "groupnorm")
+    row("groupnorm C % G != 0", fwd(320, 0, 33), "groupnorm")
+    row("groupnorm C > 4096", fwd(4104, 0, 8), "too large")
+    row("groupnorm G > 256", fwd(1024, 0, 512), "too large")
+    row("groupnorm x2 given with C2 == 0", fwd(64, 0, 32, x2=X), "x2/C2")
+    row("groupnorm C2 > 0 without x2", fwd(64, 64, 32), "x2/C2")
+    row("groupnorm_bwd dx2 missing with C2 > 0", bwd(64, 64, 32, x2=X), "groupnorm_bwd")
+    row("groupnorm_bwd add2 given with C2 == 0", bwd(64, 0, 32, add2=X, dx2=False), "groupnorm_bwd")
+    cs = lambda C1, B, HW: lambda y, y2, s, ws: lib.e4t_groupnorm_fwd_cs(X, C1, P, None, 0, None, P, P, y.ptr, s.ptr, B, HW, 32, 1e-5, 1, ws.ptr, ws.bytes, st)
+    row("groupnorm_fwd_cs HW % 32 != 0", cs(64, 1, 40), "groupnorm_fwd_cs")
+    row("groupnorm_fwd_cs B48 HW1024 (32 blocks, 21 chunks)", cs(64, 48, 1024), "do not split")
+    ln = lambda D, fn=lib.e4t_layernorm_fwd, x=X: lambda y, y2, s, ws: fn(x, P, P, y.ptr, s.ptr, 4, D, 1e-5, st)
+    row("layernorm D % 8 != 0", ln(36), "layernorm")
+    row("layernorm D = 1544", ln(1544), "layernorm")
+    row("layernorm_fwd_f32 x offset by 8 bytes", ln(64, lib.e4t_layernorm_fwd_f32, P + 8), "16-byte aligned")
+    row("layernorm_bwd D = 1544", lambda y, y2, s, ws: lib.e4t_layernorm_bwd(X, X, P, P, None, y.ptr, 4, 1544, st), "layernorm")
+    row("colsum ldx % 8 != 0", lambda y, y2, s, ws: lib.e4t_colsum(X, 68, 16, 64, s.ptr, 0, ws.ptr, ws.bytes, st), "colsum")
+    return out
+
+
+def check_norm_guards(hip, emu, dev):
+    """Every norm entry point through the C ABI with each output between sentinel rows, the workspace exactly the required size with sentinels behind
+    it (4 bytes less: -22, nothing written), every input between whole rows of NaN (an out-of-range read that reaches a sum, or a masked lane that
+    multiplies by 0, turns the result non-finite: the rows are `finite and within tolerance of fp64`); then the argument checks (-22, error text,
+    outputs untouched)."""
+    out = []
+    for c in GN_GUARD_CASES:
+        out += _guard_groupnorm(hip, dev, c)
+    for case in LN_GUARD_CASES:
+        out += _guard_layernorm(hip, dev, case)
+    return out + _norm_rejections(hip, dev)
 
 
 def check_streaming(hip, emu, dev):
@@ -1037,6 +1672,58 @@ def check_streaming(hip, emu, dev):
     o1 = torch.zeros(2, 320, dtype=f32, device=dev); o2 = torch.zeros_like(o1)
     hip.spatial_mean(big, 2, 4096, o1, 0); emu.spatial_mean(big, 2, 4096, o2, 0)
     out.append(("spatial_mean 4096x320", rel(o1, o2), TOLF * 5))
+    return out + _check_grid_stride(hip, emu, dev)
+
+
+STRIDE_ITEMS, STRIDE_TAIL = 2048 * 256 + 333, 333      # = 107 * 4903 work items: a full grid of 2048 blocks, then a ragged second trip of 333 items
+
+
+def _check_grid_stride(hip, emu, dev):
+    """Every kernel of elementwise.hip launched through grid_for() caps its grid (2048 blocks of 256; 4096 for the weight relayout and AdamW) and
+    walks the rest with a grid-stride loop: one case per kernel whose work is one full grid plus a ragged second trip, with the existing tolerance,
+    and the items of the second trip once more on their own (333 of 524621 items move a whole-tensor relative L2 by 2.5 % when they are garbage;
+    a subtler error in them would drown)."""
+    out = []
+    g = gen(181, dev)
+    N, T = STRIDE_ITEMS, STRIDE_TAIL
+
+    def rows(name, got, ref, tol, tail):
+        """tail: the output elements (flat, trailing) the second trip wrote"""
+        out.append((f"{name}, {N} items", rel(got, ref), tol))
+        out.append((f"{name}, {N} items: the {T} items of the second trip", rel(got.reshape(-1)[-tail:], ref.reshape(-1)[-tail:]), tol))
+    x, dy = rnd(g, N, 8, dev=dev), rnd(g, N, 8, dev=dev)
+    for op in (0, 1):      # silu forward / backward (one forward, one backward op: the loop is the op's own)
+        rows(f"unary op{op}", hip.unary(x, op, dy if op & 1 else None), emu.unary(x, op, dy if op & 1 else None), TOL1, T * 8)
+    rows("add", hip.add(x, dy), emu.add(x, dy), TOL1, T * 8)
+    u = rnd(g, N, 16, dev=dev)      # H = 8: one item per row
+    rows("geglu fwd", hip.geglu_fwd(u), emu.geglu_fwd(u), TOL1, T * 8)
+    rows("geglu bwd", hip.geglu_bwd(u, dy), emu.geglu_bwd(u, dy), TOL1, T * 16)
+    xx = rnd(g, 2 * 107 * 2 * 4903, 8, dev=dev)      # one image of 214 x 9806 pixels, 8 channels -> 107 x 4903
+    rows("sumpool2", hip.sumpool2(xx, 1, 107, 4903), emu.sumpool2(xx, 1, 107, 4903), TOL1, T * 8)
+    del xx
+    gg = rnd(g, 107, 16, dtype=f32, dev=dev)
+    rows("spatial_mean_bwd", hip.spatial_mean_bwd(gg, x, 107, 4903, 8, 8), emu.spatial_mean_bwd(gg, x, 107, 4903, 8, 8), TOL1, T * 8)
+    px = torch.rand(4, 3, 512, 512, generator=g, device=dev) * 2 - 1      # 4 * 3 * 224 * 224 = 602112 items: the second trip holds the last 77824
+    got, ref = hip.clip_preprocess(px, 224, 14, 640), emu.clip_preprocess(px, 224, 14, 640)
+    out.append(("clip_preprocess B4 512->224 p14 (602112 items)", rel(got, ref), TOL1))
+    out.append(("clip_preprocess B4 512->224 p14: the last image (items 451584 up; the second trip starts at 524288)", rel(got[3 * 256:], ref[3 * 256:]), TOL1))
+    w4 = rnd(g, 320, 320, 3, 3, scale=0.05, dtype=f32, dev=dev)      # 2 * 320 * 9 * 320 = 1843200 items against a grid of 4096 blocks
+    (wf, wd), (wf2, wd2) = hip.conv_weight_prepare(w4), emu.conv_weight_prepare(w4)
+    out.append(("conv_weight_prepare 320->320 fwd layout (1843200 items, grid cap 4096)", rel(wf, wf2), 0.0))
+    out.append(("conv_weight_prepare 320->320 dgrad layout", rel(wd, wd2), 0.0))
+    out.append(("conv_weight_prepare 320->320 dgrad layout: the last 794624 items (the second trip)", rel(wd.reshape(-1)[-794624:], wd2.reshape(-1)[-794624:]), 0.0))
+    n = 4096 * 1024 + 4 * T + 1      # AdamW: four elements per thread, grid cap 4096; the last thread holds one element
+    p = rnd(g, n, dtype=f32, dev=dev); gr = rnd(g, n, dtype=f32, dev=dev); m = rnd(g, n, dtype=f32, dev=dev) * 0.1; v = rnd(g, n, dtype=f32, dev=dev).abs() * 0.01
+    p2, m2, v2 = p.clone(), m.clone(), v.clone()
+    hip.adamw(p, gr, m, v, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 3, 0.5)
+    emu.adamw(p2, gr, m2, v2, 1e-3, 0.9, 0.999, 1e-8, 1e-2, 3, 0.5)
+    for nm, a, b in (("p", p, p2), ("m", m, m2), ("v", v, v2)):
+        out.append((f"adamw {nm}, {n} elements", rel(a, b), TOLF))
+        out.append((f"adamw {nm}, {n} elements: the {4 * T + 1} elements of the second trip", rel(a[-(4 * T + 1):], b[-(4 * T + 1):]), TOLF))
+    del p, gr, m, v, p2, m2, v2
+    wdm = rnd(g, N, dtype=f32, dev=dev)      # masked_mse_bwd: dpred = g * 2 / den * wd, den = stats[1]
+    stats, up = torch.tensor([0.25, 37.0, 0.0, 0.0], dtype=f32, device=dev), torch.tensor([0.7], dtype=f32, device=dev)
+    rows("masked_mse_bwd", hip.masked_mse_bwd(wdm, stats, up), (wdm.double() * (0.7 * 2.0 / 37.0)).float(), TOLF, T)
     return out
 
 
@@ -1180,6 +1867,7 @@ def all_checks(hip, emu, dev, ops_mod):
     yield "conv_guards", lambda: check_conv_guards(hip, emu, dev)
     yield "attention", lambda: check_attention(hip, emu, dev)
     yield "norms", lambda: check_norms(hip, emu, dev)
+    yield "norm_guards", lambda: check_norm_guards(hip, emu, dev)
     yield "streaming", lambda: check_streaming(hip, emu, dev)
     yield "wo", lambda: check_wo(hip, emu, dev, ops_mod)
     yield "image_prep", lambda: check_image_prep(hip, emu, dev)
