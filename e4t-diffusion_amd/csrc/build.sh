@@ -8,7 +8,7 @@ SRCS="core gemm attention norm wo elementwise image comm tome"
 mkdir -p obj
 pids=()
 for f in $SRCS; do
-  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || { [ $f = gemm ] && { [ gemm_common.h -nt obj/$f.o ] || [ gemm_dma_kernel.inc -nt obj/$f.o ] || [ gemm_pq_kernel.inc -nt obj/$f.o ]; }; } || [ ../../include/e4t_hip.h -nt obj/$f.o ]; then
+  if [ ! -f obj/$f.o ] || [ $f.hip -nt obj/$f.o ] || [ common.h -nt obj/$f.o ] || { [ $f = elementwise ] && { [ adamw_kernel.inc -nt obj/$f.o ] || [ adamw_rank_kernel.inc -nt obj/$f.o ]; }; } || { [ $f = gemm ] && { [ gemm_common.h -nt obj/$f.o ] || [ gemm_dma_kernel.inc -nt obj/$f.o ] || [ gemm_pq_kernel.inc -nt obj/$f.o ]; }; } || [ ../../include/e4t_hip.h -nt obj/$f.o ]; then
     EXTRA=""
     [ $f = image ] && EXTRA="-ffp-contract=off"      # byte-exact INTER_AREA: float ops must not be fused (see image.hip)
     [ $f = attention ] && EXTRA="-fno-slp-vectorize" # packing is chosen per kernel family in the source (attention.hip: PK_REG / PK_DMA); the SLP vectorizer's own costs the dh-40 backward 30 us

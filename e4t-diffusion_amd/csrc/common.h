@@ -165,5 +165,9 @@ __device__ __forceinline__ float geglu_f(float a, float g) { return a * gelu_f(g
 __device__ __forceinline__ float geglu_da_f(float d, float g) { return d * gelu_f(g); }
 __device__ __forceinline__ float geglu_dg_f(float d, float a, float g) { return d * a * dgelu_f(g); }
 
+// EMA of a weight per element: e' = e - w * (e - p) with w = 1 - decay and p the value just stored (fp32).  The ONE statement of this arithmetic, used by
+// adamw_ema_kernel, adamw_rank_ema_kernel and ema_update_kernel (elementwise.hip); the fused multiply-add is spelled out so that no context contracts it differently
+__device__ __forceinline__ float ema_f(float e, float p, float w) { return fmaf(-w, e - p, e); }
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }

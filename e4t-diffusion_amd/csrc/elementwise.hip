@@ -239,34 +239,31 @@ __global__ __launch_bounds__(256) void clip_preprocess_kernel(const float* in, b
 // ---- fused AdamW over a flat fp32 buffer (torch.optim.AdamW semantics: decoupled weight decay) ----
 // hyper != nullptr: lr, bc1, bc2_sqrt and the gradient scale are read from DEVICE memory ([4] floats) instead of the launch arguments,
 // so that a captured (hipGraph) training step replays with the values of ITS step (e4t_adamw_hyper); same arithmetic either way.
+// EMA of the weights in the same pass (adamw_ema_kernel): 36 B per parameter instead of 28 + 12 for a pass of its own.  One body, included
+// into both kernels (adamw_kernel.inc).
 __global__ __launch_bounds__(256) void adamw_kernel(float* p, const float* g, float* m, float* v, long long n, float lr, float b1, float b2,
                                                     float eps, float wd, float bc1, float bc2_sqrt, float gscale, const float* hyper) {
-  if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; gscale = hyper[3]; }
+  constexpr bool EMA = false;
+  float* const ema = nullptr;
+  float ema_w = 0.f;
+#include "adamw_kernel.inc"
+}
+__global__ __launch_bounds__(256) void adamw_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float b1,
+                                                        float b2, float eps, float wd, float bc1, float bc2_sqrt, float gscale, float ema_w,
+                                                        const float* hyper) {
+  constexpr bool EMA = true;
+#include "adamw_kernel.inc"
+}
+
+// the EMA rule alone, for weights that something else updated (a stock optimiser over the native modules); w_dev != nullptr: w from device memory
+__global__ __launch_bounds__(256) void ema_update_kernel(float* ema, const float* p, long long n, float w, const float* w_dev) {
+  if (w_dev) w = w_dev[0];
   for (long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (long long)gridDim.x * 1024) {
     if (i + 4 <= n) {
-      float4 P = *(float4*)(p + i), M = *(float4*)(m + i), V = *(float4*)(v + i);
-      const float4 G = *(const float4*)(g + i);
-      float pp[4] = {P.x, P.y, P.z, P.w}, mm[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
-      const float gg[4] = {G.x * gscale, G.y * gscale, G.z * gscale, G.w * gscale};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        pp[k] *= 1.f - lr * wd;
-        mm[k] = b1 * mm[k] + (1.f - b1) * gg[k];
-        vv[k] = b2 * vv[k] + (1.f - b2) * gg[k] * gg[k];
-        const float denom = sqrtf(vv[k]) / bc2_sqrt + eps;
-        pp[k] -= (lr / bc1) * mm[k] / denom;
-      }
-      *(float4*)(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-      *(float4*)(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-      *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
+      const float4 E = *(float4*)(ema + i), P = *(const float4*)(p + i);
+      *(float4*)(ema + i) = make_float4(ema_f(E.x, P.x, w), ema_f(E.y, P.y, w), ema_f(E.z, P.z, w), ema_f(E.w, P.w, w));
     } else {
-      for (long long j = i; j < n; ++j) {
-        float pp = p[j] * (1.f - lr * wd);
-        const float gg = g[j] * gscale;
-        const float mm = b1 * m[j] + (1.f - b1) * gg, vv = b2 * v[j] + (1.f - b2) * gg * gg;
-        pp -= (lr / bc1) * mm / (sqrtf(vv) / bc2_sqrt + eps);
-        p[j] = pp; m[j] = mm; v[j] = vv;
-      }
+      for (long long j = i; j < n; ++j) ema[j] = ema_f(ema[j], p[j], w);
     }
   }
 }
@@ -282,66 +279,17 @@ template <int RB>
 __global__ __launch_bounds__(320) void adamw_rank_kernel(float* p, float* m, float* v, const bf16_t* G, const bf16_t* Z, int rows, int cols, int K,
                                                          int ldg, long long ldz, float lr, float b1, float b2, float eps, float wd, float bc1,
                                                          float bc2_sqrt, float gscale, const float* hyper) {
-  if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; gscale = hyper[3]; }
-  __shared__ float gs[16 * RB];                      // G[k0 + k][r0 + rr] as fp32, [rr][k]
-  const int slot = blockIdx.y, r0 = blockIdx.x * RB;
-  const int Q = cols >> 2;
-  for (int q = threadIdx.x; q < (Q + (int)blockDim.x - 1) / (int)blockDim.x * (int)blockDim.x; q += blockDim.x) {      // (uniform trip count: barriers inside)
-    const bool on = q < Q;
-    float acc[RB][4];
-#pragma unroll
-    for (int rr = 0; rr < RB; ++rr)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[rr][j] = 0.f;
-    for (int k0 = 0; k0 < K; k0 += 16) {
-      __syncthreads();
-      for (int i = threadIdx.x; i < 16 * RB; i += blockDim.x) {
-        const int rr = i >> 4, k = i & 15;
-        gs[i] = (k0 + k < K && r0 + rr < rows) ? bf2f(G[(long long)(k0 + k) * ldg + r0 + rr]) : 0.f;
-      }
-      float z[16][4];
-#pragma unroll
-      for (int k = 0; k < 16; ++k) {
-        uint2 w = make_uint2(0u, 0u);
-        if (on && k0 + k < K) w = *(const uint2*)(Z + (long long)(k0 + k) * ldz + (long long)slot * cols + 4 * q);
-        unpack4(w, z[k]);
-      }
-      __syncthreads();
-#pragma unroll
-      for (int rr = 0; rr < RB; ++rr) {
-        const float4* g4 = (const float4*)(gs + rr * 16);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-          const float4 g = g4[kk];                   // broadcast read
-          const float gk[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-          for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[rr][j] = fmaf(gk[u], z[kk * 4 + u][j], acc[rr][j]);
-        }
-      }
-    }
-    if (!on) continue;
-#pragma unroll
-    for (int rr = 0; rr < RB; ++rr) {
-      if (r0 + rr >= rows) continue;
-      const long long i = ((long long)slot * rows + r0 + rr) * cols + 4 * q;
-      float4 P = *(float4*)(p + i), M = *(float4*)(m + i), V = *(float4*)(v + i);
-      float pp[4] = {P.x, P.y, P.z, P.w}, mm[4] = {M.x, M.y, M.z, M.w}, vv[4] = {V.x, V.y, V.z, V.w};
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float gg = acc[rr][j] * gscale;
-        pp[j] *= 1.f - lr * wd;
-        mm[j] = b1 * mm[j] + (1.f - b1) * gg;
-        vv[j] = b2 * vv[j] + (1.f - b2) * gg * gg;
-        const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
-        pp[j] -= (lr / bc1) * mm[j] / denom;
-      }
-      *(float4*)(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
-      *(float4*)(m + i) = make_float4(mm[0], mm[1], mm[2], mm[3]);
-      *(float4*)(v + i) = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    }
-  }
+  constexpr bool EMA = false;
+  float* const ema = nullptr;
+  float ema_w = 0.f;
+#include "adamw_rank_kernel.inc"
+}
+template <int RB>
+__global__ __launch_bounds__(320) void adamw_rank_ema_kernel(float* p, float* m, float* v, float* ema, const bf16_t* G, const bf16_t* Z, int rows, int cols,
+                                                             int K, int ldg, long long ldz, float lr, float b1, float b2, float eps, float wd, float bc1,
+                                                             float bc2_sqrt, float gscale, float ema_w, const float* hyper) {
+  constexpr bool EMA = true;
+#include "adamw_rank_kernel.inc"
 }
 
 // sum of squares of a flat fp32 buffer -> partial[blockIdx.x]
@@ -551,6 +499,43 @@ extern "C" int e4t_adamw_rank(float* p, float* m, float* v, const void* G, const
   hipLaunchKernelGGL((adamw_rank_kernel<RB>), dim3(cdiv(rows, RB), n), dim3(threads), 0, (hipStream_t)s, p, m, v, (const bf16_t*)G, (const bf16_t*)Z, rows, cols, K,
                      ldg, ldz, hyper_dev ? 0.f : lr, beta1, beta2, eps, weight_decay, bc1, bc2, hyper_dev ? 1.f : grad_scale, hyper_dev);
   E4T_CHECK_LAUNCH("adamw_rank_kernel");
+  return 0;
+}
+extern "C" int e4t_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, int step, float grad_scale, float ema_w, const float* hyper_dev, e4t_stream s) {
+  E4T_REQUIRE(p && g && m && v && ema && n > 0 && (hyper_dev || step >= 1), "adamw_ema: bad arguments");
+  E4T_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)hyper_dev) & 15) == 0,
+              "adamw_ema: buffers must be 16-B aligned");
+  const float bc1 = hyper_dev ? 1.f : 1.f - powf(beta1, (float)step), bc2 = hyper_dev ? 1.f : sqrtf(1.f - powf(beta2, (float)step));
+  E4T_LOG_LAUNCH("adamw_ema_kernel|n%lld|%.0f|0", (long long)n, 36.0 * (double)n);
+  hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid_for((n + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)s, p, g, m, v, ema, n, hyper_dev ? 0.f : lr, beta1, beta2, eps,
+                     weight_decay, bc1, bc2, hyper_dev ? 1.f : grad_scale, hyper_dev ? 0.f : ema_w, hyper_dev);
+  E4T_CHECK_LAUNCH("adamw_ema_kernel");
+  return 0;
+}
+extern "C" int e4t_adamw_rank_ema(float* p, float* m, float* v, float* ema, const void* G, const void* Z, int n, int rows, int cols, int K, int ldg,
+                                  long long ldz, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                                  const float* hyper_dev, e4t_stream s) {
+  E4T_REQUIRE(p && m && v && ema && G && Z && n > 0 && rows > 0 && cols > 0 && K > 0 && (hyper_dev || step >= 1), "adamw_rank_ema: bad arguments");
+  E4T_REQUIRE(cols % 4 == 0 && ldz % 4 == 0 && ldg >= rows && ldz >= (long long)n * cols, "adamw_rank_ema: cols and the Z row stride must be multiples of 4");
+  E4T_REQUIRE((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema) & 15) == 0 && ((uintptr_t)Z & 7) == 0 && ((uintptr_t)hyper_dev & 15) == 0,
+              "adamw_rank_ema: buffers must be 16-B (factors 8-B) aligned");
+  const float bc1 = hyper_dev ? 1.f : 1.f - powf(beta1, (float)step), bc2 = hyper_dev ? 1.f : sqrtf(1.f - powf(beta2, (float)step));
+  constexpr int RB = 8;
+  const int threads = min(320, (cols / 4 + 63) / 64 * 64);
+  E4T_LOG_LAUNCH("adamw_rank_ema_kernel<%d>|n%d rows%d cols%d K%d|%.0f|%.0f", RB, n, rows, cols, K, 32.0 * n * rows * cols, 2.0 * n * rows * (double)cols * K);
+  hipLaunchKernelGGL((adamw_rank_ema_kernel<RB>), dim3(cdiv(rows, RB), n), dim3(threads), 0, (hipStream_t)s, p, m, v, ema, (const bf16_t*)G, (const bf16_t*)Z, rows,
+                     cols, K, ldg, ldz, hyper_dev ? 0.f : lr, beta1, beta2, eps, weight_decay, bc1, bc2, hyper_dev ? 1.f : grad_scale, hyper_dev ? 0.f : ema_w,
+                     hyper_dev);
+  E4T_CHECK_LAUNCH("adamw_rank_ema_kernel");
+  return 0;
+}
+extern "C" int e4t_ema_update(float* ema, const float* p, long long n, float ema_w, const float* w_dev, e4t_stream s) {
+  E4T_REQUIRE(ema && p && n > 0, "ema_update: bad arguments");
+  E4T_REQUIRE((((uintptr_t)ema | (uintptr_t)p) & 15) == 0 && ((uintptr_t)w_dev & 3) == 0, "ema_update: buffers must be 16-B aligned");
+  E4T_LOG_LAUNCH("ema_update_kernel|n%lld|%.0f|0", (long long)n, 12.0 * (double)n);
+  hipLaunchKernelGGL(ema_update_kernel, dim3(grid_for((n + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)s, ema, p, n, w_dev ? 0.f : ema_w, w_dev);
+  E4T_CHECK_LAUNCH("ema_update_kernel");
   return 0;
 }
 extern "C" int e4t_sumsq_partial(const float* g, long long n, float* partial, int nblocks, e4t_stream s) {

@@ -179,16 +179,18 @@ def load_clip_tower(enc, clip_source: str) -> str:
 
 
 def build_models(dev, base_dir: Optional[str], variant: str, seed: int, freeze_clip_vision: bool = True, e4t_dir: Optional[str] = None,
-                 need_vae_encoder: bool = True, clip_source: Optional[str] = None, revision: Optional[str] = None):
+                 need_vae_encoder: bool = True, clip_source: Optional[str] = None, revision: Optional[str] = None, use_ema: bool = False):
     """(unet, e4t_encoder, text_encoder, vae_encoder) on `dev` (pretrain_e4t.py:233-251, tuning_e4t.py:97-118).
     base_dir: Stable Diffusion checkpoint in either layout of the module docstring (a hub id is looked up in the local cache at
     `revision`) or None = random init from `seed`.  The pipeline layout's configs decide the architecture; otherwise `variant` does.
     clip_source: --clip_model_name_or_path for the E4T encoder's CLIP tower; None = not requested, 'none' = random init.  It is
     not read when e4t_dir holds an encoder.pt (that wins).  If it names nothing on this machine, a pipeline-layout base exits
     listing the paths searched, a flat-layout base warns and keeps the random tower, and a random base keeps it.
-    e4t_dir: directory with weight_offsets.pt | unet.pt and encoder.pt of an earlier E4T run, loaded on top (both strict)."""
+    e4t_dir: directory with weight_offsets.pt | unet.pt and encoder.pt of an earlier E4T run, loaded on top (both strict);
+    use_ema: its weight_offsets_ema.pt and encoder_ema.pt instead (ema_file_names: SystemExit when they are not there)."""
     from . import builders
     from . import checkpoints as ck
+    names = ema_file_names(e4t_dir, use_ema)
     if base_dir and not os.path.exists(base_dir):
         base_dir = ck.resolve_model_dir(base_dir, revision)
     pipeline = ck.is_pipeline_layout(base_dir)
@@ -231,12 +233,12 @@ def build_models(dev, base_dir: Optional[str], variant: str, seed: int, freeze_c
             else:
                 print(f"[e4t] {ex}: randomly initialised CLIP tower (random base model)")
     if e4t_dir:
-        for fn in ("weight_offsets.pt", "unet.pt"):
+        for fn in ((names["weight_offsets.pt"],) if use_ema else ("weight_offsets.pt", "unet.pt")):
             f = os.path.join(e4t_dir, fn)
             if os.path.exists(f):
-                checked_load(unet, f, (lambda k: "wo" not in k) if fn == "weight_offsets.pt" else (lambda k: False), what=f)
+                checked_load(unet, f, (lambda k: "wo" not in k) if fn != "unet.pt" else (lambda k: False), what=f)
                 print(f"Resuming from {f}")
-        f = os.path.join(e4t_dir, "encoder.pt")
+        f = os.path.join(e4t_dir, names["encoder.pt"])
         if os.path.exists(f):
             checked_load(enc, f, what=f)
             print(f"Resuming from {f}")
@@ -267,3 +269,43 @@ def apply_tome_args(unet, args):
     from . import tome
     g = torch.Generator().manual_seed(int(getattr(args, "seed", None) or 0))
     return tome.apply_tome(unet, args.tome_ratio, use_rand=not args.tome_no_rand, generator=g)
+
+
+# ---- EMA of the trained weights (E4TTrainer(ema_decay=...)): like ToMe a choice of the command line, config.json does not record it --------------
+EMA_ARGS = ("use_ema", "ema_decay")              # utils.save_config leaves them out of config.json
+EMA_DEFAULT_DECAY = 0.9999
+EMA_FILES = {"weight_offsets.pt": "weight_offsets_ema.pt", "encoder.pt": "encoder_ema.pt"}
+
+
+def add_ema_args(p, training=True):
+    """training=True (pretrain_e4t.py): --use_ema keeps the average and writes the *_ema files, --ema_decay sets its decay.
+    training=False (tuning_e4t.py, inference.py): --use_ema loads the *_ema files of the directory given."""
+    if training:
+        p.add_argument("--use_ema", action="store_true",
+                       help="keep an exponential moving average of the trained weights (fused into AdamW): every checkpoint directory gains "
+                            "weight_offsets_ema.pt / encoder_ema.pt and the training-time samples are drawn from the average")
+        p.add_argument("--ema_decay", type=float, default=None,
+                       help=f"EMA decay in (0, 1), default {EMA_DEFAULT_DECAY}; warmed up as min(decay, (1 + t) / (10 + t)).  Needs --use_ema")
+    else:
+        p.add_argument("--use_ema", action="store_true",
+                       help="load the averaged weights (weight_offsets_ema.pt / encoder_ema.pt, written by pretrain_e4t.py --use_ema)")
+
+
+def check_ema_args(p, args):
+    decay = getattr(args, "ema_decay", None)
+    if decay is not None and not args.use_ema:
+        p.error("--ema_decay needs --use_ema")
+    if decay is not None and not 0.0 < decay < 1.0:
+        p.error("--ema_decay must lie in (0, 1)")
+    if args.use_ema and hasattr(args, "ema_decay") and decay is None:
+        args.ema_decay = EMA_DEFAULT_DECAY
+
+
+def ema_file_names(e4t_dir, use_ema):
+    """file name -> the name to read in `e4t_dir`: with --use_ema the *_ema twins, which must both be there (SystemExit names what is missing)"""
+    if not use_ema:
+        return {k: k for k in EMA_FILES}
+    missing = [v for v in EMA_FILES.values() if not (e4t_dir and os.path.exists(os.path.join(e4t_dir, v)))]
+    if missing:
+        raise SystemExit(f"--use_ema: {e4t_dir!r} holds no {' / '.join(missing)} (averaged weights are written by pretrain_e4t.py --use_ema)")
+    return dict(EMA_FILES)

@@ -685,6 +685,32 @@ class HipBackend:
             _ptr(p), _ptr(m), _ptr(v), _ptr(G), _ptr(Z), n, rows, cols, K, G.stride(0), Z.stride(0), lr, beta1, beta2, eps, wd, int(step), grad_scale,
             _ptr(hyper), _stream()), "e4t_adamw_rank"), 24.0 * p.numel())
 
+    # ---- EMA of the trained weights: e' = e - ema_w * (e - p') in the pass that stores p' (ema_w = optimization.ema_weight(decay, step)) ----
+    def adamw_ema(self, p, g, m, v, ema, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, ema_w=0.0, hyper=None):
+        """adamw plus the EMA of p in the same pass.  hyper: device fp32 [8], {lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale, ema_w, 0, 0, 0},
+        which then replace lr / step / grad_scale / ema_w (replayable)"""
+        assert ema.dtype == f32 and ema.numel() == p.numel() and (hyper is None or hyper.numel() == 8)
+        self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_adamw_ema(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), lr, beta1, beta2, eps, wd,
+                                                                          int(step), grad_scale, ema_w, _ptr(hyper), _stream()), "e4t_adamw_ema"),
+                    36.0 * p.numel())
+
+    def adamw_rank_ema(self, p, m, v, ema, G, Z, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, ema_w=0.0, hyper=None):
+        """adamw_rank plus the EMA of the stack (ema [n, rows, cols], fp32) in the same pass; hyper as in adamw_ema"""
+        n, rows, cols = p.shape
+        K = G.shape[0]
+        assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and G.dtype == bf16 and Z.dtype == bf16
+        assert ema.is_contiguous() and ema.dtype == f32 and ema.shape == p.shape and (hyper is None or hyper.numel() == 8)
+        assert G.shape[1] == rows and Z.shape == (K, n * cols) and G.stride(1) == 1 and Z.stride(1) == 1
+        self._timed("adamw", 2.0 * p.numel() * K, lambda: _C.check(self.lib.e4t_adamw_rank_ema(
+            _ptr(p), _ptr(m), _ptr(v), _ptr(ema), _ptr(G), _ptr(Z), n, rows, cols, K, G.stride(0), Z.stride(0), lr, beta1, beta2, eps, wd, int(step), grad_scale,
+            ema_w, _ptr(hyper), _stream()), "e4t_adamw_rank_ema"), 32.0 * p.numel())
+
+    def ema_update(self, ema, p, ema_w, w_dev=None):
+        """the EMA rule alone over flat fp32 buffers, for weights that something else updated; w_dev: ema_w as one device float"""
+        assert ema.dtype == f32 and p.dtype == f32 and ema.numel() == p.numel()
+        self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_ema_update(_ptr(ema), _ptr(p), p.numel(), ema_w, _ptr(w_dev), _stream()), "e4t_ema_update"),
+                    12.0 * p.numel())
+
     def im2col_T(self, x, B, Hin, Win, Hout, Wout, mode):
         """bf16 [B*Hin*Win, C] -> [9*C, ld] with ld = B*Hout*Wout rounded up to 8 (zero padded): B operand of the wgrad GEMM"""
         assert x.is_contiguous()

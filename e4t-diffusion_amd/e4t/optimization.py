@@ -69,3 +69,16 @@ class LRSchedule:
 
     def step(self):
         self.step_count += 1
+
+
+def ema_weight(decay: float, t: int) -> float:
+    """Weight w = 1 - d_t of the parameters in the EMA update e' = e - w * (e - p) at the 1-based optimiser step t, with LDM's (LitEma) /
+    diffusers' (EMAModel) warm-up d_t = min(decay, (1 + t) / (10 + t)) so that the first steps are not dominated by the initial weights.
+    Computed in double and rounded ONCE to fp32 (returned as the Python float of that fp32 value): the eager launch argument, the step graph's
+    device scalar and the tests all take it from here, the only statement of the formula."""
+    import ctypes
+    if not 0.0 < decay < 1.0:
+        raise ValueError(f"EMA decay {decay!r} must lie in (0, 1)")
+    if t < 1:
+        raise ValueError(f"optimiser steps count from 1, got {t}")
+    return ctypes.c_float(1.0 - min(float(decay), (1.0 + t) / (10.0 + t))).value

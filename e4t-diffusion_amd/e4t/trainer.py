@@ -27,6 +27,7 @@ import torch.nn.functional as F
 from . import functional as Fn
 from . import ops
 from . import tome
+from .optimization import ema_weight
 
 f32 = torch.float32
 
@@ -105,7 +106,7 @@ class E4TTrainer:
     def __init__(self, unet, e4t_encoder, text_encoder, vae, *, lr=1e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  domain_embed_scale=0.1, reg_lambda=0.01, prediction_type="epsilon", class_token_id=0,
                  empty_prompt_ids: Optional[torch.Tensor] = None, process_group=None, device=None, tuning=False,
-                 max_grad_norm: Optional[float] = None, head_factor_exchange=True, collectives="torch"):
+                 max_grad_norm: Optional[float] = None, head_factor_exchange=True, collectives="torch", ema_decay: Optional[float] = None):
         self.unet, self.encoder, self.text_encoder, self.vae = unet, e4t_encoder, text_encoder, vae
         # data parallel: all-gather the two small factors of the 129-slot head's weight gradient instead of all-reducing the 845 MB
         # stack (_exchange_head_factors); needs the same per-rank batch size on every rank.  False = the stack rides the all-reduce.
@@ -147,6 +148,13 @@ class E4TTrainer:
             from .comm import LibraryComm
             self._lib_comm = LibraryComm.from_process_group(process_group)
         self.step_count = 0
+        # EMA of the trainable weights (LDM's LitEma, diffusers' --use_ema): a fourth flat fp32 buffer that AdamW's kernels move in
+        # the pass that stores the parameters (e4t_adamw_ema / e4t_adamw_rank_ema).  None = off: the launches and the state dict of a trainer without it.
+        if ema_decay is not None and not 0.0 < float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay={ema_decay!r}: a float in (0, 1), or None for no EMA")
+        self.ema_decay = None if ema_decay is None else float(ema_decay)
+        self.ema = None
+        self._ema_swapped = False            # inside ema_weights(): flat.data holds the average, no training step may run
         self.acp = ddpm_alphas_cumprod(device=self.device)
         self.max_grad_norm = max_grad_norm
         self.tuning = tuning
@@ -192,6 +200,8 @@ class E4TTrainer:
         self.comm_timing = None          # bench.py sets a dict: per-region enqueue times and the exposed wait of the last step
         if self.world > 1:
             self.sync_replicas(include_frozen=True)
+        if self.ema_decay is not None:
+            self.ema = self.flat.data.clone()          # after the broadcast: every rank's average starts from rank 0's weights
         ops.bump_weights_epoch()
         # constants of the loop (pretrain_e4t.py:561-583); with a trainable text encoder they are re-evaluated every step, detached,
         # as tuning_e4t.py:276-284 does
@@ -209,6 +219,8 @@ class E4TTrainer:
         bc(self.flat.data)
         if include_moments:
             bc(self.exp_avg); bc(self.exp_avg_sq)
+            if self.ema is not None:
+                bc(self.ema)
             cnt = torch.tensor([self.step_count], dtype=torch.int64, device=self.device)
             bc(cnt)
             self.step_count = int(cnt)
@@ -229,11 +241,11 @@ class E4TTrainer:
 
     def check_replicas(self):
         """every rank must hold bit-identical trainable state (deterministic kernels + the same all-reduced gradient): compare a
-        checksum vector — sum and sum of squares of the parameters, of exp_avg and of exp_avg_sq — across ranks (MIN == MAX);
+        checksum vector — sum and sum of squares of the parameters, of exp_avg and of exp_avg_sq (and of the EMA, when on) — across ranks (MIN == MAX);
         raises on every rank when they differ.  A non-finite state is reported as such, not as divergence (NaN != NaN)."""
         if self.world <= 1:
             return True
-        bufs = (self.flat.data, self.exp_avg, self.exp_avg_sq)
+        bufs = (self.flat.data, self.exp_avg, self.exp_avg_sq) + ((self.ema,) if self.ema is not None else ())
         if self.flat.data.is_cuda:
             be = ops.backend()
             c = torch.stack([x for b in bufs for x in (b.sum(dtype=torch.float64), be.sumsq(b).double())])
@@ -606,7 +618,11 @@ class E4TTrainer:
     def optimizer_step(self, deferred=None):
         """AdamW over the flat buffers.  deferred = ((lo, hi), handles) from all_reduce_grads(defer=...): the elements outside [lo, hi)
         are updated first, under that region's all-reduce, then the handles are waited for and [lo, hi) follows (element-wise update:
-        the split changes no bit)."""
+        the split changes no bit).  With an EMA (ema_decay) the same launches are the _ema entry points: the average moves in the pass that stores
+        the parameters, in every branch below."""
+        if self._ema_swapped:
+            raise RuntimeError("optimizer_step inside ema_weights(): the flat buffer holds the average, not the trained weights")
+        ema = self.ema
         if self._hyper is not None:
             # step-graph mode: lr / bias corrections / gradient scale live in device memory (refreshed by the host before every step, eager
             # or replayed), so the captured launch is the same launch at every step
@@ -615,14 +631,23 @@ class E4TTrainer:
                 self._write_hyper()
 
             def adamw(lo, hi):
-                ops.backend().adamw_hyper(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self._hyper,
-                                          self.betas[0], self.betas[1], self.eps, self.wd)
+                if ema is not None:
+                    ops.backend().adamw_ema(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], ema[lo:hi], 0.0,
+                                            self.betas[0], self.betas[1], self.eps, self.wd, 0, hyper=self._hyper)
+                else:
+                    ops.backend().adamw_hyper(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self._hyper,
+                                              self.betas[0], self.betas[1], self.eps, self.wd)
         else:
             self.step_count += 1
+            ema_w = ema_weight(self.ema_decay, self.step_count) if ema is not None else 0.0
 
             def adamw(lo, hi):
-                ops.backend().adamw(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr,
-                                    self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0 / self.world)
+                if ema is not None:
+                    ops.backend().adamw_ema(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], ema[lo:hi], self.lr,
+                                            self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0 / self.world, ema_w)
+                else:
+                    ops.backend().adamw(self.flat.data[lo:hi], self.flat.grad[lo:hi], self.exp_avg[lo:hi], self.exp_avg_sq[lo:hi], self.lr,
+                                        self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, 1.0 / self.world)
         factors, self._head_factors = self._head_factors, None
         if factors is not None:
             # the stack leads the flat buffer: [0, w_end) is updated from the factors, the ordinary launch starts behind it
@@ -632,7 +657,13 @@ class E4TTrainer:
             st = lambda buf: buf[:w_end].view(n, rows, cols)
             gb, Z = factors
             be = ops.backend()
-            if self._hyper is not None:
+            if ema is not None and self._hyper is not None:
+                be.adamw_rank_ema(st(self.flat.data), st(self.exp_avg), st(self.exp_avg_sq), st(ema), gb, Z, 0.0, self.betas[0], self.betas[1], self.eps,
+                                  self.wd, 0, hyper=self._hyper)
+            elif ema is not None:
+                be.adamw_rank_ema(st(self.flat.data), st(self.exp_avg), st(self.exp_avg_sq), st(ema), gb, Z, self.lr, self.betas[0], self.betas[1], self.eps,
+                                  self.wd, self.step_count, 1.0 / self.world, ema_w)
+            elif self._hyper is not None:
                 be.adamw_rank(st(self.flat.data), st(self.exp_avg), st(self.exp_avg_sq), gb, Z, 0.0, self.betas[0], self.betas[1], self.eps, self.wd, 0,
                               hyper=self._hyper)
             else:
@@ -677,8 +708,9 @@ class E4TTrainer:
         self._step_graph_on = bool(on)
         if on and self._hyper is None:
             # allocated once and kept for the trainer's lifetime: captured graphs hold its raw pointer
-            self._hyper = torch.zeros(4, dtype=f32, device=self.device)
-            self._hyper_ring = [[torch.zeros(4, dtype=f32).pin_memory(), None] for _ in range(self._HYPER_SLOTS)]
+            nh = 8 if self.ema is not None else 4          # with an EMA: [4] = its weight of the step, [5..7] reserved (zero)
+            self._hyper = torch.zeros(nh, dtype=f32, device=self.device)
+            self._hyper_ring = [[torch.zeros(nh, dtype=f32).pin_memory(), None] for _ in range(self._HYPER_SLOTS)]
         if not on:
             # graphs own whole-step memory pools: drop them (a later enable re-captures); _hyper stays
             self._step_graphs, self._seen_sigs = {}, set()
@@ -710,6 +742,8 @@ class E4TTrainer:
         host[1] = f(1.0 - libm.powf(self.betas[0], t))
         host[2] = libm.sqrtf(f(1.0 - libm.powf(self.betas[1], t)))
         host[3] = 1.0 / self.world
+        if self.ema is not None:
+            host[4] = ema_weight(self.ema_decay, self.step_count)
         self._hyper.copy_(host, non_blocking=True)
         ev = slot[1] = torch.cuda.Event()
         ev.record()
@@ -791,10 +825,51 @@ class E4TTrainer:
             enc._stack_grad_is_zero = ours
         self._accum_pending = False
 
+    # ---- EMA view of the weights ---------------------------------------------------------------------------------------------------
+    def ema_view_blocked(self):
+        """why ema_weights() would refuse to open right now (a sentence), or None"""
+        if self.ema is None:
+            return "this trainer keeps no EMA (ema_decay=None)"
+        if self._ema_swapped:
+            return "ema_weights() is already open"
+        if self._accum_pending:
+            return "micro-batch gradients are pending; finish the accumulation with a synchronising step first"
+        if self._next_px is not None or self._pref:
+            return "a prefetch is in flight; run the step it was announced for first"
+        if self._capturing or (self.flat.data.is_cuda and torch.cuda.is_current_stream_capturing()):
+            return "a graph capture is open"
+        return None
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the trainable weights ARE their EMA (sampling, saving the *_ema files): the average is copied into the flat
+        buffer, the raw weights wait in a temporary that lives only here and come back bit for bit on exit.  Both edges bump the weights
+        epoch, so no bf16 compute copy of either set survives the other.  Not while micro-batch gradients are pending or a prefetch is in
+        flight (both belong to the raw weights' next step), never inside a capture, and no training step runs inside it."""
+        why = self.ema_view_blocked()
+        if why:
+            raise RuntimeError(f"ema_weights(): {why}")
+        raw = self.flat.data.clone()
+        self.flat.data.copy_(self.ema)
+        self._ema_swapped = True
+        ops.bump_weights_epoch()
+        try:
+            yield self
+        finally:
+            self.flat.data.copy_(raw)
+            del raw
+            self._ema_swapped = False
+            ops.bump_weights_epoch()
+
     # ---- training state (accelerator.save_state / load_state of the reference, pretrain_e4t.py:536-558,659-663) ----------
     def state_dict(self):
-        return dict(params=self.flat.data.detach().cpu().clone(), exp_avg=self.exp_avg.cpu().clone(), exp_avg_sq=self.exp_avg_sq.cpu().clone(),
-                    step_count=self.step_count, lr=self.lr)
+        if self._ema_swapped:
+            raise RuntimeError("state_dict inside ema_weights(): the flat buffer holds the average, not the trained weights")
+        sd = dict(params=self.flat.data.detach().cpu().clone(), exp_avg=self.exp_avg.cpu().clone(), exp_avg_sq=self.exp_avg_sq.cpu().clone(),
+                  step_count=self.step_count, lr=self.lr)
+        if self.ema is not None:
+            sd.update(ema=self.ema.cpu().clone(), ema_decay=self.ema_decay)
+        return sd
 
     def load_state_dict(self, sd):
         if sd["params"].numel() != self.flat.data.numel():
@@ -803,6 +878,12 @@ class E4TTrainer:
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.step_count = int(sd["step_count"])
+        if self.ema is not None:
+            if "ema" in sd:
+                self.ema.copy_(sd["ema"])
+            else:        # a state saved without EMA: the average starts from the loaded parameters
+                warnings.warn("E4TTrainer: the training state holds no 'ema'; the average starts from the loaded parameters")
+                self.ema.copy_(self.flat.data)
         self.flat.grad.zero_()
         self.sync_replicas(include_moments=True)  # a per-rank-different checkpoint read must not start diverged replicas
         ops.bump_weights_epoch()                 # bf16 compute copies of the trainable weights are stale now
@@ -817,6 +898,8 @@ class E4TTrainer:
                     and loss_mask is None):
                 return self._graphed_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents)
             return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale, loss_mask)
+        if self._ema_swapped:
+            raise RuntimeError("train_step inside ema_weights(): the flat buffer holds the average, not the trained weights")
         tome.new_step(self.unet)       # token merging (opt-in): this step's draw, outside any capture; nothing for an unmarked UNet
         ts = self._training_stream()
         if ts is None or self._step_graph_on:          # (a replayed graph's branches run on the graph executor's own streams, wherever it is launched)

@@ -23,9 +23,10 @@ def weight_offset_state_dict(unet) -> dict:
     return {k: v for k, v in unet.state_dict().items() if "wo" in k}
 
 
-def save_e4t_unet(unet, save_dir):
+def save_e4t_unet(unet, save_dir, filename="weight_offsets.pt"):
+    """filename: "weight_offsets_ema.pt" for the averaged weights (called under E4TTrainer.ema_weights())"""
     os.makedirs(save_dir, exist_ok=True)
-    torch.save(weight_offset_state_dict(unet), os.path.join(save_dir, "weight_offsets.pt"))
+    torch.save(weight_offset_state_dict(unet), os.path.join(save_dir, filename))
 
 
 def load_weight_offsets(unet, path):
@@ -36,14 +37,14 @@ def load_weight_offsets(unet, path):
         raise RuntimeError(f"weight_offsets.pt does not match the UNet: missing {bad[:3]} unexpected {unexpected[:3]}")
 
 
-def save_e4t_encoder(encoder, save_dir):
+def save_e4t_encoder(encoder, save_dir, filename="encoder.pt"):
     os.makedirs(save_dir, exist_ok=True)
-    torch.save(encoder.state_dict(), os.path.join(save_dir, "encoder.pt"))
+    torch.save(encoder.state_dict(), os.path.join(save_dir, filename))
 
 
 def save_config(args_dict, save_dir):
-    from .cli_common import TOME_ARGS
-    args_dict = {k: v for k, v in args_dict.items() if k not in TOME_ARGS}      # token merging is a runtime choice, not part of the run
+    from .cli_common import EMA_ARGS, TOME_ARGS
+    args_dict = {k: v for k, v in args_dict.items() if k not in TOME_ARGS + EMA_ARGS}      # token merging and the EMA are runtime choices, not part of the run
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "config.json"), "w") as f:
         json.dump(args_dict, f, indent=2, default=str)

@@ -14,6 +14,9 @@
  *   - return value 0 = OK, negative errno-style code otherwise (-22 bad argument, -12 workspace,
  *     -5 launch failure); e4t_last_error() returns the message; nothing throws across the ABI;
  *   - one host thread per process/rank; re-entrant across streams.
+ *
+ * 74 entry points.  Optimiser: e4t_adamw / _hyper / _rank and, with the exponential moving average of the trained weights moved in
+ * the same pass, e4t_adamw_ema / e4t_adamw_rank_ema; e4t_ema_update is the average's rule alone.
  */
 #ifndef E4T_HIP_H
 #define E4T_HIP_H
@@ -360,6 +363,21 @@ int e4t_adamw_hyper(float* p, const float* g, float* m, float* v, long long n, c
 int e4t_adamw_rank(float* p, float* m, float* v, const void* G, const void* Z, int n, int rows, int cols, int K, int ldg, long long ldz,
                    float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, const float* hyper_dev,
                    e4t_stream stream);
+/* Exponential moving average (EMA) of the trained weights, LDM's LitEma / diffusers' --use_ema: e' = e - w * (e - p') in fp32, with p' the value
+ * the same thread has just computed and stores and w = 1 - decay of this step (e4t/optimization.py ema_weight).  One device helper holds the
+ * expression, so the three entry points below agree bit for bit.
+ * e4t_adamw_ema: e4t_adamw's update plus the rule in the same pass (36 B per parameter instead of 28 + 12).  hyper_dev != NULL: float[8],
+ * 16-byte aligned, {lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale} as e4t_adamw_hyper reads them, [4] = w, [5..7] reserved (zero); the lr / step /
+ * grad_scale / ema_w arguments are then ignored.  ema: n floats, 16-byte aligned. */
+int e4t_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, long long n, float lr, float beta1, float beta2, float eps,
+                  float weight_decay, int step, float grad_scale, float ema_w, const float* hyper_dev, e4t_stream stream);
+/* e4t_adamw_rank's update plus the rule; ema is the same [n][rows][cols] stack as p (32 B per parameter); hyper_dev as in e4t_adamw_ema. */
+int e4t_adamw_rank_ema(float* p, float* m, float* v, float* ema, const void* G, const void* Z, int n, int rows, int cols, int K, int ldg,
+                       long long ldz, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                       const float* hyper_dev, e4t_stream stream);
+/* The rule alone, for parameters that something else updated (a stock optimiser over the native modules): 12 B per parameter.
+ * w_dev != NULL: w is one float in device memory (ema_w ignored). */
+int e4t_ema_update(float* ema, const float* p, long long n, float ema_w, const float* w_dev, e4t_stream stream);
 int e4t_sumsq_partial(const float* g, long long n, float* partial, int nblocks, e4t_stream stream);                      /* tuning_e4t.py:335 grad-norm */
 
 /* ---------------------------------------------------------------- token merging (tome.hip) ---------- */

@@ -48,8 +48,10 @@ def parse_args():
     p.add_argument("--output", type=str, default="grid.png")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
+    cc.add_ema_args(p, training=False)
     args = p.parse_args()
     cc.check_tome_args(p, args)
+    cc.check_ema_args(p, args)
     return args
 
 
@@ -67,6 +69,8 @@ def setup(args, dev):
     cfg = AttributeDict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1)
     tok, sched = None, SCHEDULER_MAPPING[args.scheduler_type].stable_diffusion("epsilon" if args.unet_variant == "sd14" else "v_prediction")
     pipeline_cfgs = None
+    use_ema = getattr(args, "use_ema", False) and not args.random_init
+    names = cc.ema_file_names(args.pretrained_model_name_or_path, use_ema)     # --use_ema: exits here when the directory holds no averaged weights
     if not args.random_init:
         d = args.pretrained_model_name_or_path
         with open(os.path.join(d, "config.json")) as f:
@@ -103,10 +107,10 @@ def setup(args, dev):
             missing, unexpected = vae.load_state_dict(sd, strict=False)
             if missing or unexpected:
                 raise RuntimeError(f"{base}/vae.pt: missing {missing[:5]} unexpected {list(unexpected)[:5]}")
-        if os.path.exists(os.path.join(d, "unet.pt")):
+        if os.path.exists(os.path.join(d, "unet.pt")) and not use_ema:
             checked_load(unet, os.path.join(d, "unet.pt"))
         else:
-            load_weight_offsets(unet, os.path.join(d, "weight_offsets.pt"))
+            load_weight_offsets(unet, os.path.join(d, names["weight_offsets.pt"]))
         from transformers import CLIPTokenizer
         tok = CLIPTokenizer.from_pretrained(os.path.join(base, "tokenizer"))
         if os.path.exists(os.path.join(base, "scheduler", "scheduler_config.json")):
@@ -117,7 +121,7 @@ def setup(args, dev):
                                       safety_checker=None, feature_extractor=None, e4t_config=cfg, requires_safety_checker=False)
     if not args.random_init:
         d = args.pretrained_model_name_or_path
-        checked_load(enc, os.path.join(d, "encoder.pt"))
+        checked_load(enc, os.path.join(d, names["encoder.pt"]))
         if os.path.exists(os.path.join(d, "text_encoder.pt")):                                                  # inference.py:92-101
             checked_load(text, os.path.join(d, "text_encoder.pt"))        # written by --train_text_encoder: already holds the placeholder row
     unet.requires_grad_(False)

@@ -16,6 +16,7 @@ Artefacts keep the reference's names: `{output_dir}/{step}/config.json`, `weight
 from __future__ import annotations
 
 import argparse
+import contextlib
 import os
 import random
 import sys
@@ -79,8 +80,10 @@ def parse_args():
                         "holding <rel>/<stem>.png (or an image extension) for every image <rel>/<stem>.<ext>")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
+    cc.add_ema_args(p)
     args = p.parse_args()
     cc.check_tome_args(p, args)
+    cc.check_ema_args(p, args)
     if args.train_mask_dataset and (args.webdataset or args.iterable_dataset or args.synthetic_data):
         p.error("--train_mask_dataset needs image directories: it cannot be combined with --webdataset, --iterable_dataset or --synthetic_data")
     if args.use_8bit_adam:
@@ -156,7 +159,8 @@ def setup(args, dev, world=1, rank=0):
         print("Setting learning rate to {:.2e} = {} (accumulate_grad_batches) * {} (num_gpus) * {} (batchsize) * {:.2e} (base_lr)".format(
             lr, args.gradient_accumulation_steps, world, args.train_batch_size, args.learning_rate))
     tr = E4TTrainer(unet, enc, text, vae, lr=lr, domain_embed_scale=args.domain_embed_scale, reg_lambda=args.reg_lambda,
-                    prediction_type=args.prediction_type, class_token_id=class_token_id, empty_prompt_ids=empty_ids.to(dev), device=dev)
+                    prediction_type=args.prediction_type, class_token_id=class_token_id, empty_prompt_ids=empty_ids.to(dev), device=dev,
+                    ema_decay=args.ema_decay if getattr(args, "use_ema", False) else None)
     tr.prepare(args.train_batch_size)        # graph captures happen here, before any loader thread exists
     rng = random.Random((args.seed or 0) + (rank if args.per_rank_seed else 0)) if args.seed is not None else random.Random()
 
@@ -177,6 +181,7 @@ def main():
     if world > 1 and not dist.is_initialized():
         dist.init_process_group("nccl", device_id=dev)          # RCCL over xGMI
     from e4t.optimization import LRSchedule
+    from e4t import cli_common as cc
     from e4t.utils import save_config, save_e4t_encoder, save_e4t_unet
     st = setup(args, dev, world, rank)
     unet, enc, text, vae, tr, lr = st["unet"], st["enc"], st["text"], st["vae"], st["trainer"], st["lr"]
@@ -226,6 +231,17 @@ def main():
             first_step = tr.step_count * ga + 1
             sched.step_count = tr.step_count * world
 
+    def averaged(what):
+        """--use_ema: the context in which the weights are their average (E4TTrainer.ema_weights), else — or where the trainer cannot open it,
+        between the micro-batches of an accumulating step — None"""
+        if not args.use_ema:
+            return None
+        why = tr.ema_view_blocked()
+        if why:
+            print(f"[e4t] {what} from the raw weights: {why}")
+            return None
+        return tr.ema_weights()
+
     def save(step, state=False):
         if rank != 0:
             return
@@ -233,6 +249,11 @@ def main():
         save_config(vars(args), d)
         save_e4t_unet(unet, d)
         save_e4t_encoder(enc, d)
+        ctx = averaged(f"step {step}: no *_ema files")
+        if ctx is not None:         # the raw files above stay the reference's contract and what a resume reads
+            with ctx:
+                save_e4t_unet(unet, d, cc.EMA_FILES["weight_offsets.pt"])
+                save_e4t_encoder(enc, d, cc.EMA_FILES["encoder.pt"])
         if state:       # accelerator.save_state (:660-662): parameters + Adam moments + step, enough to resume bit for bit
             cd = os.path.join(args.output_dir, f"checkpoint-{step}")
             os.makedirs(cd, exist_ok=True)
@@ -272,8 +293,9 @@ def main():
         pipe = StableDiffusionE4TPipeline(vae=pipe_parts["dec"], text_encoder=text, tokenizer=pipe_parts["tok"], unet=unet, e4t_encoder=enc,
                                           scheduler=pipe_parts["sched"], e4t_config=args, already_added_placeholder_token=True)
         prompts = args.save_sample_prompt.split(",")
-        outs = [pipe(pr, guidance_scale=args.save_guidance_scale, num_inference_steps=args.save_inference_steps, image=im,
-                     height=args.resolution, width=args.resolution).images[0] for pr in prompts for im in pils]
+        with (averaged(f"step {step}: samples") or contextlib.nullcontext()):          # --use_ema: sampled from the average
+            outs = [pipe(pr, guidance_scale=args.save_guidance_scale, num_inference_steps=args.save_inference_steps, image=im,
+                         height=args.resolution, width=args.resolution).images[0] for pr in prompts for im in pils]
         d = os.path.join(args.output_dir, "samples")
         os.makedirs(d, exist_ok=True)
         image_grid(pils, rows=1, cols=len(pils)).save(os.path.join(d, f"input-{step}.png"))
@@ -292,7 +314,10 @@ def main():
             sched.apply(tr)
         batch = pending
         pending = next(data) if global_step < args.max_train_steps else None
-        if pending is not None:
+        # (--use_ema: the averaged view of the weights does not open over a prefetch in flight; a step that saves or samples starts none)
+        views = args.use_ema and (global_step % args.checkpointing_steps == 0
+                                  or (args.log_steps and (global_step == 1 or global_step % args.log_steps == 0)))
+        if pending is not None and not views:
             tr.prefetch(pending[0])
         loss, ld, lr_ = tr.train_step(*batch[:3], sync=sync, loss_scale=1.0 / ga, loss_mask=batch[3] if len(batch) > 3 else None)
         if sync:

@@ -58,8 +58,10 @@ def parse_args():
                    help="loss mask of --train_image_path (grey image of the same size): the diffusion loss is weighted by it")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
+    cc.add_ema_args(p, training=False)
     a = p.parse_args()
     cc.check_tome_args(p, a)
+    cc.check_ema_args(p, a)
     if a.train_mask_path and not a.train_image_path:
         p.error("--train_mask_path needs --train_image_path")
     if a.use_8bit_adam:
@@ -77,6 +79,8 @@ def setup(args, dev):
     from e4t.trainer import E4TTrainer
     from e4t.utils import AttributeDict, load_config_from_pretrained
     src = args.pretrained_model_name_or_path
+    if getattr(args, "use_ema", False):
+        cc.ema_file_names(src, True)         # exits here, before anything is built, when the directory holds no averaged weights
     if src:
         pretrained_args = load_config_from_pretrained(src)                                         # :97
         base = pretrained_args.pretrained_model_name_or_path
@@ -91,7 +95,7 @@ def setup(args, dev):
     # a base named by hub id (a run directory written by the reference): its snapshot in the local cache
     base = cc.resolve_base(base, getattr(args, "revision", None) or pretrained_args.revision)
     unet, enc, text, vae = cc.build_models(dev, base, args.unet_variant, seed=args.seed or 0, freeze_clip_vision=not args.unfreeze_clip_vision,
-                                           e4t_dir=src)                                             # :99-118
+                                           e4t_dir=src, use_ema=getattr(args, "use_ema", False))    # :99-118
     tokenizer = cc.load_tokenizer(base, allow_offline_standin=args.synthetic_data or base is None,
                                   vocab_size=text.get_input_embeddings().weight.shape[0], max_len=text.config["max_len"])
     placeholder_token_id = cc.add_placeholder_token(tokenizer, text, pretrained_args.placeholder_token)   # :120-127
