@@ -734,16 +734,21 @@ namespace {
 constexpr int MMSE_MAX_BLOCKS = 1024;
 
 // one thread per pixel (b, p), all C channels: w is read once, sum(w) falls out of the same pass.  wd (pred's layout, may be null) = w * d.
+// WEIGHTED (e4t_weighted_mse_fwd): w may be null (all ones) and the pixel's weight on d is lam[b] * w (lam may be null: all ones), while
+// sum(w) — the normaliser — stays the mask's alone; wd = lam * w * d.  WEIGHTED = false is the masked loss, operation for operation.
+template <bool WEIGHTED>
 __global__ __launch_bounds__(256) void masked_mse_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ w,
-                                                                 float* __restrict__ wd, float* __restrict__ partial, int B, int C, int HW, int nhwc) {
+                                                                 const float* __restrict__ lam, float* __restrict__ wd, float* __restrict__ partial,
+                                                                 int B, int C, int HW, int nhwc) {
   __shared__ float red[32];
   const long long npix = (long long)B * HW;
   float se = 0.f, sw = 0.f;
   for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < npix; q += (long long)gridDim.x * 256) {
     const long long b = q / HW;
     const int p = (int)(q - b * HW);
-    const float wq = w[q];
+    float wq = (WEIGHTED && !w) ? 1.f : w[q];
     sw += wq;
+    if (WEIGHTED && lam) wq = lam[b] * wq;
     for (int c = 0; c < C; ++c) {
       const long long it = (b * C + c) * HW + p;
       const long long ip = nhwc ? q * C + c : it;
@@ -782,8 +787,21 @@ extern "C" int e4t_masked_mse_fwd(const float* pred, const float* target, const 
   static_assert(E4T_MASKED_MSE_STATS == 2 + 2 * MMSE_MAX_BLOCKS, "stats = {loss, den} + the two partial rows");
   E4T_REQUIRE(pred && target && w && stats && B > 0 && C > 0 && HW > 0, "masked_mse_fwd: bad arguments");
   const int nb = (int)min(cdivl((long long)B * HW, 256), (long long)MMSE_MAX_BLOCKS);
-  hipLaunchKernelGGL(masked_mse_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, wd, stats + 2, B, C, HW, pred_nhwc);
+  hipLaunchKernelGGL(masked_mse_partial_kernel<false>, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, (const float*)nullptr, wd, stats + 2, B, C,
+                     HW, pred_nhwc);
   E4T_CHECK_LAUNCH("masked_mse_partial_kernel");
+  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)(stats + 2), nb, C, stats);
+  E4T_CHECK_LAUNCH("masked_mse_final_kernel");
+  return 0;
+}
+// the same two launches with a per-image weight lam[B] and an optional mask (min-SNR weighting); the backward is
+// e4t_masked_mse_bwd on the saved lam * w * d, whose arithmetic (g * 2 / den * wd) is already the weighted gradient's
+extern "C" int e4t_weighted_mse_fwd(const float* pred, const float* target, const float* w, const float* lam, float* wd, float* stats, int B, int C,
+                                    int HW, int pred_nhwc, e4t_stream s) {
+  E4T_REQUIRE(pred && target && stats && B > 0 && C > 0 && HW > 0, "weighted_mse_fwd: bad arguments (pred, target, stats non-null; B, C, HW > 0)");
+  const int nb = (int)min(cdivl((long long)B * HW, 256), (long long)MMSE_MAX_BLOCKS);
+  hipLaunchKernelGGL(masked_mse_partial_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, lam, wd, stats + 2, B, C, HW, pred_nhwc);
+  E4T_CHECK_LAUNCH("weighted_mse_partial_kernel");
   hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)(stats + 2), nb, C, stats);
   E4T_CHECK_LAUNCH("masked_mse_final_kernel");
   return 0;
@@ -792,5 +810,75 @@ extern "C" int e4t_masked_mse_bwd(const float* wd, const float* stats, const flo
   E4T_REQUIRE(wd && stats && g && dpred && n > 0, "masked_mse_bwd: bad arguments");
   hipLaunchKernelGGL(masked_mse_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)s, wd, stats, g, dpred, n);
   E4T_CHECK_LAUNCH("masked_mse_bwd_kernel");
+  return 0;
+}
+
+// ---- the diffusion objective's inputs in one pass (trainer.py add_noise + the target lines) ----
+//   n' = noise + s * z[b][c]  (only with an offset: z null = n' is noise itself),  noisy = a*x0 + sg*n',
+//   target = n' (epsilon) | a*n' - sg*x0 (v-prediction),  lam[b] = coef[t][2],  {a, sg} = coef[t][0..1],  t = timesteps[b] clamped to the table.
+// Every product, sum and difference is rounded on its own, in the order of the torch expressions, so the outputs are those of the stock
+// elementwise ops bit for bit.  hipcc's __fmul_rn / __fadd_rn / __fsub_rn are plain `*`, `+`, `-`, which this file's -ffp-contract=fast
+// contracts into an FMA like any other (the float4 kernel came out as v_pk_fma_f32: up to 120 ulp from torch where the two products
+// cancel), and under that flag `#pragma clang fp contract(off)` is ignored.  So every product goes through mul_rn: the canonicalize
+// behind the multiply is dropped at instruction selection (a product is canonical already, it costs no instruction) but leaves the
+// combiner no multiply next to the sum or difference to fuse with.  Every sum / difference here has such products as its operands.
+// V = 4: HW % 4 == 0 and 16-byte aligned tensors, a float4 never crosses a (b, c) row; V = 1 otherwise.
+namespace {
+__device__ __forceinline__ float mul_rn(float a, float b) { return __builtin_canonicalizef(a * b); }
+__device__ __forceinline__ void diffuse_f(float x, float nz, bool offs, float off, float a, float sg, int vpred, float& ny, float& tg) {
+  const float n1 = offs ? nz + off : nz;                     // off = mul_rn(s, z)
+  ny = mul_rn(a, x) + mul_rn(sg, n1);
+  tg = vpred ? mul_rn(a, n1) - mul_rn(sg, x) : n1;
+}
+template <int V>
+__global__ __launch_bounds__(256) void diffuse_kernel(const float* __restrict__ x0, const float* __restrict__ noise, const float* __restrict__ z,
+                                                      const long long* __restrict__ timesteps, const float* __restrict__ coef, float* __restrict__ noisy,
+                                                      float* __restrict__ target, float* __restrict__ lam, int B, int C, int HW, int T, float s, int vpred) {
+  const int rowg = HW / V;                                   // groups of V elements per (b, c) row
+  const long long ng = (long long)B * C * rowg;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < ng; i += (long long)gridDim.x * 256) {
+    const long long r = i / rowg;                            // row b * C + c
+    const int b = (int)(r / C);
+    long long t = timesteps[b];
+    t = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
+    const float a = coef[3 * t], sg = coef[3 * t + 1];
+    if (i == (long long)b * C * rowg) lam[b] = coef[3 * t + 2];
+    const bool offs = z != nullptr;
+    const float off = offs ? mul_rn(s, z[r]) : 0.f;
+    if (V == 4) {
+      const float4 X = *(const float4*)(x0 + i * 4), N = *(const float4*)(noise + i * 4);
+      float4 Y, G;
+      diffuse_f(X.x, N.x, offs, off, a, sg, vpred, Y.x, G.x);
+      diffuse_f(X.y, N.y, offs, off, a, sg, vpred, Y.y, G.y);
+      diffuse_f(X.z, N.z, offs, off, a, sg, vpred, Y.z, G.z);
+      diffuse_f(X.w, N.w, offs, off, a, sg, vpred, Y.w, G.w);
+      *(float4*)(noisy + i * 4) = Y;
+      *(float4*)(target + i * 4) = G;
+    } else {
+      float y, g;
+      diffuse_f(x0[i], noise[i], offs, off, a, sg, vpred, y, g);
+      noisy[i] = y;
+      target[i] = g;
+    }
+  }
+}
+}  // namespace
+
+extern "C" int e4t_diffuse(const float* x0, const float* noise, const float* z, const long long* timesteps, const float* coef, float* noisy, float* target,
+                           float* lam, int B, int C, int HW, int T, float s, int v_prediction, e4t_stream st) {
+  E4T_REQUIRE(x0 && noise && timesteps && coef && noisy && target && lam, "diffuse: null pointer (only z may be null)");
+  E4T_REQUIRE(B > 0 && C > 0 && HW > 0 && T > 0, "diffuse: B = %d, C = %d, HW = %d, T = %d must be positive", B, C, HW, T);
+  E4T_REQUIRE(z || s == 0.f, "diffuse: a noise offset s = %g needs z", (double)s);
+  E4T_REQUIRE(s >= 0.f, "diffuse: the noise offset s = %g must be >= 0", (double)s);
+  if (s == 0.f) z = nullptr;                                 // no offset term at all: n' is noise itself, not noise + 0 * z
+  const long long n = (long long)B * C * HW;
+  const bool vec = HW % 4 == 0 && (((uintptr_t)x0 | (uintptr_t)noise | (uintptr_t)noisy | (uintptr_t)target) & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(diffuse_kernel<4>, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)st, x0, noise, z, timesteps, coef, noisy, target, lam, B, C, HW,
+                       T, s, v_prediction);
+  else
+    hipLaunchKernelGGL(diffuse_kernel<1>, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)st, x0, noise, z, timesteps, coef, noisy, target, lam, B, C, HW, T, s,
+                       v_prediction);
+  E4T_CHECK_LAUNCH("diffuse_kernel");
   return 0;
 }

@@ -110,6 +110,8 @@ SIGNATURES = {
     "e4t_mask_prep": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "e4t_masked_mse_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "e4t_masked_mse_bwd": (i32, [vp, vp, vp, vp, i64, vp]),
+    "e4t_weighted_mse_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "e4t_diffuse": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "e4t_softmax_rows": (i32, [vp, i64, i32, i32, vp]),
     "e4t_im2col3_rgb": (i32, [vp, vp, i32, i32, i32, vp]),
     "e4t_im2col_T": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),

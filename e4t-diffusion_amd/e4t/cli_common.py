@@ -271,6 +271,24 @@ def apply_tome_args(unet, args):
     return tome.apply_tome(unet, args.tome_ratio, use_rand=not args.tome_no_rand, generator=g)
 
 
+# ---- the diffusion objective's options (E4TTrainer(snr_gamma=..., noise_offset=...)): properties of the run, so config.json
+# records them like reg_lambda; tuning_e4t.py takes its own flags and inherits neither from the pre-trained run's config.json ----
+def add_objective_args(p):
+    p.add_argument("--snr_gamma", type=float, default=None,
+                   help="min-SNR-gamma loss weighting: each image's loss is weighted by min(SNR(t), gamma) / SNR(t) (the usual choice is 5); "
+                        "must be > 0, default off")
+    p.add_argument("--noise_offset", type=float, default=0.0,
+                   help="noise offset: a per-(image, channel) N(0, 1) constant times this scale is added to the noise (0.05 - 0.1 is usual); "
+                        "must be >= 0, default 0 = off")
+
+
+def check_objective_args(p, args):
+    if args.snr_gamma is not None and not args.snr_gamma > 0.0:
+        p.error("--snr_gamma must be > 0")
+    if not args.noise_offset >= 0.0:
+        p.error("--noise_offset must be >= 0")
+
+
 # ---- EMA of the trained weights (E4TTrainer(ema_decay=...)): like ToMe a choice of the command line, config.json does not record it --------------
 EMA_ARGS = ("use_ema", "ema_decay")              # utils.save_config leaves them out of config.json
 EMA_DEFAULT_DECAY = 0.9999

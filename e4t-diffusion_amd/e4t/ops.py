@@ -665,6 +665,46 @@ class HipBackend:
         _C.check(self.lib.e4t_masked_mse_bwd(_ptr(wd), _ptr(stats), _ptr(g), _ptr(dpred), wd.numel(), _stream()), "e4t_masked_mse_bwd")
         return dpred
 
+    def weighted_mse(self, pred, target, lam=None, w=None, save=True):
+        """sum lam[b] w (pred - target)^2 / (C max(sum w, 1)) -> (loss (0-dim), wd, stats): masked_mse with a per-image weight lam [B]
+        (None = ones) and an optional mask w [B, h, w] (None = ones); wd = lam * w * (pred - target) in pred's layout."""
+        B, Cn = pred.shape[0], pred.shape[1]
+        HW = pred.numel() // (B * Cn)
+        assert pred.dtype == f32 and target.dtype == f32 and pred.dim() == 4 and target.shape == pred.shape
+        assert w is None or (w.dtype == f32 and w.numel() == B * HW)
+        assert lam is None or (lam.dtype == f32 and lam.numel() == B)
+        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
+        if not nhwc:
+            pred = pred.contiguous()
+        target = target.contiguous()
+        w = None if w is None else w.contiguous()
+        lam = None if lam is None else lam.contiguous()
+        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
+        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
+        _C.check(self.lib.e4t_weighted_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(lam), _ptr(wd), _ptr(stats), B, Cn, HW, int(nhwc), _stream()),
+                 "e4t_weighted_mse_fwd")
+        return stats[0], wd, stats
+
+    def weighted_mse_bwd(self, wd, stats, g):
+        """dpred = g * 2 * wd / den for weighted_mse's wd = lam * w * d: masked_mse_bwd's arithmetic, and its entry point"""
+        return self.masked_mse_bwd(wd, stats, g)
+
+    def diffuse(self, x0, noise, timesteps, coef, z=None, offset=0.0, v_prediction=False):
+        """(noisy, target, lam) of functional.diffusion_objective in one launch: x0, noise fp32 [B, C, h, w]; timesteps int64 [B] and
+        coef fp32 [T, 3] on the device (nothing is read on the host); z fp32 [B, C] with offset > 0"""
+        B, Cn = x0.shape[0], x0.shape[1]
+        HW = x0.numel() // (B * Cn)
+        assert x0.dtype == f32 and noise.dtype == f32 and x0.dim() == 4 and noise.shape == x0.shape
+        assert timesteps.dtype == torch.int64 and timesteps.numel() == B and coef.dtype == f32 and coef.dim() == 2 and coef.shape[1] == 3
+        assert z is None or (z.dtype == f32 and z.numel() == B * Cn)
+        x0, noise, timesteps, coef = x0.contiguous(), noise.contiguous(), timesteps.contiguous(), coef.contiguous()
+        z = None if z is None else z.contiguous()
+        noisy, target = torch.empty_like(x0), torch.empty_like(x0)
+        lam = torch.empty(B, dtype=f32, device=x0.device)
+        _C.check(self.lib.e4t_diffuse(_ptr(x0), _ptr(noise), _ptr(z), _ptr(timesteps), _ptr(coef), _ptr(noisy), _ptr(target), _ptr(lam), B, Cn, HW,
+                                      coef.shape[0], float(offset), int(bool(v_prediction)), _stream()), "e4t_diffuse")
+        return noisy, target, lam
+
     def adamw(self, p, g, m, v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0):
         self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_adamw(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), lr, beta1, beta2, eps, wd, step,
                                                                       grad_scale, _stream()), "e4t_adamw"), 28.0 * p.numel())

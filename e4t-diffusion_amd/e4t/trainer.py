@@ -38,6 +38,21 @@ def ddpm_alphas_cumprod(n=1000, beta_start=0.00085, beta_end=0.012, device=None)
     return torch.cumprod(1.0 - betas, dim=0)
 
 
+def objective_coef(acp, snr_gamma=None, v_prediction=False, check=True):
+    """The per-timestep table of the diffusion objective: fp32 [T, 3] on acp's device =
+    {acp.sqrt(), (1 - acp).sqrt(), lambda}.  The first two columns are add_noise's own expressions over the whole table, so a gathered
+    row holds the bits of acp[t].sqrt().  lambda, the min-SNR-gamma loss weight, is evaluated in float64 from the fp32 table and rounded
+    once: 1 without snr_gamma; min(snr, gamma) / snr for epsilon prediction, min(snr, gamma) / (snr + 1) for v-prediction, snr = acp / (1 - acp)."""
+    if check:
+        assert bool(((acp > 0) & (acp < 1)).all()), "the objective's options need 0 < alphas_cumprod < 1 (no zero-terminal-SNR schedule)"
+    lam = torch.ones_like(acp, dtype=torch.float64)
+    if snr_gamma is not None:
+        a64 = acp.double()
+        snr = a64 / (1.0 - a64)
+        lam = torch.clamp(snr, max=float(snr_gamma)) / ((snr + 1.0) if v_prediction else snr)
+    return torch.stack([acp.sqrt(), (1 - acp).sqrt(), lam.to(f32)], dim=1).contiguous()
+
+
 def select_trainable(unet, encoder, tuning=False, text_encoder=None):
     """pre-training (pretrain_e4t.py:274-278): encoder params with requires_grad + UNet params whose name contains "wo";
     every other UNet parameter is frozen (the reference never reads their grads).
@@ -106,7 +121,8 @@ class E4TTrainer:
     def __init__(self, unet, e4t_encoder, text_encoder, vae, *, lr=1e-6, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2,
                  domain_embed_scale=0.1, reg_lambda=0.01, prediction_type="epsilon", class_token_id=0,
                  empty_prompt_ids: Optional[torch.Tensor] = None, process_group=None, device=None, tuning=False,
-                 max_grad_norm: Optional[float] = None, head_factor_exchange=True, collectives="torch", ema_decay: Optional[float] = None):
+                 max_grad_norm: Optional[float] = None, head_factor_exchange=True, collectives="torch", ema_decay: Optional[float] = None,
+                 snr_gamma: Optional[float] = None, noise_offset: float = 0.0):
         self.unet, self.encoder, self.text_encoder, self.vae = unet, e4t_encoder, text_encoder, vae
         # data parallel: all-gather the two small factors of the 129-slot head's weight gradient instead of all-reducing the 845 MB
         # stack (_exchange_head_factors); needs the same per-rank batch size on every rank.  False = the stack rides the all-reduce.
@@ -156,6 +172,16 @@ class E4TTrainer:
         self.ema = None
         self._ema_swapped = False            # inside ema_weights(): flat.data holds the average, no training step may run
         self.acp = ddpm_alphas_cumprod(device=self.device)
+        # The objective's options, both off by default: min-SNR-gamma loss weighting and the noise offset.  With either on,
+        # noisy / target / the per-image weight come from Fn.diffusion_objective over `coef`; with neither, the step is the plain one.
+        if snr_gamma is not None and not float(snr_gamma) > 0.0:
+            raise ValueError(f"snr_gamma={snr_gamma!r}: a float > 0, or None for no min-SNR weighting")
+        if not float(noise_offset) >= 0.0:
+            raise ValueError(f"noise_offset={noise_offset!r}: a float >= 0")
+        self.snr_gamma = None if snr_gamma is None else float(snr_gamma)
+        self.noise_offset = float(noise_offset)
+        self._objective_on = self.snr_gamma is not None or self.noise_offset > 0
+        self.coef = objective_coef(self.acp, self.snr_gamma, prediction_type != "epsilon", check=self._objective_on)
         self.max_grad_norm = max_grad_norm
         self.tuning = tuning
         self._armed = False
@@ -284,18 +310,27 @@ class E4TTrainer:
         s = (1 - self.acp[t]).sqrt().view(-1, 1, 1, 1)
         return a * x0 + s * noise
 
-    def losses(self, pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask=None):
+    def losses(self, pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask=None, offset_eps=None):
         """Forward half of the step (pretrain_e4t.py:616-647).  Returns (loss, loss_diff, loss_reg).
         loss_mask (fp32 [B, h, w] on the latent grid, from DeviceLoader's ``loss_mask``): loss_diff becomes the masked mean-squared
         error of functional.masked_mse (the reference's README.md:112-115).  Under data parallelism each rank normalises by the
-        sum(w) of ITS batch before the gradients are averaged, as each rank's plain mean is taken over its own batch."""
+        sum(w) of ITS batch before the gradients are averaged, as each rank's plain mean is taken over its own batch.
+        offset_eps ([B, C], with noise_offset > 0): the noise offset's draw; drawn here when it is not given.  With snr_gamma or
+        noise_offset set, noisy / target / the per-image loss weight come from functional.diffusion_objective."""
         B = latents.shape[0]
         te = self.text_encoder
         if self.text_trainable:
             self._refresh_text_constants()
         with torch.set_grad_enabled(self.text_trainable and torch.is_grad_enabled()):     # the embedding table trains with the text encoder
             inputs_embeds = te.get_input_embeddings()(input_ids)
-        noisy = self.add_noise(latents, noise, timesteps)
+        lam = None
+        if self._objective_on:
+            if self.noise_offset > 0 and offset_eps is None:
+                offset_eps = torch.randn((B, latents.shape[1]), device=latents.device)
+            noisy, target, lam = Fn.diffusion_objective(latents, noise, timesteps, self.coef, z=offset_eps if self.noise_offset > 0 else None,
+                                                        offset=self.noise_offset, v_prediction=self.pred_type != "epsilon")
+        else:
+            noisy = self.add_noise(latents, noise, timesteps)
         # both UNet passes see the same (noisy, timesteps): the context-independent prefix is computed once (SURVEY §8a (3))
         share = self.unet.shared_prefix() if (self.share_prefix and hasattr(self.unet, "shared_prefix")) else contextlib.nullcontext()
         # The frozen CLIP-ViT only needs the image: run it on a side stream under the UNet encoder pass, whose low-resolution
@@ -323,13 +358,17 @@ class E4TTrainer:
             emb[torch.arange(B, device=emb.device), placeholder_idx] = domain.to(emb.dtype)
             ctx = te(inputs_embeds=emb)[0]
             pred = self.unet(noisy, timesteps, ctx).sample
-        if self.pred_type == "epsilon":
+        if self._objective_on:                   # (target came with noisy)
+            pass
+        elif self.pred_type == "epsilon":
             target = noise
         else:
             a = self.acp[timesteps].sqrt().view(-1, 1, 1, 1)
             s = (1 - self.acp[timesteps]).sqrt().view(-1, 1, 1, 1)
             target = a * noise - s * latents
-        if loss_mask is not None:
+        if self.snr_gamma is not None:
+            loss_diff = Fn.weighted_mse(pred.float(), target.float(), lam, loss_mask)
+        elif loss_mask is not None:
             loss_diff = Fn.masked_mse(pred.float(), target.float(), loss_mask)
         else:
             loss_diff = F.mse_loss(pred.float(), target.float(), reduction="mean")
@@ -748,9 +787,11 @@ class E4TTrainer:
         ev = slot[1] = torch.cuda.Event()
         ev.record()
 
-    def _graphed_step(self, pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents):
+    def _graphed_step(self, pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, offset_eps=None):
         ins = dict(pixel_values=pixel_values, input_ids=input_ids, placeholder_idx=placeholder_idx, noise=noise, timesteps=timesteps,
                    vae_eps=vae_eps, latents=latents)
+        if offset_eps is not None:               # the noise offset's draw, when handed in: one more static input, part of the signature
+            ins["offset_eps"] = offset_eps
         sig = tuple((k, tuple(v.shape), v.dtype) for k, v in ins.items() if v is not None)
         ent = self._step_graphs.get(sig)
         if ent is None:
@@ -889,15 +930,16 @@ class E4TTrainer:
         ops.bump_weights_epoch()                 # bf16 compute copies of the trainable weights are stale now
 
     def train_step(self, pixel_values, input_ids, placeholder_idx, noise=None, timesteps=None, vae_eps=None, latents=None,
-                   sync=True, loss_scale=1.0, loss_mask=None):
+                   sync=True, loss_scale=1.0, loss_mask=None, offset_eps=None):
         """One training step (see _train_step); replayed from the step's HIP graph when enable_step_graph() is on and the call is a plain
-        synchronising step without a loss mask (a masked step always runs eagerly)."""
+        synchronising step without a loss mask (a masked step always runs eagerly).  The objective's options (snr_gamma, noise_offset)
+        do not change that: their per-image weights are gathered on the device from the step's timesteps."""
         def run():
             # (a replayed graph bakes in the first-write / factored treatment of the head's gradient stack: only from a clean gradient)
             if (self._step_graph_on and sync and loss_scale == 1.0 and self._next_px is None and not self._pref and not self._accum_pending
                     and loss_mask is None):
-                return self._graphed_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents)
-            return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale, loss_mask)
+                return self._graphed_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, offset_eps)
+            return self._train_step(pixel_values, input_ids, placeholder_idx, noise, timesteps, vae_eps, latents, sync, loss_scale, loss_mask, offset_eps)
         if self._ema_swapped:
             raise RuntimeError("train_step inside ema_weights(): the flat buffer holds the average, not the trained weights")
         tome.new_step(self.unet)       # token merging (opt-in): this step's draw, outside any capture; nothing for an unmarked UNet
@@ -968,8 +1010,9 @@ class E4TTrainer:
         return self._train_stream
 
     def _train_step(self, pixel_values, input_ids, placeholder_idx, noise=None, timesteps=None, vae_eps=None, latents=None,
-                    sync=True, loss_scale=1.0, loss_mask=None):
-        """Full step.  Random draws may be passed in (parity tests) or are sampled on the device.
+                    sync=True, loss_scale=1.0, loss_mask=None, offset_eps=None):
+        """Full step.  Random draws may be passed in (parity tests) or are sampled on the device, in the order vae_eps, noise, the noise
+        offset's [B, C] draw (only with noise_offset > 0), timesteps.
         Gradient accumulation (``accelerator.accumulate``, pretrain_e4t.py:595): call with ``sync=False`` and
         ``loss_scale=1/k`` for the first k-1 micro-batches — gradients accumulate locally, no collective, no optimiser step —
         and with ``sync=True`` (same loss_scale) for the k-th."""
@@ -987,9 +1030,11 @@ class E4TTrainer:
             latents = self.encode_latents(pixel_values, vae_eps)
         if noise is None:
             noise = torch.randn_like(latents)
+        if self.noise_offset > 0 and offset_eps is None:
+            offset_eps = torch.randn((B, latents.shape[1]), device=dev)
         if timesteps is None:
             timesteps = torch.randint(0, self.acp.shape[0], (B,), device=dev).long()
-        loss, loss_diff, loss_reg = self.losses(pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask)
+        loss, loss_diff, loss_reg = self.losses(pixel_values, latents, noise, timesteps, input_ids, placeholder_idx, loss_mask, offset_eps)
         if self._next_px is not None:        # announced by prefetch(): the next batch's frozen encoders start with this backward
             self._start_prefetch()           # (starting them with the step instead: 101.95 vs 101.8 ms, profiles/r05_ab/r05b_at_step.json)
         self._armed = bool(sync)             # micro-batches that only accumulate start no collectives

@@ -81,9 +81,11 @@ def parse_args():
     from e4t import cli_common as cc
     cc.add_tome_args(p)
     cc.add_ema_args(p)
+    cc.add_objective_args(p)
     args = p.parse_args()
     cc.check_tome_args(p, args)
     cc.check_ema_args(p, args)
+    cc.check_objective_args(p, args)
     if args.train_mask_dataset and (args.webdataset or args.iterable_dataset or args.synthetic_data):
         p.error("--train_mask_dataset needs image directories: it cannot be combined with --webdataset, --iterable_dataset or --synthetic_data")
     if args.use_8bit_adam:
@@ -160,7 +162,8 @@ def setup(args, dev, world=1, rank=0):
             lr, args.gradient_accumulation_steps, world, args.train_batch_size, args.learning_rate))
     tr = E4TTrainer(unet, enc, text, vae, lr=lr, domain_embed_scale=args.domain_embed_scale, reg_lambda=args.reg_lambda,
                     prediction_type=args.prediction_type, class_token_id=class_token_id, empty_prompt_ids=empty_ids.to(dev), device=dev,
-                    ema_decay=args.ema_decay if getattr(args, "use_ema", False) else None)
+                    ema_decay=args.ema_decay if getattr(args, "use_ema", False) else None,
+                    snr_gamma=getattr(args, "snr_gamma", None), noise_offset=getattr(args, "noise_offset", 0.0))
     tr.prepare(args.train_batch_size)        # graph captures happen here, before any loader thread exists
     rng = random.Random((args.seed or 0) + (rank if args.per_rank_seed else 0)) if args.seed is not None else random.Random()
 

@@ -59,9 +59,11 @@ def parse_args():
     from e4t import cli_common as cc
     cc.add_tome_args(p)
     cc.add_ema_args(p, training=False)
+    cc.add_objective_args(p)
     a = p.parse_args()
     cc.check_tome_args(p, a)
     cc.check_ema_args(p, a)
+    cc.check_objective_args(p, a)
     if a.train_mask_path and not a.train_image_path:
         p.error("--train_mask_path needs --train_image_path")
     if a.use_8bit_adam:
@@ -111,7 +113,8 @@ def setup(args, dev):
     lr = args.learning_rate * (args.train_batch_size * ga if args.scale_lr else 1)                  # :149-156 (one process)
     tr = E4TTrainer(unet, enc, text, vae, lr=lr, domain_embed_scale=args.domain_embed_scale, reg_lambda=args.reg_lambda,
                     prediction_type=getattr(pretrained_args, "prediction_type", None) or "epsilon", class_token_id=class_token_id,
-                    empty_prompt_ids=empty_ids.to(dev), device=dev, tuning=True, max_grad_norm=args.max_grad_norm)
+                    empty_prompt_ids=empty_ids.to(dev), device=dev, tuning=True, max_grad_norm=args.max_grad_norm,
+                    snr_gamma=getattr(args, "snr_gamma", None), noise_offset=getattr(args, "noise_offset", 0.0))    # its own flags, not the pre-trained run's
     tr.prepare(args.train_batch_size)
     print(f"Number of Trainable Parameters: {tr.flat.numel * 1.e-6:.2f} M")
     import random
