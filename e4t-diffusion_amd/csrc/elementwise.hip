@@ -373,9 +373,15 @@ extern "C" int e4t_guided_step(const float* pred, const float* sample, const flo
 // and x_in, so reading the old values before writing the new ones needs no synchronisation and x may alias out.
 // Terms whose coefficient is 0 are skipped (uniform branch on a row value), which keeps a DDIM row's arithmetic exactly
 // guided_step_kernel's: same expressions in the same order, so the same contraction.
+// BLEND (e4t_sampler_step_edit): the finished o is mixed with the original latent re-noised to the level of the row's output,
+// y = a_keep*x0 + s_keep*n0 with (a_keep, s_keep) = row[14], row[15], weighted by keep; both entry points are instances of
+// this one body, and everything up to the mix is the same code, so the plain entry point's arithmetic cannot drift.
+template <bool BLEND>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restrict__ pred, const float* x, float* out, float* hist, float* saved,
                                                            const float* __restrict__ noise, float* x_in, const float* __restrict__ row,
-                                                           int B, int C, int HW, int K, int cfg, int nhwc, int x_in_copies) {
+                                                           const float* __restrict__ keep, const float* __restrict__ x0, const float* __restrict__ n0,
+                                                           int B, int C, int HW, int K, int cfg, int nhwc, int x_in_copies,
+                                                           int keep_per_image, int x0_per_image) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long n = (long long)B * C * HW;
   if (i >= n) return;
@@ -403,6 +409,12 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
   if (noise && c_n != 0.f) o += c_n * noise[i];
   if (w >= 0 && w < K) hist[w * n + i] = m;
   if (save_x && saved) saved[i] = xv;
+  if constexpr (BLEND) {
+    const long long chw = (long long)C * HW;
+    const float kp = keep[(keep_per_image ? (i / chw) * HW : 0) + i % HW];
+    const float y = __fmaf_rn(row[15], n0[i], row[14] * x0[x0_per_image ? i : i % chw]);
+    o = __fmaf_rn(kp, y, (1.f - kp) * o);
+  }
   out[i] = o;
   if (x_in_copies > 0) {
     const float v = k_in * o;
@@ -416,9 +428,24 @@ extern "C" int e4t_sampler_step(const float* pred, const float* x, float* out, f
   E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
   E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 2 && (x_in_copies == 0 || x_in), "sampler_step: x_in_copies = %d (0..2, x_in required when > 0)", x_in_copies);
   const long long n = (long long)B * C * HW;
-  hipLaunchKernelGGL(sampler_step_kernel, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
-                     B, C, HW, K, cfg, pred_nhwc, x_in_copies);
+  hipLaunchKernelGGL(sampler_step_kernel<false>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
+                     nullptr, nullptr, nullptr, B, C, HW, K, cfg, pred_nhwc, x_in_copies, 0, 0);
   E4T_CHECK_LAUNCH("sampler_step_kernel");
+  return 0;
+}
+extern "C" int e4t_sampler_step_edit(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
+                                     const float* row, const float* keep, const float* x0, const float* n0, int B, int C, int HW, int K, int cfg,
+                                     int pred_nhwc, int x_in_copies, int keep_per_image, int x0_per_image, e4t_stream s) {
+  E4T_REQUIRE(pred && x && out && row && B > 0 && C > 0 && HW > 0, "sampler_step_edit: bad arguments");
+  E4T_REQUIRE(keep && x0 && n0, "sampler_step_edit: keep, x0 and n0 are required");
+  E4T_REQUIRE((keep_per_image == 0 || keep_per_image == 1) && (x0_per_image == 0 || x0_per_image == 1),
+              "sampler_step_edit: keep_per_image = %d, x0_per_image = %d (0 or 1)", keep_per_image, x0_per_image);
+  E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step_edit: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
+  E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 2 && (x_in_copies == 0 || x_in), "sampler_step_edit: x_in_copies = %d (0..2, x_in required when > 0)", x_in_copies);
+  const long long n = (long long)B * C * HW;
+  hipLaunchKernelGGL(sampler_step_kernel<true>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
+                     keep, x0, n0, B, C, HW, K, cfg, pred_nhwc, x_in_copies, keep_per_image, x0_per_image);
+  E4T_CHECK_LAUNCH("sampler_step_edit_kernel");
   return 0;
 }
 extern "C" int e4t_transpose(const void* in, void* out, int batch, int R, int C, int ldi, int ldo, long long bsi, long long bso, e4t_stream s) {

@@ -106,6 +106,7 @@ SIGNATURES = {
     "e4t_clip_preprocess": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "e4t_guided_step": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "e4t_sampler_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "e4t_sampler_step_edit": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
     "e4t_image_prep": (i32, [vp, vp, vp, i32, i32, vp]),
     "e4t_mask_prep": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "e4t_masked_mse_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),

@@ -597,10 +597,10 @@ class HipBackend:
                  "e4t_guided_step")
         return out
 
-    def sampler_step(self, pred, x, row, hist=None, saved=None, noise=None, x_in=None, cfg=True, pred_nhwc=False, out=None):
+    def sampler_step(self, pred, x, row, hist=None, saved=None, noise=None, x_in=None, cfg=True, pred_nhwc=False, out=None, edit=None):
         """guidance + one linear sampler update (the row contract of e4t_sampler_step in include/e4t_hip.h); row = device fp32
         [16]; hist = [K, *x.shape] (K <= 4); x_in = [x.shape[0] or 2*x.shape[0], ...] receives k_in*out once or twice.
-        Returns out (x may be passed as out: in place)."""
+        Returns out (x may be passed as out: in place).  edit = (keep, x0, n0): sampler_step_edit's operands."""
         B, Cn = x.shape[0], x.shape[1]
         HW = x.numel() // (B * Cn)
         assert pred.dtype == f32 and x.dtype == f32 and row.dtype == f32 and row.numel() == _C.SAMPLER_ROW and row.is_contiguous()
@@ -618,9 +618,25 @@ class HipBackend:
         if out is None:
             out = torch.empty_like(x)
         assert out.dtype == f32 and out.is_contiguous() and out.shape == x.shape
+        if edit is not None:
+            keep, x0, n0 = edit
+            for t in edit:
+                assert t.dtype == f32 and t.is_contiguous() and t.device == x.device
+            assert keep.numel() in (HW, B * HW) and x0.numel() in (Cn * HW, B * Cn * HW) and n0.shape == x.shape
+            _C.check(self.lib.e4t_sampler_step_edit(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
+                                                    _ptr(keep), _ptr(x0), _ptr(n0), B, Cn, HW, K, int(cfg), int(pred_nhwc), copies,
+                                                    int(B > 1 and keep.numel() == B * HW), int(B > 1 and x0.numel() == B * Cn * HW), _stream()),
+                     "e4t_sampler_step_edit")
+            return out
         _C.check(self.lib.e4t_sampler_step(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
                                            B, Cn, HW, K, int(cfg), int(pred_nhwc), copies, _stream()), "e4t_sampler_step")
         return out
+
+    def sampler_step_edit(self, pred, x, row, keep, x0, n0, **kw):
+        """sampler_step with the masked blend of e4t_sampler_step_edit (include/e4t_hip.h): out = keep*(a_keep*x0 + s_keep*n0) +
+        (1 - keep)*out with (a_keep, s_keep) = row[14:16]; keep = fp32 [HW] (shared) or [B, HW], x0 = fp32 [C, HW] (shared) or
+        [B, C, HW], n0 = fp32 of x's shape; trailing dimensions may be split as (H, W)."""
+        return self.sampler_step(pred, x, row, edit=(keep, x0, n0), **kw)
 
     def image_prep(self, pool, table, B, S, out=None):
         """raw uint8 RGB images packed in `pool` + int64 [B,8] plan `table` (both on the device) -> fp32 [B,3,S,S]"""

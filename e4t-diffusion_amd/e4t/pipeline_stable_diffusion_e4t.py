@@ -22,6 +22,12 @@ the MI355X:
     step is GPU-bound); ``use_graph=False`` -> eager.  Without ``e4t_sampler_step`` (the CPU op emulation) only DDIM with
     eta == 0 is fused, through ``e4t_guided_step``; every other case takes the generic ``scale_model_input`` / ``step`` path.
 
+Editing (not in the reference): ``init_image=`` starts from a photograph re-noised to ``strength`` of the schedule
+(``scheduler.set_timesteps(n, begin=k)``), ``mask_image=`` additionally holds everything outside the mask to the photograph at
+every step.  The definition is the generic loop (``step`` + the torch blend below); on the fused path the blend is part of the
+step kernel (``e4t_sampler_step_edit``, rows of ``fused_plan(blend=True)``), so an edited step is still one UNet pass + one
+update launch inside the replayed graph.  The CPU op emulation takes the generic loop.
+
 The tokenizer is whatever object the caller passes (``transformers.CLIPTokenizer`` in inference.py): it needs
 ``__call__(text, padding=, truncation=, max_length=, return_tensors="pt", add_special_tokens=)``, ``add_tokens``,
 ``convert_tokens_to_ids``, ``model_max_length`` and ``__len__``.  The safety checker is not built (the reference runs the
@@ -60,10 +66,11 @@ def preprocess(image):
 
 class StableDiffusionE4TPipeline:
     def __init__(self, vae, text_encoder, tokenizer, unet, e4t_encoder, scheduler, safety_checker=None, feature_extractor=None,
-                 e4t_config=None, requires_safety_checker: bool = True, already_added_placeholder_token: bool = False):
+                 e4t_config=None, requires_safety_checker: bool = True, already_added_placeholder_token: bool = False, vae_encoder=None):
         if safety_checker is not None:
             raise NotImplementedError("the safety checker is not part of this build: pass safety_checker=None")
         self.vae, self.text_encoder, self.tokenizer, self.unet, self.scheduler = vae, text_encoder, tokenizer, unet, scheduler
+        self.vae_encoder = vae_encoder       # e4t.vae.VAEEncoder: only editing (init_image=) needs it
         self.e4t_encoder = e4t_encoder
         self.safety_checker, self.feature_extractor = None, feature_extractor
         boc = getattr(vae, "block_out_channels", None) or getattr(getattr(vae, "config", None), "block_out_channels", (0,) * 4)
@@ -93,8 +100,9 @@ class StableDiffusionE4TPipeline:
     _execution_device = device
 
     def to(self, device):
-        for m in (self.vae, self.text_encoder, self.unet, self.e4t_encoder):
-            m.to(device)
+        for m in (self.vae, self.text_encoder, self.unet, self.e4t_encoder, self.vae_encoder):
+            if m is not None:
+                m.to(device)
         self.class_embed = self.class_embed.to(device)
         self._graph = None
         return self
@@ -133,6 +141,11 @@ class StableDiffusionE4TPipeline:
         shape = (batch_size, num_channels_latents, height // self.vae_scale_factor, width // self.vae_scale_factor)
         if isinstance(generator, list) and len(generator) != batch_size:
             raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch size of {batch_size}.")
+        return self._unit_noise(shape, dtype, device, generator, latents) * self.scheduler.init_noise_sigma
+
+    @staticmethod
+    def _unit_noise(shape, dtype, device, generator, latents=None):
+        """the one N(0, 1) draw of the latent shape (or the caller's `latents`): the start of plain sampling, n0 of editing"""
         if latents is None:
             if isinstance(generator, list):
                 latents = torch.cat([torch.randn((1,) + shape[1:], generator=g, device=g.device, dtype=dtype).to(device) for g in generator])
@@ -141,7 +154,30 @@ class StableDiffusionE4TPipeline:
                 latents = torch.randn(shape, generator=generator, device=gdev, dtype=dtype).to(device)
         else:
             latents = latents.to(device=device, dtype=dtype)
-        return latents * self.scheduler.init_noise_sigma
+        return latents
+
+    def prepare_edit(self, init_image, strength, mask_image, num_inference_steps, batch_size, height, width, device):
+        """img2img / inpainting inputs -> (begin, x0, keep): the first kept step of the schedule, the clean latent
+        of `init_image` (posterior mean * scaling factor; one for the batch, or one per image) and the [h*w] keep map
+        (1 - the mask averaged onto the latent grid; None without a mask)."""
+        if self.vae_encoder is None:
+            raise ValueError("`init_image` needs the pipeline's `vae_encoder` (an e4t.vae.VAEEncoder)")
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"`strength` has to lie in (0, 1] but is {strength}")
+        init_steps = min(int(num_inference_steps * strength), num_inference_steps)
+        if init_steps < 1:
+            raise ValueError(f"`strength` = {strength} leaves no denoising step of {num_inference_steps}")
+        pixels = preprocess(_resized(init_image, height, width)).to(device=device, dtype=torch.float32)
+        if tuple(pixels.shape[1:]) != (3, height, width) or pixels.shape[0] not in (1, batch_size):
+            raise ValueError(f"`init_image` has to be one or {batch_size} RGB images of {height} x {width} but is {tuple(pixels.shape)}")
+        f = self.vae_scale_factor
+        eps = torch.zeros((pixels.shape[0], self.unet.in_channels, height // f, width // f), dtype=torch.float32, device=device)
+        x0 = self.vae_encoder.encode_sample(pixels, eps).float().contiguous()          # zero eps: the posterior mean, deterministic
+        keep = None
+        if mask_image is not None:
+            m = _mask_tensor(mask_image, height, width).to(device=device, dtype=torch.float32)
+            keep = (1.0 - torch.nn.functional.avg_pool2d(m[None, None], f)).reshape(-1).contiguous()
+        return num_inference_steps - init_steps, x0, keep
 
     def decode_latents(self, latents):
         return self.vae.decode_latents(latents).cpu().float().numpy()                # (B, H, W, 3) in [0, 1]
@@ -192,6 +228,8 @@ class StableDiffusionE4TPipeline:
         UNet input into bufs["x_in"]"""
         nhwc = pred.permute(0, 2, 3, 1)
         kw = dict(hist=bufs["hist"], saved=bufs["saved"], noise=bufs["noise"], x_in=bufs["x_in"], cfg=cfg, out=latents)
+        if bufs.get("edit") is not None:                 # masked editing: the blend with the re-noised original, in the same kernel
+            kw["edit"] = bufs["edit"]
         if nhwc.is_contiguous():                         # the native UNet hands out an NCHW view of NHWC storage
             ops.backend().sampler_step(nhwc, latents, row, pred_nhwc=True, **kw)
         else:
@@ -203,7 +241,10 @@ class StableDiffusionE4TPipeline:
                  num_inference_steps: int = 50, guidance_scale: float = 7.5, negative_prompt=None, num_images_per_prompt: Optional[int] = 1,
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None, negative_prompt_embeds=None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, callback: Optional[Callable] = None, callback_steps: int = 1,
-                 cross_attention_kwargs=None, image=None, domain_embed_scale: Optional[float] = None, use_graph: Optional[bool] = None):
+                 cross_attention_kwargs=None, image=None, domain_embed_scale: Optional[float] = None, use_graph: Optional[bool] = None,
+                 init_image=None, strength: float = 0.8, mask_image=None):
+        """image: the conditioning image (the subject).  init_image: the photograph to edit (img2img: re-noised to `strength` of
+        the schedule and denoised from there); mask_image: white = repaint, everything else is held to init_image at every step."""
         scale = self.domain_embed_scale if domain_embed_scale is None else domain_embed_scale
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
@@ -219,11 +260,25 @@ class StableDiffusionE4TPipeline:
         pixels = preprocess(image).to(device=device, dtype=torch.float32)
         if pixels.shape[0] != 1:
             raise ValueError("one conditioning image per call")
-        e4t = self.prepare_for_e4t(prompt, device)
-        self.scheduler.set_timesteps(num_inference_steps, device=device)
-        timesteps = self.scheduler.timesteps
         bsz = num_images_per_prompt
-        latents = self.prepare_latents(bsz, self.unet.in_channels, height, width, torch.float32, device, generator, latents).contiguous()
+        if mask_image is not None and init_image is None:
+            raise ValueError("`mask_image` needs `init_image`")
+        edit = init_image is not None
+        e4t = self.prepare_for_e4t(prompt, device)
+        if edit:
+            begin, x0, keep = self.prepare_edit(init_image, strength, mask_image, num_inference_steps, bsz, height, width, device)
+            self.scheduler.set_timesteps(num_inference_steps, device=device, begin=begin)
+        else:
+            keep = None
+            self.scheduler.set_timesteps(num_inference_steps, device=device)
+        timesteps = self.scheduler.timesteps
+        if edit:        # the start is the original at the first kept timestep's noise level; n0 is drawn where plain sampling draws
+            shape = (bsz, self.unet.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
+            n0 = self._unit_noise(shape, torch.float32, device, generator, latents).contiguous()
+            a, sg = self.scheduler.noise_level(timesteps[0])
+            latents = (a * x0 + sg * n0).contiguous()
+        else:
+            latents = self.prepare_latents(bsz, self.unet.in_channels, height, width, torch.float32, device, generator, latents).contiguous()
 
         vision = None
         if hasattr(self.e4t_encoder, "encode_vision"):                                # image features: once, not per step
@@ -234,9 +289,11 @@ class StableDiffusionE4TPipeline:
 
         sch = self.scheduler
         native = device.type == "cuda" and hasattr(ops.backend(), "sampler_step")
-        plan = sch.fused_plan(guidance_scale, eta) if self._fused_sampling and hasattr(sch, "fused_plan") else None
-        if plan is not None and not native and not (isinstance(sch, DDIMScheduler) and eta == 0.0):
-            plan = None                  # without e4t_sampler_step only DDIM with eta == 0 is fused (through e4t_guided_step)
+        plan = None
+        if self._fused_sampling and hasattr(sch, "fused_plan"):
+            plan = sch.fused_plan(guidance_scale, eta, blend=True) if keep is not None else sch.fused_plan(guidance_scale, eta)
+        if plan is not None and not native and (edit or not (isinstance(sch, DDIMScheduler) and eta == 0.0)):
+            plan = None                  # without e4t_sampler_step only plain DDIM with eta == 0 is fused (through e4t_guided_step)
         if use_graph is None:       # measured (SD-1.4, 512 px, 50 steps, DDIM): 13.6 -> 11.8 ms/step at 1 image, no gain from 4 images up
             use_graph = plan is not None and device.type == "cuda" and bsz <= 2
         if use_graph and plan is None:
@@ -258,6 +315,8 @@ class StableDiffusionE4TPipeline:
                 if cfg:
                     x_in[bsz:].copy_(x_in[:bsz])
                 state = [latents] + [bufs[k] for k in ("hist", "saved", "x_in") if bufs[k] is not None]
+                if keep is not None:     # fixed, read-only operands of e4t_sampler_step_edit: outside the captured state
+                    bufs["edit"] = (keep, x0, n0)
 
                 def one_step():
                     self._sampler_update(self._model_step(latents, t_buf, s, x_in=x_in), latents, row, bufs, cfg)
@@ -300,6 +359,9 @@ class StableDiffusionE4TPipeline:
                     u, c = pred.chunk(2)
                     pred = u + guidance_scale * (c - u)                              # :209-211
                 latents = sch.step(pred.float(), t, latents, **extra).prev_sample    # :214
+                if keep is not None:     # the definition of masked editing: hold the kept region at the next timestep's noise level
+                    a, sg = sch.noise_level(timesteps[i + 1]) if i + 1 < len(timesteps) else (1.0, 0.0)
+                    latents = keep.view(1, 1, *latents.shape[2:]) * (a * x0 + sg * n0) + (1.0 - keep.view(1, 1, *latents.shape[2:])) * latents
                 if callback is not None and i % callback_steps == 0:
                     callback(i, t, latents)
 
@@ -332,6 +394,28 @@ class StableDiffusionE4TPipeline:
         for b, k in zip(bufs, keep):      # capture does not execute: the first replay starts from the same state
             b.copy_(k)
         return graph
+
+
+def _resized(image, height, width):
+    """PIL image(s) -> resized to (width, height); tensors pass through (they must have that size already)"""
+    if isinstance(image, (list, tuple)):
+        return [_resized(i, height, width) for i in image]
+    if hasattr(image, "resize") and not isinstance(image, (torch.Tensor, np.ndarray)):
+        return image.convert("RGB").resize((width, height))
+    return image
+
+
+def _mask_tensor(mask, height, width):
+    """PIL image / array / tensor -> float32 (height, width) in [0, 1], 1 (white) = repaint; soft values stay soft"""
+    if hasattr(mask, "resize") and not isinstance(mask, (torch.Tensor, np.ndarray)):
+        return torch.from_numpy(np.asarray(mask.convert("L").resize((width, height)), dtype=np.float32) / 255.0)
+    m = torch.as_tensor(mask).float()
+    m = m.reshape(m.shape[-2:]) if m.numel() == m.shape[-2] * m.shape[-1] else m
+    if m.dim() != 2:
+        raise ValueError(f"`mask_image` has to be one single-channel map but is {tuple(m.shape)}")
+    if tuple(m.shape) != (height, width):
+        m = torch.nn.functional.interpolate(m[None, None], size=(height, width), mode="bilinear", align_corners=False)[0, 0]
+    return m.clamp(0.0, 1.0)
 
 
 class _Attr(dict):

@@ -308,7 +308,7 @@ int e4t_guided_step(const float* pred, const float* sample, const float* noise, 
  *   hist[w] = m   (0 <= w < K; w = -1: none)         saved = x when save_x    (both after all reads: out may alias x)
  *   x_in  = k_in*out, written x_in_copies (0..2) times back to back ([x_in | x_in] = the UNet's CFG batch)
  * row: DEVICE float[16] (so a captured graph replays with new values) =
- *   {g, a_e, a_x, c_x, c_s, c_m, c_n, k_in, w, save_x, c_hist[0..3], 0, 0}.
+ *   {g, a_e, a_x, c_x, c_s, c_m, c_n, k_in, w, save_x, c_hist[0..3], a_keep, s_keep}   (the last two: e4t_sampler_step_edit only).
  * x, out, saved, noise, x_in and each of the K slots of hist ([K][n]) are [B][C][HW] fp32.  saved / noise may be NULL (their
  * terms are dropped); terms whose coefficient is 0 are not read.  A DDIM row {g, 1, 0, c_sample, 0, c_pred, c_noise, ...}
  * computes exactly what e4t_guided_step computes with {g, c_sample, c_pred, c_noise}, bit for bit. */
@@ -316,6 +316,19 @@ int e4t_guided_step(const float* pred, const float* sample, const float* noise, 
 #define E4T_SAMPLER_ROW 16
 int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
                      const float* row, int B, int C, int HW, int K, int cfg, int pred_nhwc, int x_in_copies, e4t_stream stream);
+/* The same step for editing (img2img with a mask: the region to keep is held to the original at every step).  Row contract and
+ * element ownership are e4t_sampler_step's; the row's two trailing slots, which e4t_sampler_step ignores, are read here:
+ *   row[14] = a_keep, row[15] = s_keep: the noise level of the latent this row writes (the next model call's timestep; 1, 0 in
+ *   the last row).  After out = o has been formed as above, per element i (p = i % HW, b = i / (C*HW)):
+ *   y    = fma(s_keep, n0[i], a_keep * x0[x0_per_image ? i : i % (C*HW)])        the original at that noise level
+ *   k    = keep[keep_per_image ? b*HW + p : p]                                    1 = hold the original, 0 = free, soft between
+ *   out  = fma(k, y, (1 - k) * o)        x_in = k_in * out, as above
+ * hist[w] still receives the unblended m and saved the input x.  So k == 0 gives e4t_sampler_step's bits, k == 1 gives y
+ * whatever pred holds, and the last row ends at x0 exactly.  keep: fp32 [HW] or [B][HW]; x0: fp32 [C][HW] or [B][C][HW]; n0:
+ * fp32 [B][C][HW] (one fixed unit-noise draw); all three are read-only and required (NULL: -22), the two flags are 0 or 1. */
+int e4t_sampler_step_edit(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
+                          const float* row, const float* keep, const float* x0, const float* n0, int B, int C, int HW, int K, int cfg,
+                          int pred_nhwc, int x_in_copies, int keep_per_image, int x0_per_image, e4t_stream stream);
 /* Data path (pretrain_e4t.py:137-144 make_transforms = SmallestMaxSize(interpolation=3: cv2.INTER_AREA) -> RandomCrop ->
  * HorizontalFlip, and :174-177 image/127.5-1, HWC->CHW): a batch of raw decoded uint8 RGB images in one device pool ->
  * out fp32 [B][3][S][S].  table: int64 [B][8] (device) = {byte offset of the image in pool, H, W, newH, newW (the

@@ -7,7 +7,12 @@ unet.pt, encoder.pt, optionally text_encoder.pt); the base Stable Diffusion weig
 config: a local directory or a hub id whose snapshot is in the local Hugging Face cache, in the diffusers pipeline layout or as
 state dicts unet.pt / vae.pt / text_encoder.pt, with a tokenizer/ folder (e4t/cli_common.py) — there is no hub access here.  With
 --random_init everything is randomly initialised and an offline whitespace tokenizer is used (smoke runs, benchmarks).
-All six samplers of the reference are available; DDIM additionally has the fused, graph-replayed update.
+All six samplers of the reference are available, each with the fused, graph-replayed update.
+
+    python inference.py ... --init_image photo.png --strength 0.6 [--mask_image mask.png]
+
+places the subject into an existing photograph: img2img from the re-noised photograph, and with a mask (white = repaint)
+everything outside it is held to the photograph at every denoising step.
 """
 import argparse
 import json
@@ -30,7 +35,7 @@ def image_grid(imgs, rows, cols):
     return grid
 
 
-def parse_args():
+def parse_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument("--image_path_or_url", type=str, help="path to the input image")
     p.add_argument("--pretrained_model_name_or_path", type=str, help="model dir including config.json, encoder.pt, weight_offsets.pt")
@@ -46,12 +51,24 @@ def parse_args():
     p.add_argument("--random_init", action="store_true", help="random weights + offline tokenizer (no checkpoint needed)")
     p.add_argument("--unet_variant", type=str, default="sd14", choices=["sd14", "sd21"])
     p.add_argument("--output", type=str, default="grid.png")
+    p.add_argument("--init_image", type=str, default=None,
+                   help="edit this photograph (img2img): it is re-noised to --strength of the schedule and denoised from there")
+    p.add_argument("--strength", type=float, default=0.8,
+                   help="share of the schedule an --init_image is re-noised by, in (0, 1]: 1 keeps little of it, small values stay close to it")
+    p.add_argument("--mask_image", type=str, default=None,
+                   help="inpainting mask for --init_image: white is repainted, black is held to the photograph at every step (soft values blend)")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
     cc.add_ema_args(p, training=False)
-    args = p.parse_args()
+    args = p.parse_args(argv)
     cc.check_tome_args(p, args)
     cc.check_ema_args(p, args)
+    if not 0.0 < args.strength <= 1.0:
+        p.error("--strength must lie in (0, 1]")
+    if args.mask_image is not None and args.init_image is None:
+        p.error("--mask_image needs --init_image")
+    if args.init_image is not None and int(args.num_inference_steps * args.strength) < 1:
+        p.error(f"--strength {args.strength} leaves no denoising step of {args.num_inference_steps}")
     return args
 
 
@@ -69,6 +86,7 @@ def setup(args, dev):
     cfg = AttributeDict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1)
     tok, sched = None, SCHEDULER_MAPPING[args.scheduler_type].stable_diffusion("epsilon" if args.unet_variant == "sd14" else "v_prediction")
     pipeline_cfgs = None
+    edit = getattr(args, "init_image", None) is not None        # editing encodes the photograph: the VAE's encoder half is loaded too
     use_ema = getattr(args, "use_ema", False) and not args.random_init
     names = cc.ema_file_names(args.pretrained_model_name_or_path, use_ema)     # --use_ema: exits here when the directory holds no averaged weights
     if not args.random_init:
@@ -89,13 +107,13 @@ def setup(args, dev):
         if ck.is_pipeline_layout(base):
             pipeline_cfgs = ck.pipeline_configs(base)
     if pipeline_cfgs is not None:       # the checkpoint's configs decide the architecture; the pipeline adds the placeholder row
-        unet, enc, text, _ = builders.build_from_configs(dev, pipeline_cfgs["unet"], pipeline_cfgs["text"], pipeline_cfgs["vae"],
-                                                         builders.clip_arch(args.unet_variant), seed=args.seed or 0)
+        unet, enc, text, vae_enc = builders.build_from_configs(dev, pipeline_cfgs["unet"], pipeline_cfgs["text"], pipeline_cfgs["vae"],
+                                                               builders.clip_arch(args.unet_variant), seed=args.seed or 0)
         print(f"[e4t] architecture from {base}: {ck.describe(pipeline_cfgs)}")
         vae = cc.pipeline_vae_decoder(dev, base)
-        cc.load_pipeline_weights(base, unet=unet, text=text)
+        cc.load_pipeline_weights(base, unet=unet, text=text, vae=vae_enc if edit else None)
     else:
-        unet, enc, text, _ = builders.build_models(dev, args.unet_variant, seed=args.seed or 0)    # 49408-row token table; the pipeline adds the placeholder row
+        unet, enc, text, vae_enc = builders.build_models(dev, args.unet_variant, seed=args.seed or 0)    # 49408-row token table; the pipeline adds the placeholder row
         with torch.device(dev):
             vae = VAEDecoder().requires_grad_(False)
     if not args.random_init:
@@ -103,10 +121,12 @@ def setup(args, dev):
             # every load is strict: a misnamed key must not leave random weights behind (e4t/utils.py:119-124)
             checked_load(unet, os.path.join(base, "unet.pt"), lambda k: "wo" in k)
             checked_load(text, os.path.join(base, "text_encoder.pt"))
-            sd = {k: v for k, v in torch.load(os.path.join(base, "vae.pt"), map_location="cpu").items() if k.startswith(("decoder.", "post_quant_conv."))}
-            missing, unexpected = vae.load_state_dict(sd, strict=False)
-            if missing or unexpected:
-                raise RuntimeError(f"{base}/vae.pt: missing {missing[:5]} unexpected {list(unexpected)[:5]}")
+            vae_sd = torch.load(os.path.join(base, "vae.pt"), map_location="cpu")
+            for mod, prefixes in ((vae, ("decoder.", "post_quant_conv.")), (vae_enc if edit else None, ("encoder.", "quant_conv."))):
+                if mod is not None:
+                    missing, unexpected = mod.load_state_dict({k: v for k, v in vae_sd.items() if k.startswith(prefixes)}, strict=False)
+                    if missing or unexpected:
+                        raise RuntimeError(f"{base}/vae.pt: missing {missing[:5]} unexpected {list(unexpected)[:5]}")
         if os.path.exists(os.path.join(d, "unet.pt")) and not use_ema:
             checked_load(unet, os.path.join(d, "unet.pt"))
         else:
@@ -118,7 +138,8 @@ def setup(args, dev):
     else:
         tok = WhitespaceTokenizer(base_size=49408, model_max_length=77)
     pipe = StableDiffusionE4TPipeline(vae=vae, text_encoder=text, tokenizer=tok, unet=unet, e4t_encoder=enc, scheduler=sched,
-                                      safety_checker=None, feature_extractor=None, e4t_config=cfg, requires_safety_checker=False)
+                                      safety_checker=None, feature_extractor=None, e4t_config=cfg, requires_safety_checker=False,
+                                      vae_encoder=vae_enc.requires_grad_(False) if edit else None)
     if not args.random_init:
         d = args.pretrained_model_name_or_path
         checked_load(enc, os.path.join(d, names["encoder.pt"]))
@@ -129,7 +150,7 @@ def setup(args, dev):
     cc.apply_tome_args(unet, args)
     if args.enable_xformers_memory_efficient_attention:
         pipe.enable_xformers_memory_efficient_attention()
-    return dict(pipe=pipe, unet=unet, enc=enc, text=text, vae=vae, tokenizer=tok, scheduler=sched, base_dir=base if not args.random_init else None)
+    return dict(pipe=pipe, unet=unet, enc=enc, text=text, vae=vae, vae_encoder=pipe.vae_encoder, tokenizer=tok, scheduler=sched, base_dir=base if not args.random_init else None)
 
 
 def main():
@@ -144,10 +165,14 @@ def main():
         image = Image.fromarray((torch.rand(512, 512, 3) * 255).to(torch.uint8).numpy())
     generator = torch.Generator(device=dev).manual_seed(args.seed) if args.seed else None
     prompts = args.prompt.split("::")
+    edit_kw = {}
+    if args.init_image:
+        edit_kw = dict(init_image=Image.open(args.init_image).convert("RGB"), strength=args.strength,
+                       mask_image=Image.open(args.mask_image).convert("L") if args.mask_image else None)
     all_images = []
     for prompt in prompts:
         all_images.extend(pipe(prompt, num_inference_steps=args.num_inference_steps, guidance_scale=args.guidance_scale, generator=generator,
-                               image=image, num_images_per_prompt=args.num_images_per_prompt, height=args.height, width=args.width).images)
+                               image=image, num_images_per_prompt=args.num_images_per_prompt, height=args.height, width=args.width, **edit_kw).images)
     image_grid(all_images, len(prompts), args.num_images_per_prompt).save(args.output)
     print(f"DONE! See `{args.output}` for the results!")
 

@@ -2,7 +2,9 @@
 scale_model_input / step loop vs the fused e4t_sampler_step loop run eagerly vs its hipGraph replay, at 1 and 4 images per
 call, plus the VAE decode.  Random-init weights, word-level stand-in tokenizer.
 
-    python tools/bench_inference.py --scheduler ddim dpm_solver++ euler_ancestral plms      (STEPS=50 by default)"""
+    python tools/bench_inference.py --scheduler ddim dpm_solver++ euler_ancestral plms      (STEPS=50 by default)
+    python tools/bench_inference.py --edit --repeats 3       masked inpainting (strength 1: every step runs) next
+                                                             to plain sampling, fused legs only, each leg timed --repeats times"""
 import argparse, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -11,12 +13,14 @@ for p in (os.path.join(ROOT, "e4t-diffusion_amd"), ROOT, os.path.join(ROOT, "tes
 from bench import build_models
 from e4t.pipeline_stable_diffusion_e4t import StableDiffusionE4TPipeline
 from e4t.schedulers import SCHEDULER_MAPPING, DDIMScheduler
-from e4t.vae import VAEDecoder
+from e4t.vae import VAEDecoder, VAEEncoder
 from word_tokenizer import WordTokenizer
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--scheduler", nargs="+", default=["ddim"], choices=sorted(SCHEDULER_MAPPING))
 ap.add_argument("--images", nargs="+", type=int, default=[1, 4])
+ap.add_argument("--edit", action="store_true", help="time masked inpainting (init_image + mask, strength 1) next to plain sampling; fused legs only")
+ap.add_argument("--repeats", type=int, default=1, help="timed calls per leg (their spread is the tool's run-to-run spread)")
 args = ap.parse_args()
 
 dev = torch.device("cuda:0")
@@ -29,19 +33,30 @@ tok = WordTokenizer(base_size=49408, model_max_length=77)
 pipe = StableDiffusionE4TPipeline(vae=vae, text_encoder=text, tokenizer=tok, unet=unet, e4t_encoder=enc, scheduler=DDIMScheduler.stable_diffusion(),
                                   e4t_config=dict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1), already_added_placeholder_token=False)
 image = torch.rand(1, 3, 512, 512) * 2 - 1
+modes = [("plain", {})]
+if args.edit:
+    with torch.device(dev):
+        pipe.vae_encoder = VAEEncoder().requires_grad_(False)
+    mask = torch.zeros(512, 512)
+    mask[:, 252:] = 1.0                  # the edge is not on the latent grid: soft keep values occur
+    modes.append(("edit", dict(init_image=torch.rand(1, 3, 512, 512) * 2 - 1, strength=1.0, mask_image=mask)))
+legs = (("generic", False, False), ("fused eager", True, False), ("graph", True, True))
 for name in args.scheduler:
     pipe.scheduler = SCHEDULER_MAPPING[name].stable_diffusion()
     for n in args.images:
-        for leg, fused, graph in (("generic", False, False), ("fused eager", True, False), ("graph", True, True)):
-            pipe._fused_sampling = fused
-            kw = dict(num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=n, image=image, output_type="np", use_graph=graph)
-            pipe("a painting of *s", **dict(kw, num_inference_steps=2))
-            torch.cuda.synchronize(); t0 = time.perf_counter()
-            out = pipe("a painting of *s", **kw).images
-            torch.cuda.synchronize(); dt = time.perf_counter() - t0
-            calls = len(pipe.scheduler.timesteps)
-            print(f"{name} images/call={n} {leg}: {dt:.2f} s for {calls} model calls ({dt/calls*1e3:.1f} ms/step incl. capture+decode) "
-                  f"-> {n/dt:.2f} img/s; out {out.shape}", flush=True)
+        for mode, edit_kw in modes:
+            for leg, fused, graph in (legs[1:] if args.edit else legs):
+                pipe._fused_sampling = fused
+                kw = dict(num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=n, image=image, output_type="np", use_graph=graph,
+                          **edit_kw)
+                pipe("a painting of *s", **dict(kw, num_inference_steps=2))
+                for _ in range(args.repeats):
+                    torch.cuda.synchronize(); t0 = time.perf_counter()
+                    out = pipe("a painting of *s", **kw).images
+                    torch.cuda.synchronize(); dt = time.perf_counter() - t0
+                    calls = len(pipe.scheduler.timesteps)
+                    print(f"{name} {mode} images/call={n} {leg}: {dt:.2f} s for {calls} model calls ({dt/calls*1e3:.1f} ms/step incl. capture+decode"
+                          f"{'+encode' if edit_kw else ''}) -> {n/dt:.2f} img/s; out {out.shape}", flush=True)
     pipe._fused_sampling = True
 z = torch.randn(4, 4, 64, 64, device=dev) * 0.18215
 vae.decode_latents(z); torch.cuda.synchronize(); t0 = time.perf_counter()
