@@ -1622,29 +1622,56 @@ int resolve_launch(const GemmPlan& pl, GemmArgs& p, bool conv, int epi, size_t w
   return splitk;
 }
 
-int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
-  int tail = 0;
-  const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
+// Everything a launch decides between the plan and the kernel launch, in ONE place that launch_gemm() and e4t_gemm_kernel() both call, so that
+// the launch cannot decide anything the query does not see: the fused-GEGLU refusal, the tail rows taken off the tile grid, resolve_launch()
+// (split-K that really runs, kernel entry), the store path of write_tile (fast_epi / fast_f32 / scalar / split-K partial), whether column
+// statistics are written, the reduce kernel (vec8 and reduce_kernel()) and the row-panel refusal.  Fills p; dereferences nothing.
+struct LaunchDecision {
+  const KernelEntry* entry;
+  const ReduceKernel* reduce;      // nullptr: no reduction follows
+  int splitk, nz, m_all, epi, store, stats_written;
+  bool vec8;
+};
+// the branch order of write_tile (gemm_common.h), restated on the host for the query: keep the two together
+int store_path(const GemmArgs& p, int epi) {
+  return epi != EPI_PLAIN ? E4T_STORE_BF16_STAGED : p.ws ? E4T_STORE_SPLITK_PARTIAL : p.fast_epi ? E4T_STORE_BF16_STAGED : p.fast_f32 ? E4T_STORE_F32_DIRECT : E4T_STORE_SCALAR;
+}
+int decide_launch(const GemmPlan& pl, GemmArgs& p, bool conv, int tail, size_t ws_bytes, int splitk_req, int batch, LaunchDecision& ld) {
   const Variant& v = *pl.run;
-  const int epi = conv ? EPI_PLAIN : epi_kind(p);
+  const int epi = ld.epi = conv ? EPI_PLAIN : epi_kind(p);
   E4T_REFUSE_FUSED(pl, p, tail, batch);
-  const int m_all = p.M;                 // (launch log: the caller's shape)
+  ld.m_all = p.M;                        // (launch log: the caller's shape)
   if (tail) { p.M -= tail; p.tail_row0 = p.M; p.tail_rows = tail; }      // the tile grid covers [0, M - tail); gemm_tail() the rest
-  const KernelEntry* entry = nullptr;
-  const int splitk = resolve_launch(pl, p, conv, epi, ws_bytes, splitk_req, batch, entry);
+  const int splitk = resolve_launch(pl, p, conv, epi, ws_bytes, splitk_req, batch, ld.entry);
   if (splitk < 0) return splitk;
-  const KernelEntry& k = *entry;
+  ld.splitk = splitk;
   p.group_m = 8;                           // row panels per raster group (swept in round 4: profiles/r04_ab/r04f_*)
   p.fast_epi = bf16_rows_aligned16(p) && p.strideC % 8 == 0;
   p.fast_f32 = (p.flags & E4T_OUT_F32) && !(p.flags & E4T_ACCUM) && !p.rowbias && (!p.residual || (p.flags & E4T_RES_F32)) &&
                (!(p.flags & E4T_ACT_GELU) || pl.general_epi);
   if (p.colstats && (p.ws || !p.fast_epi || p.M % 32 != 0 || batch != 1)) p.colstats = nullptr;   // only the bf16 single-pass epilogue produces them
-  const int stats_written = p.colstats != nullptr && (v.caps & CAP_COLSTATS);
+  ld.stats_written = p.colstats != nullptr && (v.caps & CAP_COLSTATS);
   // split-K / batch reduction: 8 columns per thread when bias, row bias and workspace are 16-byte aligned too
-  const bool vec8 = p.ws && bf16_rows_aligned16(p) && p.strideC % 8 == 0 &&
-                    (!p.bias || (((uintptr_t)p.bias & 15) == 0 && p.strideBias % 4 == 0)) &&
-                    (!p.rowbias || (((uintptr_t)p.rowbias & 15) == 0 && p.ldrb % 4 == 0)) && ((uintptr_t)p.ws & 15) == 0;
-  const int nz = p.reduce_batch ? splitk * batch : splitk;
+  ld.vec8 = p.ws && bf16_rows_aligned16(p) && p.strideC % 8 == 0 &&
+            (!p.bias || (((uintptr_t)p.bias & 15) == 0 && p.strideBias % 4 == 0)) &&
+            (!p.rowbias || (((uintptr_t)p.rowbias & 15) == 0 && p.ldrb % 4 == 0)) && ((uintptr_t)p.ws & 15) == 0;
+  ld.nz = p.reduce_batch ? splitk * batch : splitk;
+  ld.reduce = p.ws ? &reduce_kernel(p, ld.vec8) : nullptr;
+  ld.store = store_path(p, epi);
+  if (p.panel_rows && !((v.caps & CAP_PANELS) && splitk == 1 && !p.ws))
+    E4T_FAIL(-22, "gemm: row panels need the 256 x 320 ping-pong tile (N %% 320 == 0, K %% 64 == 0, no split-K); the plan chose tile %d", pl.tile);
+  return splitk;
+}
+
+int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int splitk_req, int batch, hipStream_t st) {
+  int tail = 0;
+  const GemmPlan pl = plan_gemm_tail(p, conv, tile_hint, splitk_req, batch, tail);
+  LaunchDecision ld = {};
+  const int splitk = decide_launch(pl, p, conv, tail, ws_bytes, splitk_req, batch, ld);
+  if (splitk < 0) return splitk;
+  const KernelEntry& k = *ld.entry;
+  const int epi = ld.epi, m_all = ld.m_all, nz = ld.nz, stats_written = ld.stats_written;
+  const bool vec8 = ld.vec8;
   if (e4t_launch_log_enabled()) {
     // algorithmic bytes: every operand element once (conv: the input map once, not once per tap), the output once
     const double osz = (p.flags & E4T_OUT_F32) ? 4.0 : 2.0;
@@ -1661,8 +1688,6 @@ int launch_gemm(GemmArgs p, bool conv, int tile_hint, size_t ws_bytes, int split
                         by + (double)tail * (2.0 * p.K + (osz + (p.residual ? ((p.flags & E4T_RES_F32) ? 4.0 : 2.0) : 0.0)) * p.N), 2.0 * m_all * p.N * (double)p.K * batch);
     if (p.ws) log_splitk_reduce(p, nz, splitk * batch, vec8);
   }
-  if (p.panel_rows && !((v.caps & CAP_PANELS) && splitk == 1 && !p.ws))
-    E4T_FAIL(-22, "gemm: row panels need the 256 x 320 ping-pong tile (N %% 320 == 0, K %% 64 == 0, no split-K); the plan chose tile %d", pl.tile);
   hipLaunchKernelGGL(k.fn, dim3(pl.gx, pl.gy, splitk * batch), dim3(k.threads), 0, st, p);
   E4T_CHECK_LAUNCH("gemm_kernel");
   if (const int rc = p.ws ? launch_splitk_reduce(p, nz, p.reduce_batch ? 1 : batch, vec8, st) : 0; rc < 0) return rc;
@@ -1764,7 +1789,10 @@ extern "C" int e4t_gemm_tn_plan(const e4t_gemm_desc* d, e4t_gemm_plan_t* out) {
   return 0;
 }
 
-extern "C" int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream) {
+namespace {
+
+// the arguments e4t_gemm_nt accepts, for the launch and for the kernel query alike
+int check_gemm_nt_args(const e4t_gemm_desc* d) {
   E4T_REQUIRE(d && d->A && d->B && d->C, "gemm_nt: null operand");
   E4T_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0, "gemm_nt: bad shape M=%d N=%d K=%d", d->M, d->N, d->K);
   E4T_REQUIRE(d->K % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0, "gemm_nt: K, lda, ldb must be multiples of 8 (16-B rows)");
@@ -1784,18 +1812,19 @@ extern "C" int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream) {
                 "gemm_nt: row panels do not combine with batch / row bias / column statistics / two-source A / accumulate / split-K");
   }
   E4T_REQUIRE(!(d->flags & (E4T_EPI_GEGLU | E4T_EPI_GEGLU_BWD)) || d->aux, "gemm_nt: the fused GEGLU epilogues need aux (h out / u in)");
-  GemmArgs p;
-  fill_gemm_args(d, p);
-  return launch_gemm(p, false, d->tile, d->workspace_bytes, d->splitk, batch, (hipStream_t)stream);
+  return 0;
 }
 
-extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
+// What e4t_gemm_tn decides before its launch, in ONE place that the launch and e4t_gemm_tn_kernel() both call: argument checks, operand extents, the
+// split-K that really runs (the automatic choice falls back to one pass without its workspace, an explicit one fails with -12), the store path.
+// Fills p and dereferences nothing.  Returns the split-K, or a negative error code with the message set.
+int resolve_tn(const e4t_gemm_desc* d, GemmArgs& p) {
   E4T_REQUIRE(d && d->A && d->B && d->C, "gemm_tn: null operand");
   E4T_REQUIRE(d->M > 0 && d->N > 0 && d->K > 0 && d->batch <= 1 && !d->A2 && !d->rowbias, "gemm_tn: bad / unsupported arguments");
   E4T_REQUIRE(!(d->flags & (E4T_ACT_GELU | E4T_EPI_GEGLU | E4T_EPI_GEGLU_BWD)), "gemm_tn: the GELU / GEGLU epilogues are not built for the TN kernel");
   E4T_REQUIRE(d->M % 8 == 0 && d->N % 8 == 0 && d->lda % 8 == 0 && d->ldb % 8 == 0 && ((uintptr_t)d->A & 15) == 0 && ((uintptr_t)d->B & 15) == 0,
               "gemm_tn: M, N, lda, ldb must be multiples of 8 and the operands 16-byte aligned");
-  GemmArgs p;      // (not fill_gemm_args: the fields the TN kernel does not support — lda2, strides, row panels, ... — stay zero whatever the caller left there)
+  // (not fill_gemm_args: the fields the TN kernel does not support — lda2, strides, row panels, ... — stay zero whatever the caller left there)
   memset(&p, 0, sizeof(p));
   p.zslab = -1;
   p.A = (const bf16_t*)d->A; p.lda = d->lda; p.B = (const bf16_t*)d->B; p.ldb = d->ldb;
@@ -1803,7 +1832,7 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   p.M = d->M; p.N = d->N; p.K = d->K; p.K1 = d->K; p.alpha = d->alpha; p.flags = d->flags & ~E4T_REDUCE_BATCH;
   p.rows_per_batch = 1; p.ldrb = d->N;
   p.ws = (float*)d->workspace;
-  const int nkt = cdiv(p.K, BK), gx = cdiv(p.N, 128), gy = cdiv(p.M, 128);
+  const int nkt = cdiv(p.K, BK);
   {   // operand extents for the buffer resources (32-bit byte offsets)
     const unsigned long long ab = ((unsigned long long)(p.K - 1) * p.lda + p.M) * 2, bb = ((unsigned long long)(p.K - 1) * p.ldb + p.N) * 2;
     E4T_REQUIRE(ab < 0xFFFF0000ull && bb < 0xFFFF0000ull, "gemm_tn: operands beyond 4 GB are not supported");
@@ -1822,6 +1851,42 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   p.group_m = 8;
   p.xcd3 = splitk > 1;                     // (2-D raster: gemm_tn M960 N320 K65536 90.6 vs 67.4 us)
   p.fast_epi = bf16_rows_aligned16(p);
+  return splitk;
+}
+
+void export_kernel(const char* symbol, const ReduceKernel* reduce, int splitk, int tail, int store, int stats, e4t_gemm_kernel_t* out) {
+  out->symbol = symbol; out->reduce = reduce ? reduce->text : nullptr; out->splitk = splitk; out->tail_rows = tail; out->store = store; out->colstats = stats;
+}
+
+}  // namespace
+
+extern "C" int e4t_gemm_nt(const e4t_gemm_desc* d, e4t_stream stream) {
+  if (const int rc = check_gemm_nt_args(d); rc < 0) return rc;
+  GemmArgs p;
+  fill_gemm_args(d, p);
+  return launch_gemm(p, false, d->tile, d->workspace_bytes, d->splitk, d->batch > 0 ? d->batch : 1, (hipStream_t)stream);
+}
+
+extern "C" int e4t_gemm_kernel(const e4t_gemm_desc* d, e4t_gemm_kernel_t* out) {
+  E4T_REQUIRE(out, "gemm_kernel: bad arguments");
+  if (const int rc = check_gemm_nt_args(d); rc < 0) return rc;
+  GemmArgs p;
+  fill_gemm_args(d, p);
+  const int batch = d->batch > 0 ? d->batch : 1;
+  int tail = 0;
+  const GemmPlan pl = plan_gemm_tail(p, false, d->tile, d->splitk, batch, tail);
+  LaunchDecision ld = {};
+  const int sk = decide_launch(pl, p, false, tail, d->workspace_bytes, d->splitk, batch, ld);
+  if (sk < 0) return sk;
+  export_kernel(ld.entry->text, ld.reduce, sk, tail, ld.store, ld.stats_written, out);
+  return 0;
+}
+
+extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
+  GemmArgs p;
+  const int splitk = resolve_tn(d, p);
+  if (splitk < 0) return splitk;
+  const int gx = cdiv(p.N, 128), gy = cdiv(p.M, 128);
   hipStream_t st = (hipStream_t)stream;
   if (e4t_launch_log_enabled()) {
     const double osz = (p.flags & E4T_OUT_F32) ? 4.0 : 2.0;
@@ -1832,6 +1897,15 @@ extern "C" int e4t_gemm_tn(const e4t_gemm_desc* d, e4t_stream stream) {
   hipLaunchKernelGGL(gemm_tn_kernel, dim3(gx, gy, splitk), dim3(512), 0, st, p);
   E4T_CHECK_LAUNCH("gemm_tn_kernel");
   return p.ws ? launch_splitk_reduce(p, splitk, 1, false, st) : 0;
+}
+
+extern "C" int e4t_gemm_tn_kernel(const e4t_gemm_desc* d, e4t_gemm_kernel_t* out) {
+  E4T_REQUIRE(out, "gemm_tn_kernel: bad arguments");
+  GemmArgs p;
+  const int splitk = resolve_tn(d, p);
+  if (splitk < 0) return splitk;
+  export_kernel("gemm_tn_kernel", p.ws ? &reduce_kernel(p, false) : nullptr, splitk, 0, store_path(p, EPI_PLAIN), 0, out);
+  return 0;
 }
 
 extern "C" int e4t_conv3x3(const e4t_conv_desc* d, e4t_stream stream) {

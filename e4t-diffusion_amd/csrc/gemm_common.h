@@ -118,6 +118,8 @@ __device__ __forceinline__ void write_tile(const GemmArgs& p, f32x16 (&acc)[FM][
   const int frow = lane & 31, fhi = lane >> 5;
   // ---- epilogue: C/D layout of 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5) ----
   const bool partial = p.ws != nullptr;
+  // (the order of the four store paths below — staged bf16, direct fp32, scalar, split-K partial — is restated on the host for e4t_gemm_kernel:
+  // gemm.hip, store_path(); a change here goes there too)
   if (EPI != EPI_PLAIN || (!partial && p.fast_epi)) {
     // bf16 output: stage the wave's WM x WN tile through LDS (the operand tiles are dead after the loop's final
     // barrier) so that C is written — and the residual read — as 16-byte chunks, 128 B contiguous per row.

@@ -43,6 +43,11 @@ class GemmPlan(C.Structure):
     _fields_ = [("tile", i32), ("tile_m", i32), ("tile_n", i32), ("splitk", i32), ("workspace_bytes", sz), ("tail_rows", i32), ("stages", i32)]
 
 
+class GemmKernel(C.Structure):
+    """e4t_gemm_kernel_t: the kernels a GEMM descriptor launches, from the launcher's own decision (e4t_gemm_kernel / e4t_gemm_tn_kernel)"""
+    _fields_ = [("symbol", C.c_char_p), ("reduce", C.c_char_p), ("splitk", i32), ("tail_rows", i32), ("store", i32), ("colstats", i32)]
+
+
 class AttentionPlan(C.Structure):
     """e4t_attention_plan_t: the kernels the attention launchers choose for a shape, as the launch log spells them"""
     _fields_ = [("fwd", C.c_char_p), ("dq", C.c_char_p), ("dkv", C.c_char_p), ("tsplit", i32), ("tchunk", i32), ("dkv_occ", i32), ("workspace_floats", sz)]
@@ -70,6 +75,8 @@ SIGNATURES = {
     "e4t_gemm_tn_plan": (i32, [C.POINTER(GemmDesc), C.POINTER(GemmPlan)]),
     "e4t_conv3x3_plan": (i32, [C.POINTER(ConvDesc), C.POINTER(GemmPlan)]),
     "e4t_conv3x3_kernel": (i32, [C.POINTER(ConvDesc), C.POINTER(C.c_char_p), C.POINTER(i32)]),
+    "e4t_gemm_kernel": (i32, [C.POINTER(GemmDesc), C.POINTER(GemmKernel)]),
+    "e4t_gemm_tn_kernel": (i32, [C.POINTER(GemmDesc), C.POINTER(GemmKernel)]),
     "e4t_attention_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i64, i64, i64, i64, f32, i32, vp]),
     "e4t_attention_bwd": (i32, [vp] * 10 + [i32] * 9 + [i64] * 4 + [f32, i32, vp]),
     "e4t_attention_bwd_workspace_floats": (sz, [i32] * 5),
@@ -142,6 +149,7 @@ SIGNATURES = {
 OUT_F32, RES_F32, ACT_GELU, ACCUM, REDUCE_BATCH = 1, 2, 4, 8, 16
 EPI_GEGLU, EPI_GEGLU_BWD = 32, 64      # GEGLU fused into the GEMM epilogue (e4t_hip.h)
 ERR_NO_FUSED = -95                     # e4t_gemm_nt: no fused kernel for the descriptor's plan; nothing was launched
+STORE_NAMES = ("bf16-staged", "f32-direct", "scalar", "splitk-partial")      # E4T_STORE_* of e4t_gemm_kernel_t.store, in clear text
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 1, 2, 3, 4, 5
 WO_STORE_F32, WO_OFFSETS_ONLY = 1, 2
 SAMPLER_MAX_HIST, SAMPLER_ROW = 4, 16

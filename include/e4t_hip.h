@@ -160,6 +160,26 @@ int e4t_conv3x3_plan(const e4t_conv_desc* d, e4t_gemm_plan_t* out);
  * one pass included (an explicit split-K without its workspace fails with -12, as the launch does).  Pure host code from the launcher's own
  * decision; no pointer of the descriptor is dereferenced (NULL or not matters as for the plan; X, W, Y may be NULL). */
 int e4t_conv3x3_kernel(const e4t_conv_desc* d, const char** symbol, int* splitk);
+/* Which kernels e4t_gemm_nt / e4t_gemm_tn will launch for a descriptor, WITHOUT launching, from the function the launch itself calls for the
+ * decision (gemm.hip: decide_launch / resolve_tn) — the launch decides nothing this does not report.  Pure host code.  No pointer of the descriptor is
+ * ever dereferenced: whether a pointer is NULL or not and whether it is 16-byte aligned are read (A, B, C, A2, bias, rowbias, residual, colstats,
+ * workspace, aux: alignment selects the store path, the reduce kernel and the tail stage), workspace_bytes is read as given.  Every argument check of
+ * the launch is made (same code, same message); an explicit split-K without its workspace returns -12, a fused GEGLU descriptor the launch would
+ * refuse E4T_ERR_NO_FUSED with the launch's message. */
+#define E4T_STORE_BF16_STAGED 0    /* bf16 C through the LDS-staged 16-byte stores (write_tile: fast_epi; the fused GEGLU epilogues) */
+#define E4T_STORE_F32_DIRECT 1     /* fp32 C straight from the accumulator layout (fast_f32) */
+#define E4T_STORE_SCALAR 2         /* one element at a time (epilogue_store) */
+#define E4T_STORE_SPLITK_PARTIAL 3 /* fp32 partial sums into the workspace; `reduce` writes C */
+typedef struct {
+  const char* symbol;  /* the GEMM kernel's symbol text as the launch log spells it (a string owned by the library) */
+  const char* reduce;  /* the split-K / batch reduction kernel that follows it, or NULL */
+  int splitk;          /* the split-K that really runs, the automatic fall-back to one pass without workspace included */
+  int tail_rows;       /* rows handed to the tail stage of the same launch (e4t_gemm_plan_t.tail_rows) */
+  int store;           /* E4T_STORE_* of the tile grid's rows (tail rows always go through the scalar store) */
+  int colstats;        /* 1: column statistics will be written (what e4t_gemm_nt returns) */
+} e4t_gemm_kernel_t;
+int e4t_gemm_kernel(const e4t_gemm_desc* d, e4t_gemm_kernel_t* out);
+int e4t_gemm_tn_kernel(const e4t_gemm_desc* d, e4t_gemm_kernel_t* out);
 
 /* ---------------------------------------------------------------- attention (attention.hip) -- */
 /* O = softmax(Q K^T * scale) V ; Q/K/V/O are (B, T|S, heads*DH) bf16 matrices with row strides ld*

@@ -8,9 +8,9 @@ bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumu
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
 
-Importable without a GPU: the attention, conv and norm case lists, slices(), conv_slices() and norm_slices(), norm_plan() and the fp64 norm
-references are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py, test_conv_slices_cpu.py, test_norm_slices_cpu.py,
-test_norm_plan_cpu.py).
+Importable without a GPU: the attention, conv, norm and GEMM case lists, slices(), conv_slices(), norm_slices() and gemm_slices(), norm_plan() and the
+fp64 norm and GEMM references are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py, test_conv_slices_cpu.py,
+test_norm_slices_cpu.py, test_norm_plan_cpu.py, test_gemm_slices_cpu.py).
 """
 from __future__ import annotations
 
@@ -51,20 +51,36 @@ def check_probe(hip, emu, dev):
     return [("mfma32 row map", rel(rows, exp_rows), 0.0), ("mfma32 col map", rel(cols, exp_cols), 0.0)]
 
 
+# the shapes of check_gemm as plain data (tests/test_gemm_dispatch.py pins their kernels through check_gemm_pinned())
+CHECK_GEMM_NT = [  # M, N, K, tile, splitk
+    (256, 256, 128, 0, 0), (200, 72, 64, 0, 0), (1000, 320, 320, 128, 1), (130, 200, 1032, 64, 3),
+    (16, 1280, 1280, 0, 0), (4096, 640, 2560, 0, 0), (64, 64, 4096, 0, 0), (1000, 200, 328, 256, 1), (2048, 256, 64, 256, 1),
+    (700, 320, 1280, 256, 2), (900, 320, 384, 160, 1), (300, 480, 128, 160, 2), (513, 200, 72, 160, 1),
+    (512, 512, 512, 512, 1), (700, 520, 256, 512, 1), (300, 256, 64, 512, 1), (1000, 300, 128, 512, 1), (513, 1000, 1152, 512, 2),
+    (2048, 1280, 1920, 512, 0), (257, 64, 192, 512, 1),
+    (4096, 1280, 10240, 0, 0), (4096, 2560, 8192, 0, 0),       # auto: K-deep, 64-255 tiles of 256 x 256 -> ping-pong + split-K (3 | 1)
+    (900, 384, 512, 5256, 1), (5000, 640, 320, 5256, 1),         # 256 x 128 with 32-wide K-tiles: ragged M, N one and a half / five column tiles
+    # k-step-phased ping-pong tile (gemm_pq_kernel): 256 x 320 (wave tile 64 x 160); ragged M / N, one K-tile, split-K
+    (1000, 320, 320, 2320, 1), (700, 640, 256, 2320, 1), (300, 200, 64, 2320, 1), (4096, 1280, 2560, 2320, 0), (513, 1000, 1152, 2320, 2),
+    (65536, 320, 320, 2320, 1), (16384, 640, 640, 2320, 0),
+]
+CHECK_GEMM_TN = [(64, 128, 128, 1), (1000, 320, 320, 0), (4096, 960, 320, 0), (777, 200, 72, 3), (65536, 320, 320, 0),
+                 (1232, 2560, 768, 0), (130, 8, 1280, 1)]      # K, M, N, splitk
+CHECK_GEMM_COLSTATS = [(256, 128, 128, 0), (4096, 320, 320, 160), (1024, 640, 1280, 128), (2048, 512, 2304, 512), (192, 72, 64, 64),
+                       (4096, 320, 320, 160), (8192, 256, 128, 128), (66560, 640, 192, 160), (34816, 128, 64, 128),      # more than 65536 rows, K = 192, one K-tile
+                       (4096, 320, 320, 2320), (8192, 640, 640, 2320)]      # M, N, K, tile
+CHECK_GEMM_TAIL = [(4112, 1280, 1280, dict(f32=True)), (4112, 5120, 1280, dict(gelu=True)), (4112, 1280, 5120, dict(f32=True)), (4112, 3840, 1280, {}),
+                   (8224, 1280, 1280, dict(res=True)), (8224, 5120, 1280, dict(gelu=True)), (4096 + 1, 1280, 1280, dict(res=True)), (4096 + 31, 3840, 1280, {}),
+                   (4112, 1280, 1296, dict(f32=True)), (2056, 1280, 5120, {})]
+CHECK_GEMM_F32RES = [(4112, 1280, 1280, 0), (4112, 1280, 5120, 0), (1000, 1280, 320, 160), (700, 512, 256, 512), (513, 200, 64, 64), (900, 384, 96, 5256),
+                     (1000, 640, 320, 2320)]      # M, N, K, tile
+CHECK_GEMM_PQ_GENERAL = [(1000, 640, 320), (4096, 320, 1280), (513, 960, 64)]
+CHECK_GEMM_PANELS = [(3, 257, 640, 128, 256, bf16), (16, 257, 5120, 1280, 256, bf16), (2, 520, 320, 64, 512, f32), (5, 257, 960, 192, 256, bf16)]      # B, T, N, K, panel rows, C type
+
+
 def check_gemm(hip, emu, dev):
     out = []
-    cases = [  # M, N, K, tile, splitk
-        (256, 256, 128, 0, 0), (200, 72, 64, 0, 0), (1000, 320, 320, 128, 1), (130, 200, 1032, 64, 3),
-        (16, 1280, 1280, 0, 0), (4096, 640, 2560, 0, 0), (64, 64, 4096, 0, 0), (1000, 200, 328, 256, 1), (2048, 256, 64, 256, 1),
-        (700, 320, 1280, 256, 2), (900, 320, 384, 160, 1), (300, 480, 128, 160, 2), (513, 200, 72, 160, 1),
-        (512, 512, 512, 512, 1), (700, 520, 256, 512, 1), (300, 256, 64, 512, 1), (1000, 300, 128, 512, 1), (513, 1000, 1152, 512, 2),
-        (2048, 1280, 1920, 512, 0), (257, 64, 192, 512, 1),
-        (4096, 1280, 10240, 0, 0), (4096, 2560, 8192, 0, 0),       # auto: K-deep, 64-255 tiles of 256 x 256 -> ping-pong + split-K (3 | 1)
-        (900, 384, 512, 5256, 1), (5000, 640, 320, 5256, 1),         # 256 x 128 with 32-wide K-tiles: ragged M, N one and a half / five column tiles
-        # k-step-phased ping-pong tile (gemm_pq_kernel): 256 x 320 (wave tile 64 x 160); ragged M / N, one K-tile, split-K
-        (1000, 320, 320, 2320, 1), (700, 640, 256, 2320, 1), (300, 200, 64, 2320, 1), (4096, 1280, 2560, 2320, 0), (513, 1000, 1152, 2320, 2),
-        (65536, 320, 320, 2320, 1), (16384, 640, 640, 2320, 0),
-    ]
+    cases = CHECK_GEMM_NT
     for i, (M, N, K, tile, sk) in enumerate(cases):
         g = gen(10 + i, dev)
         a, b = rnd(g, M, K, dev=dev), rnd(g, N, K, scale=K ** -0.5, dev=dev)
@@ -74,8 +90,7 @@ def check_gemm(hip, emu, dev):
         yr = emu.gemm(a, b, bias=bias, residual=res)
         out.append((f"gemm {M}x{N}x{K} t{tile} s{sk} bias+res", rel(y, yr), TOL1))
     # TN: contraction over the rows (weight gradients)
-    for i, (K, M, N, sk) in enumerate([(64, 128, 128, 1), (1000, 320, 320, 0), (4096, 960, 320, 0), (777, 200, 72, 3), (65536, 320, 320, 0),
-                                       (1232, 2560, 768, 0), (130, 8, 1280, 1)]):
+    for i, (K, M, N, sk) in enumerate(CHECK_GEMM_TN):
         g = gen(40 + i, dev)
         a, b = rnd(g, K, M + 8, dev=dev)[:, :M], rnd(g, K, N, scale=K ** -0.5, dev=dev)
         out.append((f"gemm_tn K{K} M{M} N{N} s{sk}", rel(hip.gemm_tn(a, b, splitk=sk), emu.gemm_tn(a, b)), TOLF * 50))
@@ -88,9 +103,7 @@ def check_gemm(hip, emu, dev):
     hip.gemm_tn(a, b, out=wide[:, 100:428]); emu.gemm_tn(a, b, out=wide2[:, 100:428])
     out.append(("gemm_tn into a column slice", rel(wide, wide2), TOLF * 50))
     # column statistics left by the epilogue for the consuming GroupNorm (all tile variants; with / without residual)
-    for i, (M, N, K, tile) in enumerate([(256, 128, 128, 0), (4096, 320, 320, 160), (1024, 640, 1280, 128), (2048, 512, 2304, 512), (192, 72, 64, 64),
-                                         (4096, 320, 320, 160), (8192, 256, 128, 128), (66560, 640, 192, 160), (34816, 128, 64, 128),      # more than 65536 rows, K = 192, one K-tile
-                                         (4096, 320, 320, 2320), (8192, 640, 640, 2320)]):
+    for i, (M, N, K, tile) in enumerate(CHECK_GEMM_COLSTATS):
         g = gen(60 + i, dev)
         a, b = rnd(g, M, K, dev=dev), rnd(g, N, K, scale=K ** -0.5, dev=dev)
         res = rnd(g, M, N, dev=dev) if i % 2 == 0 else None
@@ -122,9 +135,7 @@ def check_gemm(hip, emu, dev):
     gt = gen(35, dev)
     import ctypes as _ct
     from e4t import _C as _Cm
-    for (Mt, Nt, Kt, kw) in [(4112, 1280, 1280, dict(f32=True)), (4112, 5120, 1280, dict(gelu=True)), (4112, 1280, 5120, dict(f32=True)), (4112, 3840, 1280, {}),
-                             (8224, 1280, 1280, dict(res=True)), (8224, 5120, 1280, dict(gelu=True)), (4096 + 1, 1280, 1280, dict(res=True)), (4096 + 31, 3840, 1280, {}),
-                             (4112, 1280, 1296, dict(f32=True)), (2056, 1280, 5120, {})]:
+    for (Mt, Nt, Kt, kw) in CHECK_GEMM_TAIL:
         at, bt = rnd(gt, Mt, Kt, dev=dev), rnd(gt, Nt, Kt, scale=Kt ** -0.5, dev=dev)
         bi = rnd(gt, Nt, dtype=f32, dev=dev)
         res = rnd(gt, Mt, Nt, dtype=f32 if kw.get("f32") else bf16, dev=dev) if (kw.get("f32") or kw.get("res")) else None
@@ -142,8 +153,7 @@ def check_gemm(hip, emu, dev):
             out.append((f"gemm {Mt}x{Nt}x{Kt} tail{r}: the last tile rows in front of the tail", rel(y[Mt - r - 64:Mt - r], yr[Mt - r - 64:Mt - r]), tol))
     # fp32 C + fp32 residual (the CLIP-ViT's fp32 residual stream): the line-wide direct-store epilogue, every kernel family
     gv = gen(33, dev)
-    for (Mv, Nv, Kv, t) in [(4112, 1280, 1280, 0), (4112, 1280, 5120, 0), (1000, 1280, 320, 160), (700, 512, 256, 512), (513, 200, 64, 64), (900, 384, 96, 5256),
-                             (1000, 640, 320, 2320)]:
+    for (Mv, Nv, Kv, t) in CHECK_GEMM_F32RES:
         av, bw = rnd(gv, Mv, Kv, dev=dev), rnd(gv, Nv, Kv, scale=Kv ** -0.5, dev=dev)
         r32, bi = rnd(gv, Mv, Nv, dtype=f32, dev=dev), rnd(gv, Nv, dtype=f32, dev=dev)
         out.append((f"gemm {Mv}x{Nv}x{Kv} t{t} fp32 out + fp32 residual", rel(hip.gemm(av, bw, bias=bi, residual=r32, out_dtype=f32, tile=t),
@@ -151,14 +161,14 @@ def check_gemm(hip, emu, dev):
     # the GENERAL (GELU / row-lookup) epilogue of the 256 x 320 ping-pong tile (GEMM only) and its row panels (e4t_gemm_desc.panel_*):
     # ragged M, several K depths, bf16 and fp32 output; panels leave the rows between them (the class-token rows) untouched
     gp = gen(34, dev)
-    for (Mg, Ng, Kg) in [(1000, 640, 320), (4096, 320, 1280), (513, 960, 64)]:
+    for (Mg, Ng, Kg) in CHECK_GEMM_PQ_GENERAL:
         ag, bg, big = rnd(gp, Mg, Kg, dev=dev), rnd(gp, Ng, Kg, scale=Kg ** -0.5, dev=dev), rnd(gp, Ng, dtype=f32, dev=dev)
         out.append((f"gemm {Mg}x{Ng}x{Kg} t2320 gelu", rel(hip.gemm(ag, bg, bias=big, gelu=True, tile=2320), emu.gemm(ag, bg, bias=big, gelu=True)), TOL1))
         Mr = (Mg // 97) * 97                      # rows_per_batch = 97 (not a multiple of 32): the per-row row-bias lookup of the GENERAL epilogue
         rbg = rnd(gp, Mr // 97, Ng, dtype=f32, dev=dev)
         out.append((f"gemm {Mr}x{Ng}x{Kg} t2320 row bias, rows_per_batch 97", rel(hip.gemm(ag[:Mr], bg, rowbias=rbg, rows_per_batch=97, tile=2320),
                                                                                  emu.gemm(ag[:Mr], bg, rowbias=rbg, rows_per_batch=97)), TOL1))
-    for (Bp, Tp, Np, Kp, pr, dt) in [(3, 257, 640, 128, 256, bf16), (16, 257, 5120, 1280, 256, bf16), (2, 520, 320, 64, 512, f32), (5, 257, 960, 192, 256, bf16)]:
+    for (Bp, Tp, Np, Kp, pr, dt) in CHECK_GEMM_PANELS:
         ap, bp, bip = rnd(gp, Bp * Tp, Kp, dev=dev), rnd(gp, Np, Kp, scale=Kp ** -0.5, dev=dev), rnd(gp, Np, dtype=f32, dev=dev)
         resid = rnd(gp, Bp * Tp, Np, dtype=dt, dev=dev) if dt == f32 else None
         yh = torch.full((Bp * Tp, Np), 7.0, dtype=dt, device=dev)
@@ -1858,10 +1868,616 @@ def check_gemm_races(hip, emu, dev):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ dense GEMM: K-loop, edges, forms, guards
+# Plain data, importable without a GPU.  tests/test_gemm_dispatch.py pins what e4t_gemm_kernel / e4t_gemm_tn_kernel say every case runs (kernel symbol,
+# split-K, store path, reduce kernel, tail rows) and holds the set the cases reach against everything the query returns over the dispatch corpus;
+# tests/test_gemm_slices_cpu.py holds a rounding-only model to half the tolerance on every row gemm_slices() emits for them.
+# hint -> tile_m, tile_n, K-tile width, LDS stages, needs whole K-tiles, needs whole column tiles, has a GENERAL instantiation, carries the tail stage
+GEMM_TILES = {
+    64: (64, 64, 64, 2, False, False, True, False), 3064: (64, 64, 64, 3, False, False, True, False), 4064: (64, 64, 64, 4, False, False, False, False),
+    128: (128, 128, 64, 2, False, False, True, False), 3128: (128, 128, 64, 3, False, False, False, False), 4128: (128, 128, 64, 4, False, False, False, False),
+    160: (128, 160, 64, 2, False, False, True, True), 3160: (128, 160, 64, 3, False, False, False, True), 4160: (128, 160, 64, 4, False, False, False, True),
+    5256: (256, 128, 32, 3, False, False, False, False), 512: (256, 256, 64, 2, True, False, True, True), 2320: (256, 320, 64, 2, True, True, True, True),
+}
+GemmCase = namedtuple("GemmCase", "M N K tile sk form batch K1", defaults=(1, 0))      # K1 > 0: two-source A, columns [K1, K) from A2
+TnCase = namedtuple("TnCase", "K M N sk form")
+# The call forms: which optional operands are given (NULL or not, and their alignment, are part of the launcher's decision), flags and strides.
+# rowbias = rows_per_batch (32: a 32-row fragment lies in one entry; 24: the per-row lookup of the GENERAL instantiation)
+GEMM_FORM_DEFS = {
+    "bare": dict(), "bias": dict(bias=True), "bias+res": dict(bias=True, residual=True), "full": dict(bias=True, rowbias=32, residual=True),
+    "gelu": dict(gelu=True), "gelu+bias+res": dict(bias=True, gelu=True, residual=True), "general full": dict(bias=True, rowbias=24, gelu=True, residual=True),
+    "rowbias24": dict(rowbias=24),
+    "f32": dict(bias=True, f32=True), "f32 res32": dict(bias=True, residual=True, f32=True, res32=True), "f32 res16": dict(bias=True, residual=True, f32=True),
+    "accum16": dict(accum=True), "accum32": dict(accum=True, f32=True), "alpha": dict(bias=True, alpha=0.5),
+    "rowbias slice": dict(rowbias=32, ldrb=1280),      # a column slice of a wider [rows][1280] matrix
+    "C slice8": dict(bias=True, ldc_pad=8), "C slice4": dict(bias=True, ldc_pad=4), "res slice": dict(residual=True, ldr_pad=16),
+    "colstats": dict(bias=True, colstats=True), "colstats+res": dict(bias=True, residual=True, colstats=True),
+    "gelu C slice4": dict(bias=True, gelu=True, ldc_pad=4),      # the GENERAL instantiation through the scalar store
+    "bias misaligned": dict(bias=True, bias_off=1),      # the bias starts 4 bytes behind a 16-byte boundary: the scalar reduce kernel under split-K
+    "f32 bare": dict(f32=True),                          # fp32 C with nothing in the epilogue: the float4 reduce kernel under split-K
+}
+TN_FORM_DEFS = {"f32": dict(f32=True), "lda": dict(f32=True, lda_pad=8), "C slice": dict(f32=True, ldc_pad=372), "accum": dict(f32=True, accum=True),
+                "alpha": dict(f32=True, alpha=0.5), "bf16": dict()}
+
+
+def _gemm_mnk(hint):
+    """one partial tile beside one full tile (tm + 40 rows, tn + 24 columns; two whole column tiles where the row needs them) and a K of two K-tiles
+    plus the 16-byte granule (whole K-tiles where the row needs them)"""
+    tm, tn, kt, st, whole_k, whole_n, general, tail = GEMM_TILES[hint]
+    return tm + 40, (2 * tn if whole_n else tn + 24), (128 if whole_k else 136)
+
+
+def _kloop_cases():
+    out = []
+    for hint, (tm, tn, kt, st, whole_k, whole_n, general, tail) in GEMM_TILES.items():
+        M, N, _ = _gemm_mnk(hint)
+        Ks = [kt * n for n in sorted({1, 2, 3, st, st + 1, st + 2, st + 3})]      # nkt % stages, nkt < stages: prologue, unrolled body, 1..3-step remainder
+        if not whole_k:
+            Ks += [64 + 8, 64 * st + 40]                                            # a ragged last K-tile: the 16-byte granule, and 40 of 64
+        if kt == 32:
+            Ks += [32 * 2 + 24, 32 * 3 + 16]                                        # ... which both leave 8 of a 32-wide K-tile: 24 and 16 of 32 too
+        for forms in (("bare", "bias+res"),) + ((("gelu", "gelu+bias+res"),) if general else ()):
+            for form in forms:
+                out += [GemmCase(M, N, K, hint, 1, form) for K in Ks]
+                # (splits are counted in 64-wide K-tiles on every row, the 32-wide one included: resolve_launch, ktiles_per_split)
+                out.append(GemmCase(M, N, 320, hint, 2, form))      # 5 K-tiles of 64 in 2 splits: 3 + 2, the last one shorter
+                out.append(GemmCase(M, N, 192, hint, 3, form))      # splitk == nkt: one 64-wide K-tile per split
+    return out
+
+
+def _edge_cases():
+    out = []
+    for hint, (tm, tn, kt, st, whole_k, whole_n, general, tail) in GEMM_TILES.items():
+        M, N, K = _gemm_mnk(hint)
+        cases = [GemmCase(1, N if whole_n else tn + 40, K, hint, 1, "?"), GemmCase(tm - 1, N, K, hint, 1, "?")]      # (M = 1: 40 columns, so that every slice holds >= 32 values)
+        if not whole_n:
+            cases += [GemmCase(M, 8, K, hint, 1, "?"), GemmCase(M, tn + 20, K, hint, 1, "?")]      # N = 8; N % 8 == 4: the scalar store
+        # 10 row tiles x 3 column tiles = 30 tiles: crosses a raster group of group_m = 8 row panels, and the XCD re-deal has a remainder
+        cases.append(GemmCase(9 * tm + 40, 3 * tn if whole_n else 2 * tn + 24, K, hint, 1, "?"))
+        # two-source A: e4t_gemm_nt takes K1 % 64 == 0 only (no row takes another K1: the rejection is reached in gemm_guards); K - K1 = 40 < 64
+        # where the row takes a ragged K
+        cases.append(GemmCase(M, N, 128 if whole_k else 104, hint, 1, "?", 1, 64))
+        if tail:
+            cases += [GemmCase(1152 + r, 320, K if whole_k else 144, hint, 1, "?") for r in (1, 17, 32)]      # the tail stage (it wants K % 16 == 0)
+        out += [c._replace(form=f) for c in cases for f in ("bare", "bias+res")]
+        out += [GemmCase(M, N, K, hint, 1, f, 2) for f in ("bare", "bias")]      # batch 2, ragged M (a residual is not batched: every entry would read the same one)
+    return out
+
+
+GEMM_FORM_FAMILIES = (64, 128, 160, 5256, 512, 2320)      # gemm_dma_kernel at each tile shape, gemm_pp_kernel, gemm_pq_kernel
+_GENERAL_FORMS = ("gelu", "gelu+bias+res", "general full", "rowbias24", "gelu C slice4")
+GEMM_FORM_SPLITK = {"bias+res": "splitk_reduce8_kernel", "bias misaligned": "splitk_reduce_kernel", "f32 bare": "splitk_reduce4f_kernel"}
+
+
+def _form_cases():
+    out = []
+    for hint in GEMM_FORM_FAMILIES:
+        tm, tn, kt, st, whole_k, whole_n, general, tail = GEMM_TILES[hint]
+        M, N, K = _gemm_mnk(hint)
+        for form, f in GEMM_FORM_DEFS.items():
+            if form in _GENERAL_FORMS and not general:      # (the planner's own answer: it sends these to a narrower tile, which has its own row here)
+                continue
+            out.append(GemmCase(tm + 32 if f.get("colstats") else M, N, K, hint, 1, form))      # column statistics: M % 32 == 0
+        out += [GemmCase(M, N, 320, hint, 2, form) for form in GEMM_FORM_SPLITK]
+    out.append(GemmCase(*_gemm_mnk(3064), 3064, 1, "gelu C slice4"))      # (the one GENERAL instantiation that is no family of its own)
+    # the 3- and 4-stage rows share write_tile with their family; the direct fp32 store is the one path the K-loop and edge lists do not take them through
+    return out + [GemmCase(*_gemm_mnk(h), h, 1, "f32 res32") for h in GEMM_TILES if h not in GEMM_FORM_FAMILIES]
+
+
+GEMM_KLOOP_CASES = _kloop_cases()
+GEMM_EDGE_CASES = _edge_cases()
+GEMM_FORMS = _form_cases()
+GEMM_TN_CASES = [
+    TnCase(200, 168, 152, 1, "f32"),       # partial tiles in M and N; 200 rows = 3 K-tiles of 64 + 8
+    TnCase(136, 8, 152, 1, "f32"),         # M = 8
+    TnCase(300, 168, 152, 2, "f32"),       # 5 K-tiles in 2 splits: 3 + 2
+    TnCase(2048, 136, 136, 0, "f32"),      # automatic split-K wants >= 16 K-tiles per split: K = 2048 is the smallest that splits (4 tiles, 2 splits)
+    TnCase(200, 168, 152, 1, "lda"), TnCase(200, 168, 152, 1, "C slice"), TnCase(200, 168, 152, 1, "accum"), TnCase(200, 168, 152, 1, "alpha"),
+    TnCase(200, 168, 152, 1, "bf16"), TnCase(300, 168, 152, 2, "bf16"), TnCase(300, 168, 152, 2, "accum"),
+]
+# gemm_guards: one ragged case per kernel symbol, bare and with the full epilogue, the GENERAL instantiations, the three reduce kernels, two-source A
+GEMM_GUARD_CASES = (
+    [GemmCase(*_gemm_mnk(h), h, 1, f) for h in GEMM_TILES for f in ("bare", "full")] +
+    [GemmCase(*_gemm_mnk(h), h, 1, f) for h, t in GEMM_TILES.items() if t[6] for f in ("gelu", "general full")] +
+    [GemmCase(104, 88, 320, 64, 2, f) for f in ("full", "bias misaligned", "f32 bare")] +
+    [GemmCase(104, 88, 104, 64, 1, "full", 1, 64), GemmCase(296, 280, 128, 512, 1, "full", 1, 64)] +
+    [GemmCase(1152 + 17, 320, 144, 160, 1, "bias+res")])
+GEMM_AUTO_SPLIT_CASES = [GemmCase(104, 88, 2048, 64, 0, "bias+res"), TnCase(2048, 136, 136, 0, "f32")]      # the smallest K at which the automatic rule splits
+GEMM_TN_GUARD_CASES = [TnCase(200, 168, 152, 1, "f32"), TnCase(300, 168, 152, 2, "f32"), TnCase(300, 168, 152, 2, "bf16")]
+# fp32 output and TN against float64: 8 x the worst row a float32 restatement (float32 matmul, epilogue in float32) reaches against float64 over all
+# fp32 and TN cases on the CPU (tests/test_gemm_slices_cpu.py measures it: GEMM_F32_WORST); the margin covers the MFMA's summation order and the
+# split-K partial sums.  Never above the TOLF * 50 the existing fp32 rows use.
+GEMM_F32_WORST = 1.3e-7      # measured 1.273e-7: gemm 104x88x320 t64 s2 f32 bare, rows 64-103
+TOL_GEMM_F32 = min(8 * GEMM_F32_WORST, TOLF * 50)
+GEMM_GUARD = 320      # NaN / sentinel rows in front of and behind every operand: the widest column tile (rows of B behind N), more than the tallest row tile
+
+
+def gemm_tag(c):
+    if isinstance(c, TnCase):
+        return f"gemm_tn K{c.K} M{c.M} N{c.N} s{c.sk} {c.form}"
+    return f"gemm {c.M}x{c.N}x{c.K} t{c.tile} s{c.sk} {c.form}" + (f" batch{c.batch}" if c.batch > 1 else "") + (f" K1={c.K1}" if c.K1 else "")
+
+
+def gemm_form(c):
+    return TN_FORM_DEFS[c.form] if isinstance(c, TnCase) else GEMM_FORM_DEFS[c.form] if c.form in GEMM_FORM_DEFS else CHECK_GEMM_FORM_DEFS[c.form]
+
+
+def gemm_layout(c, guarded=False):
+    """leading dimensions and row counts of every operand of a case; guarded: 8 more elements per row of A, A2 and B (the `lda > K` gap), of C (the
+    `ldc - N` gap columns, which hold sentinels) and of the residual — a pad of 8 keeps every 16-byte alignment, so kernel and store path stay"""
+    f, pad = gemm_form(c), 8 if guarded else 0
+    if isinstance(c, TnCase):
+        return dict(lda=c.M + f.get("lda_pad", 0) + pad, ldb=c.N + pad, ldc=c.N + f.get("ldc_pad", 0) + pad, K1=c.K, lda2=0, ldr=0, ldrb=0, rb_rows=0)
+    K1 = c.K1 or c.K
+    rpb = f.get("rowbias", 0)
+    return dict(lda=K1 + pad, lda2=(c.K - K1 + pad) if c.K1 else 0, ldb=c.K + pad, ldc=c.N + f.get("ldc_pad", 0) + pad, K1=K1,
+                ldr=(c.N + f.get("ldr_pad", 0) + pad) if f.get("residual") else 0, ldrb=f.get("ldrb", c.N) if rpb else 0, rb_rows=-(-c.M // rpb) if rpb else 0)
+
+
+def gemm_flags(c):
+    from e4t import _C
+    f = gemm_form(c)
+    return ((_C.OUT_F32 if f.get("f32") else 0) | (_C.RES_F32 if f.get("res32") else 0) | (_C.ACT_GELU if f.get("gelu") else 0) | (_C.ACCUM if f.get("accum") else 0))
+
+
+def gemm_desc(c, ptrs=None, guarded=False, ws=None, ws_bytes=None, splitk=None):
+    """the descriptor of a case.  ptrs = None: pointers that are never dereferenced, with the alignment the real operands have, and a workspace that
+    is large enough — for e4t_gemm_plan / e4t_gemm_kernel / e4t_gemm_tn_kernel (pure host code)"""
+    from e4t import _C
+    f, L, fake = gemm_form(c), gemm_layout(c, guarded), 1 << 24
+    tn = isinstance(c, TnCase)
+    if ptrs is None:
+        used = dict(A=True, B=True, C=True, A2=not tn and c.K1, bias=f.get("bias"), residual=f.get("residual"), rowbias=f.get("rowbias"),
+                    colstats=f.get("colstats"))
+        ptrs = {k: fake for k, v in used.items() if v}
+        if f.get("bias_off"):
+            ptrs["bias"] = fake + 4 * f["bias_off"]
+        ws, ws_bytes = (fake, 1 << 40) if ws_bytes is None else (ws, ws_bytes)
+    batch = 1 if tn else c.batch
+    d = _C.GemmDesc(M=c.M, N=c.N, K=c.K, K1=L["K1"], lda=L["lda"], lda2=L["lda2"], ldb=L["ldb"], ldc=L["ldc"], ldr=L["ldr"], ldrb=L["ldrb"],
+                    rows_per_batch=f.get("rowbias", 0), flags=gemm_flags(c), tile=0 if tn else c.tile, splitk=c.sk if splitk is None else splitk, batch=batch,
+                    alpha=f.get("alpha", 1.0), workspace=ws, workspace_bytes=ws_bytes or 0)
+    if batch > 1:
+        d.strideA, d.strideB, d.strideC = c.M * L["lda"], c.N * L["ldb"], c.M * L["ldc"]
+    for k, v in ptrs.items():
+        setattr(d, k, v)
+    return d
+
+
+# call forms of check_gemm that GEMM_FORMS does not run as such
+CHECK_GEMM_FORM_DEFS = {"gelu+bias": dict(bias=True, gelu=True), "gelu f32": dict(gelu=True, f32=True), "accum32 alpha": dict(accum=True, f32=True, alpha=0.5),
+                        "rowbias96": dict(rowbias=96), "rowbias97": dict(rowbias=97)}
+
+
+def check_gemm_pinned():
+    """every launch of check_gemm as (label, case, descriptor fields set last): what hip.gemm / hip.gemm_tn hand the library for it, from the same
+    shape lists, for tests/test_gemm_dispatch.py to pin (the row labels of check_gemm where one launch makes one row)"""
+    from e4t import _C
+    out = [(f"gemm {M}x{N}x{K} t{t} s{sk} bias+res", GemmCase(M, N, K, t, sk, "bias+res"), {}) for M, N, K, t, sk in CHECK_GEMM_NT]
+    out += [(f"gemm_tn K{K} M{M} N{N} s{sk}", TnCase(K, M, N, sk, "lda"), {}) for K, M, N, sk in CHECK_GEMM_TN]
+    out += [("gemm_tn fp32 accumulate", TnCase(500, 320, 328, 0, "accum"), {}), ("gemm_tn into a column slice", TnCase(500, 320, 328, 0, "C slice"), {})]
+    out += [(f"gemm {M}x{N}x{K} t{t} colstats" + (" + residual" if i % 2 == 0 else ""), GemmCase(M, N, K, t, 1, "colstats+res" if i % 2 == 0 else "colstats"), {})
+            for i, (M, N, K, t) in enumerate(CHECK_GEMM_COLSTATS)]
+    out += [("gemm two-source A" + (f" t{t}" if t else ""), GemmCase(384, 192, 192, t, 0, "bare", 1, 128), {}) for t in (0, 512, 3064, 2320)]
+    out += [("gemm gelu" + (f" t{t}" if t else ""), GemmCase(384, 192, 128, t, 0, "gelu"), {}) for t in (0, 3064, 512, 2320)]
+    out += [("gemm gelu fp32-out t512", GemmCase(384, 192, 128, 512, 0, "gelu f32"), {}), ("gemm fp32 out + accumulate + alpha", GemmCase(384, 192, 128, 0, 0, "accum32 alpha"), {}),
+            ("gemm rowbias", GemmCase(384, 192, 128, 0, 0, "rowbias96"), {}), ("gemm strided A view", GemmCase(384, 192, 128, 0, 0, "bare"), dict(lda=384))]
+    for M, N, K, kw in CHECK_GEMM_TAIL:
+        form = "f32 res32" if kw.get("f32") else "gelu+bias" if kw.get("gelu") else "bias+res" if kw.get("res") else "bias"
+        out.append((f"gemm {M}x{N}x{K} tail {form}", GemmCase(M, N, K, 0, 0, form), {}))
+    out += [(f"gemm {M}x{N}x{K} t{t} fp32 out + fp32 residual", GemmCase(M, N, K, t, 0, "f32 res32"), {}) for M, N, K, t in CHECK_GEMM_F32RES]
+    for M, N, K in CHECK_GEMM_PQ_GENERAL:
+        out.append((f"gemm {M}x{N}x{K} t2320 gelu", GemmCase(M, N, K, 2320, 0, "gelu+bias"), {}))
+        out.append((f"gemm {M // 97 * 97}x{N}x{K} t2320 row bias, rows_per_batch 97", GemmCase(M // 97 * 97, N, K, 2320, 0, "rowbias97"), {}))
+    for B, T, N, K, pr, dt in CHECK_GEMM_PANELS:
+        out.append((f"gemm row panels B{B} T{T} N{N} K{K}", GemmCase(B * pr, N, K, 0, 0, "gelu+bias" if dt == bf16 else "f32 res32"), dict(panel_rows=pr, panel_stride=T, panel_off=T - pr)))
+    out += [("gemm batched", GemmCase(16, 128, 128, 0, 0, "bias", 9), dict(strideBias=128)),
+            ("gemm batched reduce (mean over slots)", GemmCase(16, 128, 128, 0, 0, "f32 bare", 9), dict(flags=_C.OUT_F32 | _C.REDUCE_BATCH, alpha=1.0 / 9, strideC=0)),
+            ("gemm batched broadcast A", GemmCase(16, 128, 128, 0, 0, "bare", 9), dict(strideA=0))]
+    out += [(f"gemm batched t{t}", GemmCase(300, 320, 128, t, 0, "bias", 2), dict(strideBias=320)) for t in (512, 2320)]
+    return out
+
+
+def check_gemm_logged(hip, emu, dev):
+    """check_gemm with the launch log on, plus one row that ties check_gemm_pinned() to it: the "<symbol>|<shape string>" of every GEMM / TN launch
+    the log shows == those the pinned descriptors give (symbol and split-K from e4t_gemm_kernel / e4t_gemm_tn_kernel, shape, batch and flags from the
+    descriptor), as sets (CHECK_GEMM_COLSTATS runs one shape twice).  A check_gemm call or an ops.gemm change that the restatement misses fails here."""
+    import os
+    import tempfile
+    fd, path = tempfile.mkstemp(suffix=".launchlog")
+    os.close(fd)
+    try:
+        assert hip.lib.e4t_set_launch_log(path.encode()) == 0
+        try:
+            out = check_gemm(hip, emu, dev)
+            torch.cuda.synchronize()
+        finally:
+            hip.lib.e4t_set_launch_log(None)
+        with open(path) as f:
+            logged = {"|".join(l.split("|")[:2]) for l in f.read().splitlines() if "|gemm M" in l or "|gemm_tn M" in l}
+    finally:
+        os.unlink(path)
+    want = set()
+    for label, c, override in check_gemm_pinned():
+        d = gemm_desc(c)
+        for k, v in override.items():
+            setattr(d, k, v)
+        rc, k = gemm_kernel(c, d)
+        if isinstance(c, TnCase):
+            want.add(f"{k.symbol.decode()}|gemm_tn M{c.M} N{c.N} K{c.K} splitk{k.splitk} flags{d.flags}")
+        else:
+            want.add(f"{k.symbol.decode()}|gemm M{c.M} N{c.N} K{c.K} batch{c.batch} splitk{k.splitk} flags{d.flags}")
+    diff = sorted(logged ^ want)
+    return out + [(f"check_gemm's launch log == the pinned descriptors of check_gemm_pinned() ({len(logged)} distinct launches; differing: {diff[:6]})", float(len(diff)), 0.0)]
+
+
+def gemm_plan(c, **kw):
+    import ctypes
+    from e4t import _C
+    pl = _C.GemmPlan()
+    fn = _C.load().e4t_gemm_tn_plan if isinstance(c, TnCase) else _C.load().e4t_gemm_plan
+    _C.check(fn(ctypes.byref(gemm_desc(c, **kw)), ctypes.byref(pl)), "e4t_gemm_plan")
+    return pl
+
+
+def gemm_kernel(c, d=None):
+    """the launcher's own decision for a case (e4t_gemm_kernel / e4t_gemm_tn_kernel) -> (rc, e4t_gemm_kernel_t)"""
+    import ctypes
+    from e4t import _C
+    k = _C.GemmKernel()
+    fn = _C.load().e4t_gemm_tn_kernel if isinstance(c, TnCase) else _C.load().e4t_gemm_kernel
+    return fn(ctypes.byref(d if d is not None else gemm_desc(c)), ctypes.byref(k)), k
+
+
+def gemm_kernel_text(k):
+    """'<symbol> splitk<n> <store path> [<reduce symbol>] [tail<r>]' in clear text"""
+    from e4t import _C
+    return " ".join([f"{k.symbol.decode()} splitk{k.splitk} {_C.STORE_NAMES[k.store]}"] + ([k.reduce.decode()] if k.reduce else []) +
+                    ([f"tail{k.tail_rows}"] if k.tail_rows else []))
+
+
+def gemm_values(c, seed, dev):
+    """dense values of every operand of a case: unit-variance product, bias, row bias, residual and (accumulate) initial C"""
+    g, f = gen(seed, dev), gemm_form(c)
+    out_dt = f32 if f.get("f32") else bf16
+    if isinstance(c, TnCase):
+        v = dict(a=rnd(g, c.K, c.M, dev=dev), b=rnd(g, c.K, c.N, scale=c.K ** -0.5, dev=dev))
+        rows = c.M
+    else:
+        K1, rows = c.K1 or c.K, c.batch * c.M
+        v = dict(a=rnd(g, rows, K1, dev=dev), b=rnd(g, c.batch * c.N, c.K, scale=c.K ** -0.5, dev=dev))
+        if c.K1:
+            v["a2"] = rnd(g, rows, c.K - K1, dev=dev)
+    if f.get("bias"):
+        v["bias"] = rnd(g, c.N, dtype=f32, dev=dev)
+    if f.get("rowbias"):
+        v["rowbias"] = rnd(g, -(-c.M // f["rowbias"]), c.N, dtype=f32, dev=dev)
+    if f.get("residual"):
+        v["residual"] = rnd(g, rows, c.N, dtype=f32 if f.get("res32") else bf16, dev=dev)
+    if f.get("accum"):
+        v["c0"] = rnd(g, rows, c.N, dtype=out_dt, dev=dev)
+    return v
+
+
+def _gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x * (0.5 ** 0.5)))
+
+
+def gemm_ref64(c, v, store, tail=0):
+    """float64 restatement of the descriptor's semantics from the bf16 inputs -> [batch * M, N], BEFORE the rounding to the output type.  Rounding
+    points as write_tile states them: alpha, bias, row bias and GELU are applied before any rounding; the LDS-staged bf16 path (store ==
+    'bf16-staged') rounds that value to bf16, adds the residual to the ROUNDED value and rounds again; every other path (scalar store, fp32 direct,
+    the reduce kernels, the tail rows) adds residual and (accumulate) the old C first and rounds once."""
+    f64 = torch.float64
+    f = gemm_form(c)
+    if isinstance(c, TnCase):
+        y = v["a"].to(f64).t() @ v["b"].to(f64)
+    else:
+        a = torch.cat([v["a"], v["a2"]], dim=1) if c.K1 else v["a"]
+        y = torch.cat([a[i * c.M:(i + 1) * c.M].to(f64) @ v["b"][i * c.N:(i + 1) * c.N].to(f64).t() for i in range(c.batch)])
+    y = y * f.get("alpha", 1.0)
+    if "bias" in v:
+        y = y + v["bias"].to(f64)
+    if "rowbias" in v:
+        y = y + v["rowbias"].to(f64).repeat_interleave(f["rowbias"], dim=0)[:c.M]
+    if f.get("gelu"):
+        y = _gelu64(y)
+    if "residual" in v:
+        if store == "bf16-staged":
+            main = y.shape[0] - tail
+            y = torch.cat([y[:main].to(f32).to(bf16).to(f64), y[main:]])
+        y = y + v["residual"].to(f64)
+    if "c0" in v:
+        y = y + v["c0"].to(f64)
+    return y
+
+
+def gemm_slices(tag, got, ref, plan, batch=1, tol=TOL1):
+    """Result rows that one whole-matrix relative L2 dilutes: got, ref = [batch * M, N] (ref float64).  The relative L2 of the whole matrix, the first
+    row tile and the last, partial one, the first and the last column tile, the corner block of the last row tile x the last column tile, the interior
+    (everything else), the tail rows and the 64 rows in front of them, and the first and last batch entry.  Empty and duplicate regions are skipped.
+    The tolerance is the whole matrix's: the stated bound is per element (tests/test_gemm_slices_cpu.py holds a rounding-only model to half of it on
+    every row emitted here, down to 32 values)."""
+    f64 = torch.float64
+    N = ref.shape[-1]
+    M = ref.shape[0] // batch
+    g, r = got.to(f64).reshape(batch, M, N), ref.to(f64).reshape(batch, M, N)
+    d2, r2 = (g - r) ** 2, r * r
+    tm, tn, tail = plan.tile_m, plan.tile_n, plan.tail_rows
+    Mg = M - tail                                     # rows of the tile grid
+    r_last = (Mg - 1) // tm * tm                      # first row of the last row tile, first column of the last column tile
+    c_last = (N - 1) // tn * tn
+    out, seen = [], set()
+
+    def row(label, rs, cs, bs=slice(None)):
+        key = (rs.indices(M), cs.indices(N), bs.indices(batch))
+        d, n = d2[bs, rs, cs], r2[bs, rs, cs]
+        if d.numel() and key not in seen:
+            seen.add(key)
+            e = (d.sum() / (n.sum() + 1e-300)).sqrt()
+            out.append((f"{tag}: {label}", float(torch.nan_to_num(e, nan=float("inf"))), tol))
+    A = slice(None)
+    row("whole", A, A)
+    row(f"rows 0-{min(tm, Mg) - 1} (the first row tile)", slice(0, min(tm, Mg)), A)
+    row(f"rows {r_last}-{Mg - 1} (the last row tile)", slice(r_last, Mg), A)
+    row(f"columns 0-{min(tn, N) - 1} (the first column tile)", A, slice(0, min(tn, N)))
+    row(f"columns {c_last}-{N - 1} (the last column tile)", A, slice(c_last, N))
+    row("corner (last row tile x last column tile)", slice(r_last, Mg), slice(c_last, N))
+    row("interior", slice(tm, r_last), slice(tn, c_last))
+    if tail:
+        row(f"the {tail} tail rows", slice(Mg, M), A)
+        row("the 64 rows in front of the tail", slice(Mg - 64, Mg), A)
+    if batch > 1:
+        row("batch entry 0", A, A, slice(0, 1))
+        row(f"batch entry {batch - 1}", A, A, slice(batch - 1, batch))
+    return out
+
+
+class _GemmOperands:
+    """every operand of a case as a view into a larger allocation the test owns.  guard = 0: dense, nothing around them.  guard > 0: NaN rows in
+    front of and behind A, A2, B, bias, row bias and residual, NaN in the 8-element gap behind every row of A, A2, B and the residual, sentinel rows
+    around C and the column statistics, sentinels in the 8 gap columns behind every row of C (gemm_layout)."""
+
+    def __init__(self, c, v, dev, guard=0):
+        self.c, self.guard, self.dev = c, guard, dev
+        f, L = gemm_form(c), gemm_layout(c, guard > 0)
+        self.f, self.L, self.tn = f, L, isinstance(c, TnCase)
+        self.ptrs, self.keep = {}, []
+        nan = float("nan")
+        self.ptrs["A"] = self._inp(v["a"], L["lda"], nan)
+        self.ptrs["B"] = self._inp(v["b"], L["ldb"], nan)
+        if "a2" in v:
+            self.ptrs["A2"] = self._inp(v["a2"], L["lda2"], nan)
+        if "bias" in v:
+            off = f.get("bias_off", 0)
+            buf = torch.full((guard + off + c.N + guard,), nan, dtype=f32, device=dev)
+            buf[guard + off:guard + off + c.N] = v["bias"]
+            self.keep.append(buf)
+            self.ptrs["bias"] = buf[guard + off:].data_ptr()
+        if "rowbias" in v:
+            self.ptrs["rowbias"] = self._inp(v["rowbias"], L["ldrb"], nan)
+        if "residual" in v:
+            self.ptrs["residual"] = self._inp(v["residual"], L["ldr"], nan)
+        rows = c.M if self.tn else c.batch * c.M
+        self.out_dt = f32 if f.get("f32") else bf16
+        w16 = L["ldc"] * (2 if self.out_dt == f32 else 1)
+        self.cbuf = torch.full((guard + rows + guard, w16), SENT16, dtype=torch.int16, device=dev)
+        self.C = self.cbuf[guard:guard + rows].view(self.out_dt)[:, :c.N]
+        if "c0" in v:
+            self.C.copy_(v["c0"])
+        self.ptrs["C"] = self.C.data_ptr()
+        self.cs = None
+        if f.get("colstats"):
+            n = (c.M // 32) * c.N * 2
+            self.csbuf = torch.full((guard * 8 + n + guard * 8,), SENT32, dtype=torch.int32, device=dev)
+            self.cs = self.csbuf[guard * 8:guard * 8 + n].view(f32).view(c.M // 32, c.N, 2)
+            self.ptrs["colstats"] = self.cs.data_ptr()
+        self.c_before = self.cbuf.clone()
+
+    def _inp(self, t, ld, fill):
+        rows, cols = t.shape
+        buf = torch.full((self.guard + rows + self.guard, ld), fill, dtype=t.dtype, device=self.dev)
+        buf[self.guard:self.guard + rows, :cols] = t
+        self.keep.append(buf)
+        return buf[self.guard:].data_ptr()
+
+    def sentinels_changed(self):
+        """elements outside C[:, :N] (guard rows, gap columns) and around the column statistics that changed"""
+        ch = self.cbuf != self.c_before
+        rows = self.C.shape[0]
+        ch[self.guard:self.guard + rows, :self.c.N * (2 if self.out_dt == f32 else 1)] = False      # (cbuf is int16: an fp32 element is two of its columns)
+        n = int(ch.sum())
+        if self.cs is not None and self.guard:
+            g8 = self.guard * 8
+            n += int((self.csbuf[:g8] != SENT32).sum()) + int((self.csbuf[g8 + self.cs.numel():] != SENT32).sum())
+        return n
+
+    def c_touched(self):
+        """elements of the whole C allocation, C included, that changed (a rejected call must leave 0)"""
+        return int((self.cbuf != self.c_before).sum())
+
+
+def gemm_launch(hip, c, ops, ws="plan", splitk=None, override=None, only_if_refused=False):
+    """one launch of a case through the raw ABI on placed operands `ops` -> (rc, e4t_gemm_kernel_t of the same descriptor, workspace).  ws: 'plan' = exactly
+    the plan's workspace_bytes (sentinels behind it), 'short' = one float less, 'none'.  override: descriptor fields set last."""
+    import ctypes
+    from e4t.ops import _stream
+    tn = isinstance(c, TnCase)
+    d = gemm_desc(c, ptrs=ops.ptrs, guarded=ops.guard > 0, ws=None, ws_bytes=0, splitk=splitk)
+    for k, val in (override or {}).items():
+        setattr(d, k, val)
+    pl = _Cmod().GemmPlan()
+    rc = (hip.lib.e4t_gemm_tn_plan if tn else hip.lib.e4t_gemm_plan)(ctypes.byref(d), ctypes.byref(pl))
+    w = None
+    if rc == 0 and ws != "none" and pl.workspace_bytes:
+        w = _Workspace(pl.workspace_bytes - (4 if ws == "short" else 0), ops.dev)
+        d.workspace, d.workspace_bytes = w.ptr, w.bytes
+    rcq, k = gemm_kernel(c, d)
+    if only_if_refused and rcq >= 0:      # a descriptor that is meant to be refused is never launched: the query makes the launch's own checks
+        return 0, rcq, k, w, pl
+    rc = (hip.lib.e4t_gemm_tn if tn else hip.lib.e4t_gemm_nt)(ctypes.byref(d), _stream())
+    return rc, rcq, k, w, pl
+
+
+def _Cmod():
+    from e4t import _C
+    return _C
+
+
+def _gemm_case_rows(hip, c, seed, dev, tol_f32=None):
+    """one case: launch, float64 reference with the store path's rounding points, slices"""
+    f = gemm_form(c)
+    v = gemm_values(c, seed, dev)
+    ops = _GemmOperands(c, v, dev)
+    rc, rcq, k, w, pl = gemm_launch(hip, c, ops)
+    tag = gemm_tag(c)
+    if rc < 0 or rcq != 0:
+        return [(f"{tag}: launch rc {rc}, query rc {rcq} ({_last_error(hip.lib)})", 1.0, 0.0)]
+    store = _Cmod().STORE_NAMES[k.store]
+    ref = gemm_ref64(c, v, store, k.tail_rows)
+    tol = TOL_GEMM_F32 if f.get("f32") else TOL1
+    batch = 1 if isinstance(c, TnCase) else c.batch
+    out = gemm_slices(f"{tag} [{gemm_kernel_text(k)}]", ops.C, ref, pl, batch, tol)
+    if ops.L["ldc"] > c.N:
+        out.append((f"{tag}: sentinels in the {ops.L['ldc'] - c.N} gap columns of C changed", float(ops.sentinels_changed()), 0.0))
+    if f.get("colstats"):
+        y = ops.C.float().reshape(c.M // 32, 32, c.N)
+        want = torch.stack([y.sum(1), (y * y).sum(1)], dim=-1)
+        out.append((f"{tag} colstats: reported written (1 = not)", float(rc != 1 or not k.colstats), 0.0))
+        out.append((f"{tag} colstats: == the statistics of the kernel's own output", rel(ops.cs, want) if rc == 1 else 1.0, 1e-5))
+    return out
+
+
+def check_gemm_kloop(hip, emu, dev):
+    """every DMA row of the variant table crossed with the K-loop's code paths (GEMM_KLOOP_CASES), bare and bias + residual, in slices"""
+    return [r for i, c in enumerate(GEMM_KLOOP_CASES) for r in _gemm_case_rows(hip, c, 5000 + i, dev)]
+
+
+def check_gemm_edges(hip, emu, dev):
+    """M = 1, M = tile - 1, N = 8, N % 8 == 4, more than one raster group, two-source A, batch, the tail stage, on every kernel row; the TN kernel"""
+    return [r for i, c in enumerate(GEMM_EDGE_CASES + GEMM_TN_CASES) for r in _gemm_case_rows(hip, c, 6000 + i, dev)]
+
+
+def check_gemm_forms(hip, emu, dev):
+    """every call form on one case per kernel family (GEMM_FORMS); column statistics as check_conv_forms checks them"""
+    return [r for i, c in enumerate(GEMM_FORMS) for r in _gemm_case_rows(hip, c, 7000 + i, dev)]
+
+
+def _gemm_guard_rows(hip, c, seed, dev):
+    tag = gemm_tag(c) + ", guarded"
+    v = gemm_values(c, seed, dev)
+    plain, guarded = _GemmOperands(c, v, dev), _GemmOperands(c, v, dev, GEMM_GUARD)
+    rc0, _, k0, _, _ = gemm_launch(hip, c, plain)
+    rc1, rcq, k1, w, pl = gemm_launch(hip, c, guarded)
+    if rc0 < 0 or rc1 < 0 or rcq != 0:
+        return [(f"{tag}: launch rc {rc0} / {rc1}, query rc {rcq} ({_last_error(hip.lib)})", 1.0, 0.0)]
+    bits = lambda t: t.contiguous().view(torch.int16)
+    out = [(f"{tag}: the guarded run takes another kernel ({gemm_kernel_text(k0)} / {gemm_kernel_text(k1)})", float(gemm_kernel_text(k0) != gemm_kernel_text(k1)), 0.0),
+           (f"{tag} [{gemm_kernel_text(k1)}]: elements differing from the unguarded run", float((bits(guarded.C) != bits(plain.C)).sum()), 0.0),
+           (f"{tag}: non-finite elements", float((~torch.isfinite(guarded.C.float())).sum()), 0.0),
+           (f"{tag}: sentinel elements changed (rows around C, the {guarded.L['ldc'] - c.N} gap columns of every row)", float(guarded.sentinels_changed()), 0.0)]
+    if w is not None:
+        out.append((f"{tag}: sentinels behind the {w.bytes}-byte workspace changed", float(w.outside()), 0.0))
+    if guarded.cs is not None:
+        out.append((f"{tag}: column statistics differing from the unguarded run", float((guarded.cs != plain.cs).sum()), 0.0))
+    return out
+
+
+def _gemm_short_workspace_rows(hip, c, seed, dev):
+    """one float less than the plan's workspace: -12 with an explicit split (C untouched); in auto mode one pass that is bitwise the splitk = 1 run"""
+    tag, v = gemm_tag(c), gemm_values(c, seed, dev)
+    ops = _GemmOperands(c, v, dev, GEMM_GUARD)
+    rc, rcq, k, w, pl = gemm_launch(hip, c, ops, ws="short", only_if_refused=True)
+    out = [(f"{tag}: one float less of workspace, explicit split-K: launch rc {rc}, query rc {rcq}, want -12", float(rc != -12 or rcq != -12), 0.0),
+           (f"{tag}: ... leaves C untouched", float(ops.c_touched()), 0.0)]
+    return out
+
+
+def _gemm_rejection_rows(hip, dev):
+    """each argument rejection of e4t_gemm_nt / e4t_gemm_tn once: its code, the query agrees, C untouched"""
+    out = []
+    c = GemmCase(104, 88, 136, 64, 1, "full")
+    t = TnCase(200, 168, 152, 1, "f32")
+    v, vt = gemm_values(c, 8900, dev), gemm_values(t, 8901, dev)
+    two = GemmCase(104, 88, 104, 64, 1, "full", 1, 64)
+    v2 = gemm_values(two, 8902, dev)
+    pan = GemmCase(512, 320, 128, 2320, 1, "bare")
+    vp = gemm_values(pan, 8903, dev)
+    nt = [("null A", c, v, dict(A=None), "null operand"), ("M = 0", c, v, dict(M=0), "bad shape"), ("K % 8 != 0", c, v, dict(K=132), "multiples of 8"),
+          ("lda % 8 != 0", c, v, dict(lda=140), "multiples of 8"), ("ldb % 8 != 0", c, v, dict(ldb=140), "multiples of 8"),
+          ("misaligned A", c, v, "A+2", "16-B aligned"), ("misaligned B", c, v, "B+2", "16-B aligned"),
+          ("K1 % 64 != 0", two, v2, dict(K1=40), "two-source A"), ("K1 = 0", two, v2, dict(K1=0), "two-source A"), ("K1 >= K", two, v2, dict(K1=128), "two-source A"),
+          ("misaligned A2", two, v2, "A2+2", "two-source A"), ("lda2 % 8 != 0", two, v2, dict(lda2=44), "two-source A"),
+          ("row bias without rows_per_batch", c, v, dict(rows_per_batch=0), "rowbias needs rows_per_batch"),
+          ("batch stride % 8 != 0", c, v, dict(batch=2, strideA=104 * 136 + 4, strideB=0, strideC=0), "batch strides"),
+          ("reduce-batch with two-source A", two, v2, dict(flags=16 | 1, batch=2), "reduce-batch with two-source A"),
+          ("panel_rows % 256 != 0", pan, vp, dict(panel_rows=128, panel_stride=128), "panel_rows %% 256"),
+          ("row panels with split-K", pan, vp, dict(panel_rows=256, panel_stride=256, splitk=2), "do not combine"),
+          ("row panels on a tile without them", pan, vp, dict(panel_rows=256, panel_stride=256, N=88), "the plan chose tile"),
+          ("fused GEGLU without aux", c, v, dict(flags=32), "need aux")]
+    tnr = [("null B", t, vt, dict(B=None), "null operand"), ("batch 2", t, vt, dict(batch=2), "bad / unsupported"), ("GELU", t, vt, dict(flags=1 | 4), "not built for the TN kernel"),
+           ("M % 8 != 0", t, vt, dict(M=164), "multiples of 8"), ("N % 8 != 0", t, vt, dict(N=148), "multiples of 8"), ("lda % 8 != 0", t, vt, dict(lda=172), "multiples of 8"),
+           ("misaligned A", t, vt, "A+2", "multiples of 8"),
+           ("operands beyond 4 GB", t, vt, dict(lda=12000000), "beyond 4 GB")]      # (199 rows of 12e6 elements; refused before anything is launched or read)
+    for what, case, vals, ov, says in nt + tnr:
+        ops = _GemmOperands(case, vals, dev, GEMM_GUARD)
+        if isinstance(ov, str):
+            ov = {ov[:-2]: ops.ptrs[ov[:-2]] + 2}
+        rc, rcq, k, w, pl = gemm_launch(hip, case, ops, override=ov, only_if_refused=True)
+        msg = _last_error(hip.lib)
+        fn = "e4t_gemm_tn" if isinstance(case, TnCase) else "e4t_gemm_nt"
+        out.append((f"{fn} rejects {what}: launch rc {rc}, query rc {rcq}, want -22 and '{says.replace('%%', '%')}' in the message ({msg})",
+                    float(rc != -22 or rcq != -22 or says.replace("%%", "%") not in msg), 0.0))
+        out.append((f"{fn} rejects {what}: C untouched", float(ops.c_touched()), 0.0))
+    return out
+
+
+def check_gemm_guards(hip, emu, dev):
+    """every GEMM kernel symbol, the reduce kernels and the TN kernel on operands with poison around and between them (GEMM_GUARD_CASES): bitwise the
+    unguarded run, finite, no sentinel changed; the workspace is exactly the plan's; one float less; row panels; every argument rejection"""
+    out = []
+    cases = GEMM_GUARD_CASES + GEMM_TN_GUARD_CASES
+    for i, c in enumerate(cases):
+        out += _gemm_guard_rows(hip, c, 8000 + i, dev)
+    for i, c in enumerate([x for x in cases if x.sk > 1]):
+        out += _gemm_short_workspace_rows(hip, c, 8500 + i, dev)
+    # automatic split-K (the smallest shapes whose plan splits) with one float less: one pass, bitwise the splitk = 1 run
+    for i, c in enumerate(GEMM_AUTO_SPLIT_CASES):
+        v = gemm_values(c, 8600 + i, dev)
+        one, short = _GemmOperands(c, v, dev), _GemmOperands(c, v, dev, GEMM_GUARD)
+        rc0, _, k0, _, _ = gemm_launch(hip, c, one, splitk=1)
+        rc1, rcq, k1, w, pl = gemm_launch(hip, c, short, ws="short")
+        tag = gemm_tag(c)
+        out.append((f"{tag}: the plan splits (split-K {pl.splitk}); one float less of workspace runs one pass (query: split-K {k1.splitk}, rc {rc1} / {rcq})",
+                    float(pl.splitk <= 1 or rc1 < 0 or rcq != 0 or k1.splitk != 1 or k1.reduce is not None), 0.0))
+        out.append((f"{tag}: ... bitwise the splitk = 1 run", float((short.C.contiguous().view(torch.int16) != one.C.contiguous().view(torch.int16)).sum()), 0.0))
+        out.append((f"{tag}: ... sentinels changed", float(short.sentinels_changed() + (w.outside() if w else 0)), 0.0))
+    # row panels: the rows between the panels (and around them) stay untouched
+    pr, T, nb, N, K = 256, 257, 3, 320, 64
+    c = GemmCase(nb * pr, N, K, 2320, 1, "bias")
+    v = gemm_values(c, 8700, dev)
+    g = gen(8701, dev)
+    a_all = rnd(g, nb * T, K, dev=dev)
+    y = torch.full((GEMM_GUARD + nb * T + GEMM_GUARD, N), SENT16, dtype=torch.int16, device=dev)
+    yv = y[GEMM_GUARD:GEMM_GUARD + nb * T].view(bf16)
+    hip.gemm(a_all, v["b"], bias=v["bias"], out=yv, panels=(pr, T, T - pr, nb))
+    inside = torch.arange(nb * T, device=dev).remainder(T) >= T - pr
+    ref = a_all[inside].to(torch.float64) @ v["b"].to(torch.float64).t() + v["bias"].to(torch.float64)
+    out.append((f"gemm row panels B{nb} T{T} N{N} K{K}: the panel rows", float(((yv[inside].to(torch.float64) - ref).norm() / ref.norm())), TOL1))
+    y16 = y.clone()
+    y16[GEMM_GUARD:GEMM_GUARD + nb * T][inside] = SENT16
+    out.append((f"gemm row panels B{nb} T{T}: rows outside the panels and sentinel rows changed", float((y16 != SENT16).sum()), 0.0))
+    return out + _gemm_rejection_rows(hip, dev)
+
+
 def all_checks(hip, emu, dev, ops_mod):
     yield "gemm_races", lambda: check_gemm_races(hip, emu, dev)
     yield "probe", lambda: check_probe(hip, emu, dev)
-    yield "gemm", lambda: check_gemm(hip, emu, dev)
+    yield "gemm", lambda: check_gemm_logged(hip, emu, dev)
+    yield "gemm_kloop", lambda: check_gemm_kloop(hip, emu, dev)
+    yield "gemm_edges", lambda: check_gemm_edges(hip, emu, dev)
+    yield "gemm_forms", lambda: check_gemm_forms(hip, emu, dev)
+    yield "gemm_guards", lambda: check_gemm_guards(hip, emu, dev)
     yield "conv", lambda: check_conv(hip, emu, dev)
     yield "conv_forms", lambda: check_conv_forms(hip, emu, dev)
     yield "conv_guards", lambda: check_conv_guards(hip, emu, dev)

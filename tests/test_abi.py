@@ -56,7 +56,7 @@ def test_descriptor_structs_match_the_header(tmp_path):
         import pytest
         pytest.skip("gcc not available")
     structs = {"e4t_gemm_desc": _C.GemmDesc, "e4t_conv_desc": _C.ConvDesc, "e4t_wo_desc": _C.WODesc, "e4t_gemm_plan_t": _C.GemmPlan,
-               "e4t_attention_plan_t": _C.AttentionPlan}
+               "e4t_attention_plan_t": _C.AttentionPlan, "e4t_gemm_kernel_t": _C.GemmKernel}
     lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{os.path.join(ROOT, "include", "e4t_hip.h")}"', "int main(void) {"]
     for cname, cls in structs.items():
         lines.append(f'  printf("{cname} sizeof %zu\\n", sizeof({cname}));')

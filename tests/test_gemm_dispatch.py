@@ -14,10 +14,15 @@ and the step's attention shapes stand in clear text.  A slipped threshold passes
 
 Which KERNEL a conv launch gets is decided after the plan (the strip predicates, the channel-major K order, the GENERAL epilogue, the automatic
 split-K fallback); e4t_conv3x3_kernel reports it from the launcher's own decision.  Every case of the conv checks stands here with its kernel symbol
-and split-K in clear text, and the symbols x conv modes the checks reach are held against everything the query returns over the corpus."""
+and split-K in clear text, and the symbols x conv modes the checks reach are held against everything the query returns over the corpus.
+
+The dense GEMM gets the same: e4t_gemm_kernel / e4t_gemm_tn_kernel report symbol, split-K, store path, reduce kernel and tail rows from the function the
+launch itself calls; every case of the GEMM checks, old and new, is pinned in clear text, and the (symbol, store path) pairs and reduce kernels the
+checks reach are held against everything the query returns over the corpus."""
 import ctypes as C
 import importlib.util
 import os
+import re
 
 import pytest
 
@@ -471,3 +476,770 @@ def test_conv_checks_reach_every_kernel_the_launcher_can_choose(dumper):
     excluded = {(s, m) for s, m in units if s in CONV_KERNELS_NOT_REACHED}
     assert set(CONV_KERNELS_NOT_REACHED) <= set(CONV_KERNEL_MODES) and not (reached & excluded)
     assert reached | excluded == units, (sorted(units - reached - excluded), sorted(reached - units))
+
+
+# ---- dense GEMM: what e4t_gemm_kernel / e4t_gemm_tn_kernel (the launcher's own decision: gemm.hip, decide_launch / resolve_tn) say every case of the
+# GEMM checks runs, "<kernel symbol> splitk<n> <store path> [<reduce symbol>] [tail<r>]" -> the cases (kernel_checks.gemm_tag) it is pinned for.
+# A planner or table change that moves a case off its kernel, its store path or its reduce kernel fails here.
+CHECK_GEMM_KERNELS = {
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 168x152x64 t128 s1 bare", "gemm 168x152x128 t128 s1 bare", "gemm 168x152x192 t128 s1 bare", "gemm 168x152x256 t128 s1 bare",
+        "gemm 168x152x320 t128 s1 bare", "gemm 168x152x72 t128 s1 bare", "gemm 168x152x168 t128 s1 bare", "gemm 168x152x64 t128 s1 bias+res",
+        "gemm 168x152x128 t128 s1 bias+res", "gemm 168x152x192 t128 s1 bias+res", "gemm 168x152x256 t128 s1 bias+res", "gemm 168x152x320 t128 s1 bias+res",
+        "gemm 168x152x72 t128 s1 bias+res", "gemm 168x152x168 t128 s1 bias+res", "gemm 1x168x136 t128 s1 bare", "gemm 1x168x136 t128 s1 bias+res",
+        "gemm 127x152x136 t128 s1 bare", "gemm 127x152x136 t128 s1 bias+res", "gemm 168x8x136 t128 s1 bare", "gemm 168x8x136 t128 s1 bias+res",
+        "gemm 1192x280x136 t128 s1 bare", "gemm 1192x280x136 t128 s1 bias+res", "gemm 168x152x104 t128 s1 bare K1=64", "gemm 168x152x104 t128 s1 bias+res K1=64",
+        "gemm 168x152x136 t128 s1 bare batch2", "gemm 168x152x136 t128 s1 bias batch2", "gemm 168x152x136 t128 s1 bare", "gemm 168x152x136 t128 s1 bias",
+        "gemm 168x152x136 t128 s1 bias+res", "gemm 168x152x136 t128 s1 full", "gemm 168x152x136 t128 s1 alpha", "gemm 168x152x136 t128 s1 rowbias slice",
+        "gemm 168x152x136 t128 s1 C slice8", "gemm 168x152x136 t128 s1 res slice", "gemm 160x152x136 t128 s1 colstats", "gemm 160x152x136 t128 s1 colstats+res",
+        "gemm 168x152x136 t128 s1 bias misaligned",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk1 f32-direct": [
+        "gemm 168x152x136 t128 s1 f32", "gemm 168x152x136 t128 s1 f32 res32", "gemm 168x152x136 t128 s1 f32 bare",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk1 scalar": [
+        "gemm 168x148x136 t128 s1 bare", "gemm 168x148x136 t128 s1 bias+res", "gemm 168x152x136 t128 s1 f32 res16", "gemm 168x152x136 t128 s1 accum16",
+        "gemm 168x152x136 t128 s1 accum32", "gemm 168x152x136 t128 s1 C slice4",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 168x152x320 t128 s2 f32 bare",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x320 t128 s2 bare", "gemm 168x152x320 t128 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 168x152x320 t128 s2 bias misaligned",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x192 t128 s3 bare", "gemm 168x152x192 t128 s3 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64> splitk1 bf16-staged": [
+        "gemm 168x152x64 t128 s1 gelu", "gemm 168x152x128 t128 s1 gelu", "gemm 168x152x192 t128 s1 gelu", "gemm 168x152x256 t128 s1 gelu",
+        "gemm 168x152x320 t128 s1 gelu", "gemm 168x152x72 t128 s1 gelu", "gemm 168x152x168 t128 s1 gelu", "gemm 168x152x64 t128 s1 gelu+bias+res",
+        "gemm 168x152x128 t128 s1 gelu+bias+res", "gemm 168x152x192 t128 s1 gelu+bias+res", "gemm 168x152x256 t128 s1 gelu+bias+res",
+        "gemm 168x152x320 t128 s1 gelu+bias+res", "gemm 168x152x72 t128 s1 gelu+bias+res", "gemm 168x152x168 t128 s1 gelu+bias+res", "gemm 168x152x136 t128 s1 gelu",
+        "gemm 168x152x136 t128 s1 gelu+bias+res", "gemm 168x152x136 t128 s1 general full", "gemm 168x152x136 t128 s1 rowbias24",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64> splitk1 scalar": [
+        "gemm 168x152x136 t128 s1 gelu C slice4",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x320 t128 s2 gelu", "gemm 168x152x320 t128 s2 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x192 t128 s3 gelu", "gemm 168x152x192 t128 s3 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64> splitk1 bf16-staged": [
+        "gemm 168x152x64 t3128 s1 bare", "gemm 168x152x128 t3128 s1 bare", "gemm 168x152x192 t3128 s1 bare", "gemm 168x152x256 t3128 s1 bare",
+        "gemm 168x152x320 t3128 s1 bare", "gemm 168x152x384 t3128 s1 bare", "gemm 168x152x72 t3128 s1 bare", "gemm 168x152x232 t3128 s1 bare",
+        "gemm 168x152x64 t3128 s1 bias+res", "gemm 168x152x128 t3128 s1 bias+res", "gemm 168x152x192 t3128 s1 bias+res", "gemm 168x152x256 t3128 s1 bias+res",
+        "gemm 168x152x320 t3128 s1 bias+res", "gemm 168x152x384 t3128 s1 bias+res", "gemm 168x152x72 t3128 s1 bias+res", "gemm 168x152x232 t3128 s1 bias+res",
+        "gemm 1x168x136 t3128 s1 bare", "gemm 1x168x136 t3128 s1 bias+res", "gemm 127x152x136 t3128 s1 bare", "gemm 127x152x136 t3128 s1 bias+res",
+        "gemm 168x8x136 t3128 s1 bare", "gemm 168x8x136 t3128 s1 bias+res", "gemm 1192x280x136 t3128 s1 bare", "gemm 1192x280x136 t3128 s1 bias+res",
+        "gemm 168x152x104 t3128 s1 bare K1=64", "gemm 168x152x104 t3128 s1 bias+res K1=64", "gemm 168x152x136 t3128 s1 bare batch2",
+        "gemm 168x152x136 t3128 s1 bias batch2", "gemm 168x152x136 t3128 s1 bare", "gemm 168x152x136 t3128 s1 full",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64> splitk1 f32-direct": [
+        "gemm 168x152x136 t3128 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64> splitk1 scalar": [
+        "gemm 168x148x136 t3128 s1 bare", "gemm 168x148x136 t3128 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x320 t3128 s2 bare", "gemm 168x152x320 t3128 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x192 t3128 s3 bare", "gemm 168x152x192 t3128 s3 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk1 bf16-staged": [
+        "gemm 168x152x64 t4128 s1 bare", "gemm 168x152x128 t4128 s1 bare", "gemm 168x152x192 t4128 s1 bare", "gemm 168x152x256 t4128 s1 bare",
+        "gemm 168x152x320 t4128 s1 bare", "gemm 168x152x384 t4128 s1 bare", "gemm 168x152x448 t4128 s1 bare", "gemm 168x152x72 t4128 s1 bare",
+        "gemm 168x152x296 t4128 s1 bare", "gemm 168x152x64 t4128 s1 bias+res", "gemm 168x152x128 t4128 s1 bias+res", "gemm 168x152x192 t4128 s1 bias+res",
+        "gemm 168x152x256 t4128 s1 bias+res", "gemm 168x152x320 t4128 s1 bias+res", "gemm 168x152x384 t4128 s1 bias+res", "gemm 168x152x448 t4128 s1 bias+res",
+        "gemm 168x152x72 t4128 s1 bias+res", "gemm 168x152x296 t4128 s1 bias+res", "gemm 1x168x136 t4128 s1 bare", "gemm 1x168x136 t4128 s1 bias+res",
+        "gemm 127x152x136 t4128 s1 bare", "gemm 127x152x136 t4128 s1 bias+res", "gemm 168x8x136 t4128 s1 bare", "gemm 168x8x136 t4128 s1 bias+res",
+        "gemm 1192x280x136 t4128 s1 bare", "gemm 1192x280x136 t4128 s1 bias+res", "gemm 168x152x104 t4128 s1 bare K1=64", "gemm 168x152x104 t4128 s1 bias+res K1=64",
+        "gemm 168x152x136 t4128 s1 bare batch2", "gemm 168x152x136 t4128 s1 bias batch2", "gemm 168x152x136 t4128 s1 bare", "gemm 168x152x136 t4128 s1 full",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk1 f32-direct": [
+        "gemm 168x152x136 t4128 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk1 scalar": [
+        "gemm 168x148x136 t4128 s1 bare", "gemm 168x148x136 t4128 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x320 t4128 s2 bare", "gemm 168x152x320 t4128 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x152x192 t4128 s3 bare", "gemm 168x152x192 t4128 s3 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 168x184x64 t160 s1 bare", "gemm 168x184x128 t160 s1 bare", "gemm 168x184x192 t160 s1 bare", "gemm 168x184x256 t160 s1 bare",
+        "gemm 168x184x320 t160 s1 bare", "gemm 168x184x72 t160 s1 bare", "gemm 168x184x168 t160 s1 bare", "gemm 168x184x64 t160 s1 bias+res",
+        "gemm 168x184x128 t160 s1 bias+res", "gemm 168x184x192 t160 s1 bias+res", "gemm 168x184x256 t160 s1 bias+res", "gemm 168x184x320 t160 s1 bias+res",
+        "gemm 168x184x72 t160 s1 bias+res", "gemm 168x184x168 t160 s1 bias+res", "gemm 1x200x136 t160 s1 bare", "gemm 1x200x136 t160 s1 bias+res",
+        "gemm 127x184x136 t160 s1 bare", "gemm 127x184x136 t160 s1 bias+res", "gemm 168x8x136 t160 s1 bare", "gemm 168x8x136 t160 s1 bias+res",
+        "gemm 1192x344x136 t160 s1 bare", "gemm 1192x344x136 t160 s1 bias+res", "gemm 168x184x104 t160 s1 bare K1=64", "gemm 168x184x104 t160 s1 bias+res K1=64",
+        "gemm 168x184x136 t160 s1 bare batch2", "gemm 168x184x136 t160 s1 bias batch2", "gemm 168x184x136 t160 s1 bare", "gemm 168x184x136 t160 s1 bias",
+        "gemm 168x184x136 t160 s1 bias+res", "gemm 168x184x136 t160 s1 full", "gemm 168x184x136 t160 s1 alpha", "gemm 168x184x136 t160 s1 rowbias slice",
+        "gemm 168x184x136 t160 s1 C slice8", "gemm 168x184x136 t160 s1 res slice", "gemm 160x184x136 t160 s1 colstats", "gemm 160x184x136 t160 s1 colstats+res",
+        "gemm 168x184x136 t160 s1 bias misaligned",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged tail1": [
+        "gemm 1153x320x144 t160 s1 bare", "gemm 1153x320x144 t160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged tail17": [
+        "gemm 1169x320x144 t160 s1 bare", "gemm 1169x320x144 t160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged tail32": [
+        "gemm 1184x320x144 t160 s1 bare", "gemm 1184x320x144 t160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 f32-direct": [
+        "gemm 168x184x136 t160 s1 f32", "gemm 168x184x136 t160 s1 f32 res32", "gemm 168x184x136 t160 s1 f32 bare",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 scalar": [
+        "gemm 168x180x136 t160 s1 bare", "gemm 168x180x136 t160 s1 bias+res", "gemm 168x184x136 t160 s1 f32 res16", "gemm 168x184x136 t160 s1 accum16",
+        "gemm 168x184x136 t160 s1 accum32", "gemm 168x184x136 t160 s1 C slice4",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 168x184x320 t160 s2 f32 bare",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x320 t160 s2 bare", "gemm 168x184x320 t160 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 168x184x320 t160 s2 bias misaligned",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x192 t160 s3 bare", "gemm 168x184x192 t160 s3 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, true, 64> splitk1 bf16-staged": [
+        "gemm 168x184x64 t160 s1 gelu", "gemm 168x184x128 t160 s1 gelu", "gemm 168x184x192 t160 s1 gelu", "gemm 168x184x256 t160 s1 gelu",
+        "gemm 168x184x320 t160 s1 gelu", "gemm 168x184x72 t160 s1 gelu", "gemm 168x184x168 t160 s1 gelu", "gemm 168x184x64 t160 s1 gelu+bias+res",
+        "gemm 168x184x128 t160 s1 gelu+bias+res", "gemm 168x184x192 t160 s1 gelu+bias+res", "gemm 168x184x256 t160 s1 gelu+bias+res",
+        "gemm 168x184x320 t160 s1 gelu+bias+res", "gemm 168x184x72 t160 s1 gelu+bias+res", "gemm 168x184x168 t160 s1 gelu+bias+res", "gemm 168x184x136 t160 s1 gelu",
+        "gemm 168x184x136 t160 s1 gelu+bias+res", "gemm 168x184x136 t160 s1 general full", "gemm 168x184x136 t160 s1 rowbias24",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, true, 64> splitk1 scalar": [
+        "gemm 168x184x136 t160 s1 gelu C slice4",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, true, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x320 t160 s2 gelu", "gemm 168x184x320 t160 s2 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, true, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x192 t160 s3 gelu", "gemm 168x184x192 t160 s3 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 bf16-staged": [
+        "gemm 168x184x64 t3160 s1 bare", "gemm 168x184x128 t3160 s1 bare", "gemm 168x184x192 t3160 s1 bare", "gemm 168x184x256 t3160 s1 bare",
+        "gemm 168x184x320 t3160 s1 bare", "gemm 168x184x384 t3160 s1 bare", "gemm 168x184x72 t3160 s1 bare", "gemm 168x184x232 t3160 s1 bare",
+        "gemm 168x184x64 t3160 s1 bias+res", "gemm 168x184x128 t3160 s1 bias+res", "gemm 168x184x192 t3160 s1 bias+res", "gemm 168x184x256 t3160 s1 bias+res",
+        "gemm 168x184x320 t3160 s1 bias+res", "gemm 168x184x384 t3160 s1 bias+res", "gemm 168x184x72 t3160 s1 bias+res", "gemm 168x184x232 t3160 s1 bias+res",
+        "gemm 1x200x136 t3160 s1 bare", "gemm 1x200x136 t3160 s1 bias+res", "gemm 127x184x136 t3160 s1 bare", "gemm 127x184x136 t3160 s1 bias+res",
+        "gemm 168x8x136 t3160 s1 bare", "gemm 168x8x136 t3160 s1 bias+res", "gemm 1192x344x136 t3160 s1 bare", "gemm 1192x344x136 t3160 s1 bias+res",
+        "gemm 168x184x104 t3160 s1 bare K1=64", "gemm 168x184x104 t3160 s1 bias+res K1=64", "gemm 168x184x136 t3160 s1 bare batch2",
+        "gemm 168x184x136 t3160 s1 bias batch2", "gemm 168x184x136 t3160 s1 bare", "gemm 168x184x136 t3160 s1 full",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 bf16-staged tail1": [
+        "gemm 1153x320x144 t3160 s1 bare", "gemm 1153x320x144 t3160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 bf16-staged tail17": [
+        "gemm 1169x320x144 t3160 s1 bare", "gemm 1169x320x144 t3160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 bf16-staged tail32": [
+        "gemm 1184x320x144 t3160 s1 bare", "gemm 1184x320x144 t3160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 f32-direct": [
+        "gemm 168x184x136 t3160 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 scalar": [
+        "gemm 168x180x136 t3160 s1 bare", "gemm 168x180x136 t3160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x320 t3160 s2 bare", "gemm 168x184x320 t3160 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x192 t3160 s3 bare", "gemm 168x184x192 t3160 s3 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 bf16-staged": [
+        "gemm 168x184x64 t4160 s1 bare", "gemm 168x184x128 t4160 s1 bare", "gemm 168x184x192 t4160 s1 bare", "gemm 168x184x256 t4160 s1 bare",
+        "gemm 168x184x320 t4160 s1 bare", "gemm 168x184x384 t4160 s1 bare", "gemm 168x184x448 t4160 s1 bare", "gemm 168x184x72 t4160 s1 bare",
+        "gemm 168x184x296 t4160 s1 bare", "gemm 168x184x64 t4160 s1 bias+res", "gemm 168x184x128 t4160 s1 bias+res", "gemm 168x184x192 t4160 s1 bias+res",
+        "gemm 168x184x256 t4160 s1 bias+res", "gemm 168x184x320 t4160 s1 bias+res", "gemm 168x184x384 t4160 s1 bias+res", "gemm 168x184x448 t4160 s1 bias+res",
+        "gemm 168x184x72 t4160 s1 bias+res", "gemm 168x184x296 t4160 s1 bias+res", "gemm 1x200x136 t4160 s1 bare", "gemm 1x200x136 t4160 s1 bias+res",
+        "gemm 127x184x136 t4160 s1 bare", "gemm 127x184x136 t4160 s1 bias+res", "gemm 168x8x136 t4160 s1 bare", "gemm 168x8x136 t4160 s1 bias+res",
+        "gemm 1192x344x136 t4160 s1 bare", "gemm 1192x344x136 t4160 s1 bias+res", "gemm 168x184x104 t4160 s1 bare K1=64", "gemm 168x184x104 t4160 s1 bias+res K1=64",
+        "gemm 168x184x136 t4160 s1 bare batch2", "gemm 168x184x136 t4160 s1 bias batch2", "gemm 168x184x136 t4160 s1 bare", "gemm 168x184x136 t4160 s1 full",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 bf16-staged tail1": [
+        "gemm 1153x320x144 t4160 s1 bare", "gemm 1153x320x144 t4160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 bf16-staged tail17": [
+        "gemm 1169x320x144 t4160 s1 bare", "gemm 1169x320x144 t4160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 bf16-staged tail32": [
+        "gemm 1184x320x144 t4160 s1 bare", "gemm 1184x320x144 t4160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 f32-direct": [
+        "gemm 168x184x136 t4160 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk1 scalar": [
+        "gemm 168x180x136 t4160 s1 bare", "gemm 168x180x136 t4160 s1 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x320 t4160 s2 bare", "gemm 168x184x320 t4160 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 168x184x192 t4160 s3 bare", "gemm 168x184x192 t4160 s3 bias+res",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk1 bf16-staged": [
+        "gemm 296x152x32 t5256 s1 bare", "gemm 296x152x64 t5256 s1 bare", "gemm 296x152x96 t5256 s1 bare", "gemm 296x152x128 t5256 s1 bare",
+        "gemm 296x152x160 t5256 s1 bare", "gemm 296x152x192 t5256 s1 bare", "gemm 296x152x72 t5256 s1 bare", "gemm 296x152x232 t5256 s1 bare",
+        "gemm 296x152x88 t5256 s1 bare", "gemm 296x152x112 t5256 s1 bare", "gemm 296x152x32 t5256 s1 bias+res", "gemm 296x152x64 t5256 s1 bias+res",
+        "gemm 296x152x96 t5256 s1 bias+res", "gemm 296x152x128 t5256 s1 bias+res", "gemm 296x152x160 t5256 s1 bias+res", "gemm 296x152x192 t5256 s1 bias+res",
+        "gemm 296x152x72 t5256 s1 bias+res", "gemm 296x152x232 t5256 s1 bias+res", "gemm 296x152x88 t5256 s1 bias+res", "gemm 296x152x112 t5256 s1 bias+res",
+        "gemm 1x168x136 t5256 s1 bare", "gemm 1x168x136 t5256 s1 bias+res", "gemm 255x152x136 t5256 s1 bare", "gemm 255x152x136 t5256 s1 bias+res",
+        "gemm 296x8x136 t5256 s1 bare", "gemm 296x8x136 t5256 s1 bias+res", "gemm 2344x280x136 t5256 s1 bare", "gemm 2344x280x136 t5256 s1 bias+res",
+        "gemm 296x152x104 t5256 s1 bare K1=64", "gemm 296x152x104 t5256 s1 bias+res K1=64", "gemm 296x152x136 t5256 s1 bare batch2",
+        "gemm 296x152x136 t5256 s1 bias batch2", "gemm 296x152x136 t5256 s1 bare", "gemm 296x152x136 t5256 s1 bias", "gemm 296x152x136 t5256 s1 bias+res",
+        "gemm 296x152x136 t5256 s1 full", "gemm 296x152x136 t5256 s1 alpha", "gemm 296x152x136 t5256 s1 rowbias slice", "gemm 296x152x136 t5256 s1 C slice8",
+        "gemm 296x152x136 t5256 s1 res slice", "gemm 288x152x136 t5256 s1 colstats", "gemm 288x152x136 t5256 s1 colstats+res",
+        "gemm 296x152x136 t5256 s1 bias misaligned",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk1 f32-direct": [
+        "gemm 296x152x136 t5256 s1 f32", "gemm 296x152x136 t5256 s1 f32 res32", "gemm 296x152x136 t5256 s1 f32 bare",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk1 scalar": [
+        "gemm 296x148x136 t5256 s1 bare", "gemm 296x148x136 t5256 s1 bias+res", "gemm 296x152x136 t5256 s1 f32 res16", "gemm 296x152x136 t5256 s1 accum16",
+        "gemm 296x152x136 t5256 s1 accum32", "gemm 296x152x136 t5256 s1 C slice4",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 296x152x320 t5256 s2 f32 bare",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x152x320 t5256 s2 bare", "gemm 296x152x320 t5256 s2 bias+res",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 296x152x320 t5256 s2 bias misaligned",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x152x192 t5256 s3 bare", "gemm 296x152x192 t5256 s3 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 104x88x64 t64 s1 bare", "gemm 104x88x128 t64 s1 bare", "gemm 104x88x192 t64 s1 bare", "gemm 104x88x256 t64 s1 bare", "gemm 104x88x320 t64 s1 bare",
+        "gemm 104x88x72 t64 s1 bare", "gemm 104x88x168 t64 s1 bare", "gemm 104x88x64 t64 s1 bias+res", "gemm 104x88x128 t64 s1 bias+res",
+        "gemm 104x88x192 t64 s1 bias+res", "gemm 104x88x256 t64 s1 bias+res", "gemm 104x88x320 t64 s1 bias+res", "gemm 104x88x72 t64 s1 bias+res",
+        "gemm 104x88x168 t64 s1 bias+res", "gemm 1x104x136 t64 s1 bare", "gemm 1x104x136 t64 s1 bias+res", "gemm 63x88x136 t64 s1 bare",
+        "gemm 63x88x136 t64 s1 bias+res", "gemm 104x8x136 t64 s1 bare", "gemm 104x8x136 t64 s1 bias+res", "gemm 616x152x136 t64 s1 bare",
+        "gemm 616x152x136 t64 s1 bias+res", "gemm 104x88x104 t64 s1 bare K1=64", "gemm 104x88x104 t64 s1 bias+res K1=64", "gemm 104x88x136 t64 s1 bare batch2",
+        "gemm 104x88x136 t64 s1 bias batch2", "gemm 104x88x136 t64 s1 bare", "gemm 104x88x136 t64 s1 bias", "gemm 104x88x136 t64 s1 bias+res",
+        "gemm 104x88x136 t64 s1 full", "gemm 104x88x136 t64 s1 alpha", "gemm 104x88x136 t64 s1 rowbias slice", "gemm 104x88x136 t64 s1 C slice8",
+        "gemm 104x88x136 t64 s1 res slice", "gemm 96x88x136 t64 s1 colstats", "gemm 96x88x136 t64 s1 colstats+res", "gemm 104x88x136 t64 s1 bias misaligned",
+        "gemm 104x88x104 t64 s1 full K1=64",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 f32-direct": [
+        "gemm 104x88x136 t64 s1 f32", "gemm 104x88x136 t64 s1 f32 res32", "gemm 104x88x136 t64 s1 f32 bare",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 scalar": [
+        "gemm 104x84x136 t64 s1 bare", "gemm 104x84x136 t64 s1 bias+res", "gemm 104x88x136 t64 s1 f32 res16", "gemm 104x88x136 t64 s1 accum16",
+        "gemm 104x88x136 t64 s1 accum32", "gemm 104x88x136 t64 s1 C slice4",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 104x88x320 t64 s2 f32 bare",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x320 t64 s2 bare", "gemm 104x88x320 t64 s2 bias+res", "gemm 104x88x320 t64 s2 full", "gemm 104x88x2048 t64 s0 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 104x88x320 t64 s2 bias misaligned",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x192 t64 s3 bare", "gemm 104x88x192 t64 s3 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, true, 64> splitk1 bf16-staged": [
+        "gemm 104x88x64 t64 s1 gelu", "gemm 104x88x128 t64 s1 gelu", "gemm 104x88x192 t64 s1 gelu", "gemm 104x88x256 t64 s1 gelu", "gemm 104x88x320 t64 s1 gelu",
+        "gemm 104x88x72 t64 s1 gelu", "gemm 104x88x168 t64 s1 gelu", "gemm 104x88x64 t64 s1 gelu+bias+res", "gemm 104x88x128 t64 s1 gelu+bias+res",
+        "gemm 104x88x192 t64 s1 gelu+bias+res", "gemm 104x88x256 t64 s1 gelu+bias+res", "gemm 104x88x320 t64 s1 gelu+bias+res", "gemm 104x88x72 t64 s1 gelu+bias+res",
+        "gemm 104x88x168 t64 s1 gelu+bias+res", "gemm 104x88x136 t64 s1 gelu", "gemm 104x88x136 t64 s1 gelu+bias+res", "gemm 104x88x136 t64 s1 general full",
+        "gemm 104x88x136 t64 s1 rowbias24",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, true, 64> splitk1 scalar": [
+        "gemm 104x88x136 t64 s1 gelu C slice4",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, true, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x320 t64 s2 gelu", "gemm 104x88x320 t64 s2 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, true, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x192 t64 s3 gelu", "gemm 104x88x192 t64 s3 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk1 bf16-staged": [
+        "gemm 104x88x64 t3064 s1 bare", "gemm 104x88x128 t3064 s1 bare", "gemm 104x88x192 t3064 s1 bare", "gemm 104x88x256 t3064 s1 bare",
+        "gemm 104x88x320 t3064 s1 bare", "gemm 104x88x384 t3064 s1 bare", "gemm 104x88x72 t3064 s1 bare", "gemm 104x88x232 t3064 s1 bare",
+        "gemm 104x88x64 t3064 s1 bias+res", "gemm 104x88x128 t3064 s1 bias+res", "gemm 104x88x192 t3064 s1 bias+res", "gemm 104x88x256 t3064 s1 bias+res",
+        "gemm 104x88x320 t3064 s1 bias+res", "gemm 104x88x384 t3064 s1 bias+res", "gemm 104x88x72 t3064 s1 bias+res", "gemm 104x88x232 t3064 s1 bias+res",
+        "gemm 1x104x136 t3064 s1 bare", "gemm 1x104x136 t3064 s1 bias+res", "gemm 63x88x136 t3064 s1 bare", "gemm 63x88x136 t3064 s1 bias+res",
+        "gemm 104x8x136 t3064 s1 bare", "gemm 104x8x136 t3064 s1 bias+res", "gemm 616x152x136 t3064 s1 bare", "gemm 616x152x136 t3064 s1 bias+res",
+        "gemm 104x88x104 t3064 s1 bare K1=64", "gemm 104x88x104 t3064 s1 bias+res K1=64", "gemm 104x88x136 t3064 s1 bare batch2", "gemm 104x88x136 t3064 s1 bias batch2",
+        "gemm 104x88x136 t3064 s1 bare", "gemm 104x88x136 t3064 s1 full",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk1 f32-direct": [
+        "gemm 104x88x136 t3064 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk1 scalar": [
+        "gemm 104x84x136 t3064 s1 bare", "gemm 104x84x136 t3064 s1 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x320 t3064 s2 bare", "gemm 104x88x320 t3064 s2 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x192 t3064 s3 bare", "gemm 104x88x192 t3064 s3 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64> splitk1 bf16-staged": [
+        "gemm 104x88x64 t3064 s1 gelu", "gemm 104x88x128 t3064 s1 gelu", "gemm 104x88x192 t3064 s1 gelu", "gemm 104x88x256 t3064 s1 gelu",
+        "gemm 104x88x320 t3064 s1 gelu", "gemm 104x88x384 t3064 s1 gelu", "gemm 104x88x72 t3064 s1 gelu", "gemm 104x88x232 t3064 s1 gelu",
+        "gemm 104x88x64 t3064 s1 gelu+bias+res", "gemm 104x88x128 t3064 s1 gelu+bias+res", "gemm 104x88x192 t3064 s1 gelu+bias+res",
+        "gemm 104x88x256 t3064 s1 gelu+bias+res", "gemm 104x88x320 t3064 s1 gelu+bias+res", "gemm 104x88x384 t3064 s1 gelu+bias+res",
+        "gemm 104x88x72 t3064 s1 gelu+bias+res", "gemm 104x88x232 t3064 s1 gelu+bias+res", "gemm 104x88x136 t3064 s1 gelu", "gemm 104x88x136 t3064 s1 general full",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64> splitk1 scalar": [
+        "gemm 104x88x136 t3064 s1 gelu C slice4",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x320 t3064 s2 gelu", "gemm 104x88x320 t3064 s2 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x192 t3064 s3 gelu", "gemm 104x88x192 t3064 s3 gelu+bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk1 bf16-staged": [
+        "gemm 104x88x64 t4064 s1 bare", "gemm 104x88x128 t4064 s1 bare", "gemm 104x88x192 t4064 s1 bare", "gemm 104x88x256 t4064 s1 bare",
+        "gemm 104x88x320 t4064 s1 bare", "gemm 104x88x384 t4064 s1 bare", "gemm 104x88x448 t4064 s1 bare", "gemm 104x88x72 t4064 s1 bare",
+        "gemm 104x88x296 t4064 s1 bare", "gemm 104x88x64 t4064 s1 bias+res", "gemm 104x88x128 t4064 s1 bias+res", "gemm 104x88x192 t4064 s1 bias+res",
+        "gemm 104x88x256 t4064 s1 bias+res", "gemm 104x88x320 t4064 s1 bias+res", "gemm 104x88x384 t4064 s1 bias+res", "gemm 104x88x448 t4064 s1 bias+res",
+        "gemm 104x88x72 t4064 s1 bias+res", "gemm 104x88x296 t4064 s1 bias+res", "gemm 1x104x136 t4064 s1 bare", "gemm 1x104x136 t4064 s1 bias+res",
+        "gemm 63x88x136 t4064 s1 bare", "gemm 63x88x136 t4064 s1 bias+res", "gemm 104x8x136 t4064 s1 bare", "gemm 104x8x136 t4064 s1 bias+res",
+        "gemm 616x152x136 t4064 s1 bare", "gemm 616x152x136 t4064 s1 bias+res", "gemm 104x88x104 t4064 s1 bare K1=64", "gemm 104x88x104 t4064 s1 bias+res K1=64",
+        "gemm 104x88x136 t4064 s1 bare batch2", "gemm 104x88x136 t4064 s1 bias batch2", "gemm 104x88x136 t4064 s1 bare", "gemm 104x88x136 t4064 s1 full",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk1 f32-direct": [
+        "gemm 104x88x136 t4064 s1 f32 res32",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk1 scalar": [
+        "gemm 104x84x136 t4064 s1 bare", "gemm 104x84x136 t4064 s1 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x320 t4064 s2 bare", "gemm 104x88x320 t4064 s2 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 104x88x192 t4064 s3 bare", "gemm 104x88x192 t4064 s3 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged": [
+        "gemm 296x280x64 t512 s1 bare", "gemm 296x280x128 t512 s1 bare", "gemm 296x280x192 t512 s1 bare", "gemm 296x280x256 t512 s1 bare",
+        "gemm 296x280x320 t512 s1 bare", "gemm 296x280x64 t512 s1 bias+res", "gemm 296x280x128 t512 s1 bias+res", "gemm 296x280x192 t512 s1 bias+res",
+        "gemm 296x280x256 t512 s1 bias+res", "gemm 296x280x320 t512 s1 bias+res", "gemm 1x296x128 t512 s1 bare", "gemm 1x296x128 t512 s1 bias+res",
+        "gemm 255x280x128 t512 s1 bare", "gemm 255x280x128 t512 s1 bias+res", "gemm 296x8x128 t512 s1 bare", "gemm 296x8x128 t512 s1 bias+res",
+        "gemm 2344x536x128 t512 s1 bare", "gemm 2344x536x128 t512 s1 bias+res", "gemm 296x280x128 t512 s1 bare K1=64", "gemm 296x280x128 t512 s1 bias+res K1=64",
+        "gemm 296x280x128 t512 s1 bare batch2", "gemm 296x280x128 t512 s1 bias batch2", "gemm 296x280x128 t512 s1 bias", "gemm 296x280x128 t512 s1 full",
+        "gemm 296x280x128 t512 s1 alpha", "gemm 296x280x128 t512 s1 rowbias slice", "gemm 296x280x128 t512 s1 C slice8", "gemm 296x280x128 t512 s1 res slice",
+        "gemm 288x280x128 t512 s1 colstats", "gemm 288x280x128 t512 s1 colstats+res", "gemm 296x280x128 t512 s1 bias misaligned", "gemm 296x280x128 t512 s1 full K1=64",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged tail1": [
+        "gemm 1153x320x128 t512 s1 bare", "gemm 1153x320x128 t512 s1 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged tail17": [
+        "gemm 1169x320x128 t512 s1 bare", "gemm 1169x320x128 t512 s1 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged tail32": [
+        "gemm 1184x320x128 t512 s1 bare", "gemm 1184x320x128 t512 s1 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 f32-direct": [
+        "gemm 296x280x128 t512 s1 f32", "gemm 296x280x128 t512 s1 f32 res32", "gemm 296x280x128 t512 s1 f32 bare",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 scalar": [
+        "gemm 296x276x128 t512 s1 bare", "gemm 296x276x128 t512 s1 bias+res", "gemm 296x280x128 t512 s1 f32 res16", "gemm 296x280x128 t512 s1 accum16",
+        "gemm 296x280x128 t512 s1 accum32", "gemm 296x280x128 t512 s1 C slice4",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 296x280x320 t512 s2 f32 bare",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x280x320 t512 s2 bare", "gemm 296x280x320 t512 s2 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 296x280x320 t512 s2 bias misaligned",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x280x192 t512 s3 bare", "gemm 296x280x192 t512 s3 bias+res",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk1 bf16-staged": [
+        "gemm 296x280x64 t512 s1 gelu", "gemm 296x280x128 t512 s1 gelu", "gemm 296x280x192 t512 s1 gelu", "gemm 296x280x256 t512 s1 gelu",
+        "gemm 296x280x320 t512 s1 gelu", "gemm 296x280x64 t512 s1 gelu+bias+res", "gemm 296x280x128 t512 s1 gelu+bias+res", "gemm 296x280x192 t512 s1 gelu+bias+res",
+        "gemm 296x280x256 t512 s1 gelu+bias+res", "gemm 296x280x320 t512 s1 gelu+bias+res", "gemm 296x280x128 t512 s1 general full",
+        "gemm 296x280x128 t512 s1 rowbias24",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk1 scalar": [
+        "gemm 296x280x128 t512 s1 gelu C slice4",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x280x320 t512 s2 gelu", "gemm 296x280x320 t512 s2 gelu+bias+res",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x280x192 t512 s3 gelu", "gemm 296x280x192 t512 s3 gelu+bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 bf16-staged": [
+        "gemm 296x640x64 t2320 s1 bare", "gemm 296x640x128 t2320 s1 bare", "gemm 296x640x192 t2320 s1 bare", "gemm 296x640x256 t2320 s1 bare",
+        "gemm 296x640x320 t2320 s1 bare", "gemm 296x640x64 t2320 s1 bias+res", "gemm 296x640x128 t2320 s1 bias+res", "gemm 296x640x192 t2320 s1 bias+res",
+        "gemm 296x640x256 t2320 s1 bias+res", "gemm 296x640x320 t2320 s1 bias+res", "gemm 1x640x128 t2320 s1 bare", "gemm 1x640x128 t2320 s1 bias+res",
+        "gemm 255x640x128 t2320 s1 bare", "gemm 255x640x128 t2320 s1 bias+res", "gemm 2344x960x128 t2320 s1 bare", "gemm 2344x960x128 t2320 s1 bias+res",
+        "gemm 296x640x128 t2320 s1 bare K1=64", "gemm 296x640x128 t2320 s1 bias+res K1=64", "gemm 296x640x128 t2320 s1 bare batch2",
+        "gemm 296x640x128 t2320 s1 bias batch2", "gemm 296x640x128 t2320 s1 bias", "gemm 296x640x128 t2320 s1 full", "gemm 296x640x128 t2320 s1 alpha",
+        "gemm 296x640x128 t2320 s1 rowbias slice", "gemm 296x640x128 t2320 s1 C slice8", "gemm 296x640x128 t2320 s1 res slice", "gemm 288x640x128 t2320 s1 colstats",
+        "gemm 288x640x128 t2320 s1 colstats+res", "gemm 296x640x128 t2320 s1 bias misaligned",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 bf16-staged tail1": [
+        "gemm 1153x320x128 t2320 s1 bare", "gemm 1153x320x128 t2320 s1 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 bf16-staged tail17": [
+        "gemm 1169x320x128 t2320 s1 bare", "gemm 1169x320x128 t2320 s1 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 bf16-staged tail32": [
+        "gemm 1184x320x128 t2320 s1 bare", "gemm 1184x320x128 t2320 s1 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 f32-direct": [
+        "gemm 296x640x128 t2320 s1 f32", "gemm 296x640x128 t2320 s1 f32 res32", "gemm 296x640x128 t2320 s1 f32 bare",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 scalar": [
+        "gemm 296x640x128 t2320 s1 f32 res16", "gemm 296x640x128 t2320 s1 accum16", "gemm 296x640x128 t2320 s1 accum32", "gemm 296x640x128 t2320 s1 C slice4",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm 296x640x320 t2320 s2 f32 bare",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x640x320 t2320 s2 bare", "gemm 296x640x320 t2320 s2 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm 296x640x320 t2320 s2 bias misaligned",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x640x192 t2320 s3 bare", "gemm 296x640x192 t2320 s3 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk1 bf16-staged": [
+        "gemm 296x640x64 t2320 s1 gelu", "gemm 296x640x128 t2320 s1 gelu", "gemm 296x640x192 t2320 s1 gelu", "gemm 296x640x256 t2320 s1 gelu",
+        "gemm 296x640x320 t2320 s1 gelu", "gemm 296x640x64 t2320 s1 gelu+bias+res", "gemm 296x640x128 t2320 s1 gelu+bias+res", "gemm 296x640x192 t2320 s1 gelu+bias+res",
+        "gemm 296x640x256 t2320 s1 gelu+bias+res", "gemm 296x640x320 t2320 s1 gelu+bias+res", "gemm 296x640x128 t2320 s1 general full",
+        "gemm 296x640x128 t2320 s1 rowbias24",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk1 scalar": [
+        "gemm 296x640x128 t2320 s1 gelu C slice4",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x640x320 t2320 s2 gelu", "gemm 296x640x320 t2320 s2 gelu+bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 296x640x192 t2320 s3 gelu", "gemm 296x640x192 t2320 s3 gelu+bias+res",
+    ],
+    "gemm_tn_kernel splitk1 bf16-staged": [
+        "gemm_tn K200 M168 N152 s1 bf16",
+    ],
+    "gemm_tn_kernel splitk1 scalar": [
+        "gemm_tn K200 M168 N152 s1 f32", "gemm_tn K136 M8 N152 s1 f32", "gemm_tn K200 M168 N152 s1 lda", "gemm_tn K200 M168 N152 s1 C slice",
+        "gemm_tn K200 M168 N152 s1 accum", "gemm_tn K200 M168 N152 s1 alpha",
+    ],
+    "gemm_tn_kernel splitk2 splitk-partial splitk_reduce4f_kernel": [
+        "gemm_tn K300 M168 N152 s2 f32", "gemm_tn K2048 M136 N136 s0 f32", "gemm_tn K300 M168 N152 s2 accum",
+    ],
+    "gemm_tn_kernel splitk2 splitk-partial splitk_reduce_kernel": [
+        "gemm_tn K300 M168 N152 s2 bf16",
+    ],
+}
+
+CHECK_GEMM_EXISTING_KERNELS = {
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 1000x320x320 t128 s1 bias+res", "gemm 300x200x64 t2320 s1 bias+res", "gemm 1024x640x1280 t128 colstats + residual",
+        "gemm 8192x256x128 t128 colstats + residual", "gemm 34816x128x64 t128 colstats + residual", "gemm two-source A t2320",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 513x1000x1152 t2320 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 2056x1280x5120 tail bias",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64> splitk1 bf16-staged": [
+        "gemm gelu t2320",
+    ],
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64> splitk1 bf16-staged": [
+        "gemm 4096x640x2560 t0 s0 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 900x320x384 t160 s1 bias+res", "gemm 513x200x72 t160 s1 bias+res", "gemm 4096x320x320 t160 colstats", "gemm 66560x640x192 t160 colstats",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 bf16-staged tail32": [
+        "gemm 8224x1280x1280 tail bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk1 f32-direct": [
+        "gemm 1000x1280x320 t160 fp32 out + fp32 residual",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 300x480x128 t160 s2 bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 bf16-staged tail1": [
+        "gemm 4097x1280x1280 tail bias+res",
+    ],
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64> splitk1 f32-direct tail16": [
+        "gemm 4112x1280x1280 tail f32 res32", "gemm 4112x1280x5120 tail f32 res32", "gemm 4112x1280x1296 tail f32 res32",
+        "gemm 4112x1280x1280 t0 fp32 out + fp32 residual", "gemm 4112x1280x5120 t0 fp32 out + fp32 residual",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk1 bf16-staged": [
+        "gemm 1000x200x328 t256 s1 bias+res", "gemm 2048x256x64 t256 s1 bias+res", "gemm 900x384x512 t5256 s1 bias+res", "gemm 5000x640x320 t5256 s1 bias+res",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk1 f32-direct": [
+        "gemm 900x384x96 t5256 fp32 out + fp32 residual",
+    ],
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 700x320x1280 t256 s2 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 bf16-staged": [
+        "gemm 192x72x64 t64 colstats + residual", "gemm batched", "gemm batched broadcast A",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 f32-direct": [
+        "gemm 513x200x64 t64 fp32 out + fp32 residual",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk1 splitk-partial splitk_reduce4f_kernel": [
+        "gemm batched reduce (mean over slots)",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 130x200x1032 t64 s3 bias+res",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64> splitk1 bf16-staged": [
+        "gemm two-source A t3064",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64> splitk1 bf16-staged": [
+        "gemm gelu", "gemm gelu t3064",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk1 bf16-staged": [
+        "gemm 256x256x128 t0 s0 bias+res", "gemm 200x72x64 t0 s0 bias+res", "gemm 16x1280x1280 t0 s0 bias+res", "gemm 256x128x128 t0 colstats + residual",
+        "gemm two-source A", "gemm rowbias", "gemm strided A view",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk1 scalar": [
+        "gemm fp32 out + accumulate + alpha",
+    ],
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64> splitk11 splitk-partial splitk_reduce8_kernel": [
+        "gemm 64x64x4096 t0 s0 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged": [
+        "gemm 512x512x512 t512 s1 bias+res", "gemm 700x520x256 t512 s1 bias+res", "gemm 300x256x64 t512 s1 bias+res", "gemm 2048x1280x1920 t512 s0 bias+res",
+        "gemm 257x64x192 t512 s1 bias+res", "gemm 4096x2560x8192 t0 s0 bias+res", "gemm 2048x512x2304 t512 colstats", "gemm two-source A t512", "gemm batched t512",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged tail16": [
+        "gemm 4112x3840x1280 tail bias",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 bf16-staged tail31": [
+        "gemm 4127x3840x1280 tail bias",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 f32-direct": [
+        "gemm 700x512x256 t512 fp32 out + fp32 residual",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk1 scalar": [
+        "gemm 1000x300x128 t512 s1 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 513x1000x1152 t512 s2 bias+res",
+    ],
+    "gemm_pp_kernel<0, false, false> splitk3 splitk-partial splitk_reduce8_kernel": [
+        "gemm 4096x1280x10240 t0 s0 bias+res",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk1 bf16-staged": [
+        "gemm gelu t512",
+    ],
+    "gemm_pp_kernel<0, true, false> splitk1 f32-direct": [
+        "gemm gelu fp32-out t512",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 bf16-staged": [
+        "gemm 1000x320x320 t2320 s1 bias+res", "gemm 700x640x256 t2320 s1 bias+res", "gemm 65536x320x320 t2320 s1 bias+res", "gemm 16384x640x640 t2320 s0 bias+res",
+        "gemm 4096x320x320 t2320 colstats", "gemm 8192x640x640 t2320 colstats + residual", "gemm batched t2320",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk1 f32-direct": [
+        "gemm 1000x640x320 t2320 fp32 out + fp32 residual", "gemm row panels B2 T520 N320 K64",
+    ],
+    "gemm_pq_kernel<0, 320, false> splitk2 splitk-partial splitk_reduce8_kernel": [
+        "gemm 4096x1280x2560 t2320 s0 bias+res",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk1 bf16-staged": [
+        "gemm 1000x640x320 t2320 gelu", "gemm 970x640x320 t2320 row bias, rows_per_batch 97", "gemm 4096x320x1280 t2320 gelu",
+        "gemm 4074x320x1280 t2320 row bias, rows_per_batch 97", "gemm 513x960x64 t2320 gelu", "gemm 485x960x64 t2320 row bias, rows_per_batch 97",
+        "gemm row panels B3 T257 N640 K128", "gemm row panels B16 T257 N5120 K1280", "gemm row panels B5 T257 N960 K192",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk1 bf16-staged tail16": [
+        "gemm 4112x5120x1280 tail gelu+bias",
+    ],
+    "gemm_pq_kernel<0, 320, true> splitk1 bf16-staged tail32": [
+        "gemm 8224x5120x1280 tail gelu+bias",
+    ],
+    "gemm_tn_kernel splitk1 scalar": [
+        "gemm_tn K64 M128 N128 s1", "gemm_tn K1000 M320 N320 s0", "gemm_tn K1232 M2560 N768 s0", "gemm_tn K130 M8 N1280 s1", "gemm_tn fp32 accumulate",
+        "gemm_tn into a column slice",
+    ],
+    "gemm_tn_kernel splitk3 splitk-partial splitk_reduce4f_kernel": [
+        "gemm_tn K777 M200 N72 s3",
+    ],
+    "gemm_tn_kernel splitk32 splitk-partial splitk_reduce4f_kernel": [
+        "gemm_tn K65536 M320 N320 s0",
+    ],
+    "gemm_tn_kernel splitk4 splitk-partial splitk_reduce4f_kernel": [
+        "gemm_tn K4096 M960 N320 s0",
+    ],
+}
+
+
+def _gemm_said(c, override=None):
+    import kernel_checks as kc
+    d = kc.gemm_desc(c)
+    for k, v in (override or {}).items():
+        setattr(d, k, v)
+    rc, k = kc.gemm_kernel(c, d)
+    assert rc == 0, (c, override, _C.load().e4t_last_error())
+    return kc.gemm_kernel_text(k)
+
+
+def _new_gemm_cases():
+    import kernel_checks as kc
+    return kc.GEMM_KLOOP_CASES + kc.GEMM_EDGE_CASES + kc.GEMM_FORMS + kc.GEMM_TN_CASES + kc.GEMM_GUARD_CASES + kc.GEMM_TN_GUARD_CASES + kc.GEMM_AUTO_SPLIT_CASES
+
+
+def test_the_pinned_gemm_tables_cover_exactly_what_the_gemm_checks_run():
+    """one set of case lists (tests/kernel_checks.py, importable without a GPU) behind the GPU checks and these tables"""
+    import kernel_checks as kc
+    pinned = [t for tags in CHECK_GEMM_KERNELS.values() for t in tags]
+    assert len(pinned) == len(set(pinned)) and set(pinned) == {kc.gemm_tag(c) for c in _new_gemm_cases()}
+    old = [t for tags in CHECK_GEMM_EXISTING_KERNELS.values() for t in tags]
+    assert len(old) == len(set(old)) and set(old) == {label for label, _, _ in kc.check_gemm_pinned()}
+    # the lists are what the issue of the checks asks for: every DMA row, the K-tile counts around the stage count, both ragged remainders, both splits
+    for hint, (tm, tn, kt, st, whole_k, whole_n, general, tail) in kc.GEMM_TILES.items():
+        ks = {c.K for c in kc.GEMM_KLOOP_CASES if c.tile == hint and c.sk == 1 and c.form == "bare"}
+        assert {kt * n for n in (1, 2, 3, st, st + 1, st + 2, st + 3)} <= ks and (whole_k or {72, 64 * st + 40} <= ks), hint
+        assert {(c.K, c.sk) for c in kc.GEMM_KLOOP_CASES if c.tile == hint and c.sk > 1} == {(320, 2), (192, 3)}
+        assert general == any(c.form == "gelu" for c in kc.GEMM_KLOOP_CASES if c.tile == hint)
+        assert tail == ({c.M for c in kc.GEMM_EDGE_CASES if c.tile == hint} >= {1153, 1169, 1184})
+    assert all(c.M <= 2400 and c.N <= 960 and (c.K <= 704 or c in kc.GEMM_AUTO_SPLIT_CASES or c.K == 2048) for c in _new_gemm_cases())
+    assert {"bare", "bias", "full", "gelu", "f32", "f32 res32", "f32 res16", "accum16", "accum32", "alpha", "rowbias slice", "C slice8", "C slice4",
+            "res slice", "colstats", "colstats+res"} <= {c.form for c in kc.GEMM_FORMS}
+
+
+def test_gemm_check_cases_keep_their_kernels(dumper):      # (the fixture: the tables are for 256 CUs)
+    import kernel_checks as kc
+    want = {t: text for text, tags in CHECK_GEMM_KERNELS.items() for t in tags}
+    for c in _new_gemm_cases():
+        assert _gemm_said(c) == want[kc.gemm_tag(c)], c
+    want = {t: text for text, tags in CHECK_GEMM_EXISTING_KERNELS.items() for t in tags}
+    for label, c, override in kc.check_gemm_pinned():
+        assert _gemm_said(c, override) == want[label], label
+    # every new case runs on the row its tile hint names, in the instantiation its form asks for
+    for c in kc.GEMM_KLOOP_CASES + kc.GEMM_EDGE_CASES + kc.GEMM_FORMS:
+        pl, form = kc.gemm_plan(c), kc.gemm_form(c)
+        tm, tn, kt, st = kc.GEMM_TILES[c.tile][:4]
+        general = bool(form.get("gelu")) or form.get("rowbias", 32) % 32 != 0
+        assert (pl.tile_m, pl.tile_n) == (tm, tn) and pl.stages in (0, st) and pl.splitk == max(c.sk, 1), c
+        assert ((", true, 64>" in _gemm_said(c)) or ("_kernel<0, true, false>" in _gemm_said(c)) or ("320, true>" in _gemm_said(c))) == general, c
+    # the three reduce kernels are each named for the split-K forms, on every kernel family
+    for c in kc.GEMM_FORMS:
+        if c.sk > 1:
+            assert _gemm_said(c).split(" ")[-1] == kc.GEMM_FORM_SPLITK[c.form], c
+    # the automatic split-K falls back to ONE pass without its workspace and the query says so; an explicit one is refused like the launch (-12)
+    c = kc.GEMM_AUTO_SPLIT_CASES[0]
+    d, k = kc.gemm_desc(c), _C.GemmKernel()
+    assert _C.load().e4t_gemm_kernel(C.byref(d), C.byref(k)) == 0 and k.splitk == 2 and k.reduce == b"splitk_reduce8_kernel" and k.store == 3
+    d.workspace, d.workspace_bytes = None, 0
+    assert _C.load().e4t_gemm_kernel(C.byref(d), C.byref(k)) == 0 and k.splitk == 1 and k.reduce is None and k.store == 0
+    d.splitk = 2
+    assert _C.load().e4t_gemm_kernel(C.byref(d), C.byref(k)) == -12 and _C.load().e4t_gemm_tn_kernel(C.byref(kc.gemm_desc(kc.TnCase(300, 168, 152, 2, "f32"), ws_bytes=16, ws=1 << 24)), C.byref(k)) == -12
+    # a fused GEGLU descriptor the launch would refuse: E4T_ERR_NO_FUSED with the launch's message (here: a shape whose plan is the 256 x 256 tile)
+    d = _C.GemmDesc(A=1 << 24, B=1 << 24, C=1 << 24, aux=1 << 24, M=4096, N=2560, K=8192, K1=8192, lda=8192, ldb=8192, ldc=2560, ldaux=1280, batch=1, alpha=1.0,
+                    flags=_C.EPI_GEGLU)
+    assert _C.load().e4t_gemm_kernel(C.byref(d), C.byref(k)) == _C.ERR_NO_FUSED and b"fused GEGLU" in _C.load().e4t_last_error()
+    assert _C.load().e4t_gemm_plan(C.byref(d), C.byref(_C.GemmPlan())) == _C.ERR_NO_FUSED
+
+
+# Every (kernel symbol, store path) e4t_gemm_kernel / e4t_gemm_tn_kernel return over the gemm and tn items of the dispatch corpus, the step table's
+# included, and every reduce kernel.  The store path is a run-time branch of write_tile, so symbol x store path is the unit the checks must reach.
+ALL_STORES = ("bf16-staged", "f32-direct", "scalar", "splitk-partial")
+GEMM_KERNEL_STORES = {
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 2, true, 64>": ("bf16-staged", "scalar", "splitk-partial"),
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 3, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<128, 128, 4, 2, 0, 4, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 2, true, 64>": ("bf16-staged", "splitk-partial"),
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 3, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<128, 160, 4, 1, 0, 4, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<256, 128, 4, 2, 0, 3, false, 32>": ALL_STORES,
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 2, true, 64>": ("bf16-staged", "splitk-partial"),
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, false, 64>": ALL_STORES,
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 3, true, 64>": ("bf16-staged", "scalar", "splitk-partial"),
+    "gemm_dma_kernel<64, 64, 2, 2, 0, 4, false, 64>": ALL_STORES,
+    "gemm_kernel": ("bf16-staged",),
+    "gemm_pp_kernel<0, false, false>": ALL_STORES,
+    "gemm_pp_kernel<0, true, false>": ("bf16-staged", "splitk-partial"),
+    "gemm_pq_kernel<0, 320, false>": ALL_STORES,
+    "gemm_pq_kernel<0, 320, true>": ("bf16-staged", "splitk-partial"),
+    "gemm_tn_kernel": ("bf16-staged", "scalar", "splitk-partial"),
+}
+GEMM_REDUCE_KERNELS = {"splitk_reduce_kernel", "splitk_reduce8_kernel", "splitk_reduce4f_kernel"}
+# the eleven fused-GEGLU instantiations (gemm.hip, kVariants: CAP_GEGLU): reached through the shapes of tests/test_ff_fused_gpu.py, always bf16-staged
+GEMM_GEGLU_KERNELS = {
+    "gemm_dma_geglu_kernel<128, 128, 4, 2, 2, 64, 1>",
+    "gemm_dma_geglu_kernel<128, 128, 4, 2, 2, 64, 2>",
+    "gemm_dma_geglu_kernel<128, 128, 4, 2, 4, 64, 2>",
+    "gemm_dma_geglu_kernel<128, 160, 4, 1, 2, 64, 1>",
+    "gemm_dma_geglu_kernel<128, 160, 4, 1, 3, 64, 2>",
+    "gemm_dma_geglu_kernel<256, 128, 4, 2, 3, 32, 1>",
+    "gemm_dma_geglu_kernel<256, 128, 4, 2, 3, 32, 2>",
+    "gemm_dma_geglu_kernel<64, 64, 2, 2, 3, 64, 1>",
+    "gemm_dma_geglu_kernel<64, 64, 2, 2, 4, 64, 2>",
+    "gemm_pq_geglu_kernel<320, 1>",
+    "gemm_pq_geglu_kernel<320, 2>",
+}
+# symbol -> why no check of this file's tables executes it
+GEMM_KERNELS_NOT_REACHED = {
+    "gemm_kernel": "the register-staged fallback: chosen only for an operand beyond 4 GB or under the E4T_GEMM_REGSTAGE switch (read once per process); "
+                   "tests/test_gemm_regstage_gpu.py runs it in a child process",
+}
+
+
+def _geglu_symbols():
+    """the kernels the fused feed-forward launches of tests/test_ff_fused_gpu.py get: forward u = x . W1^T (N = 8 dim), backward dh = dy . W2 (N = 4 dim)"""
+    import test_ff_fused_gpu as ff
+    got = set()
+    for M, dim in ff.STEP + ff.SD2:
+        H, k, fake = 4 * dim, _C.GemmKernel(), 1 << 24
+        for d in (_C.GemmDesc(A=fake, B=fake, C=fake, aux=fake, bias=fake, M=M, N=2 * H, K=dim, K1=dim, lda=dim, ldb=dim, ldc=2 * H, ldaux=H, batch=1, alpha=1.0, flags=_C.EPI_GEGLU),
+                  _C.GemmDesc(A=fake, B=fake, C=fake, aux=fake, M=M, N=H, K=dim, K1=dim, lda=dim, ldb=dim, ldc=2 * H, ldaux=2 * H, batch=1, alpha=1.0, flags=_C.EPI_GEGLU_BWD)):
+            assert _C.load().e4t_gemm_kernel(C.byref(d), C.byref(k)) == 0, (M, dim, _C.load().e4t_last_error())
+            assert k.store == 0 and k.splitk == 1 and k.reduce is None
+            got.add(k.symbol.decode())
+    return got
+
+
+def test_gemm_checks_reach_every_kernel_the_launcher_can_choose(dumper):
+    """(symbol, store path) and the reduce kernels over the corpus == the clear-text sets above, and the checks execute each of them but the listed
+    exceptions: a kernel added to the variant table (or a rule changed so that one is no longer reached) fails here until a check has a shape for it"""
+    reachable, reduces = {}, set()
+    for item in dump.corpus():
+        if item.kind in ("gemm", "tn"):
+            f = dumper.gemm_kernel(item).split(" ")
+            if f[0] != "rc":
+                i = next(j for j, w in enumerate(f) if w.startswith("splitk") and w[6:].isdigit())
+                reachable.setdefault(" ".join(f[:i]), set()).add(f[i + 1])
+                reduces |= {w for w in f[i + 2:] if w.startswith("splitk_reduce")}
+    assert {s: tuple(p for p in ALL_STORES if p in st) for s, st in reachable.items()} == GEMM_KERNEL_STORES
+    assert reduces == GEMM_REDUCE_KERNELS
+    reached, reached_reduces = set(), set()
+    for text in list(CHECK_GEMM_KERNELS) + list(CHECK_GEMM_EXISTING_KERNELS):
+        sym, store, rest = re.match(r"(.*) splitk\d+ (\S+)(.*)$", text).groups()
+        reached.add((sym, store))
+        reached_reduces |= {w for w in rest.split() if w.startswith("splitk_reduce")}
+    units = {(s, p) for s, stores in GEMM_KERNEL_STORES.items() for p in stores}
+    excluded = {(s, p) for s, p in units if s in GEMM_KERNELS_NOT_REACHED}
+    assert set(GEMM_KERNELS_NOT_REACHED) <= set(GEMM_KERNEL_STORES) and not (reached & excluded)
+    # (the checks also run pairs the corpus does not hold, e.g. a GENERAL instantiation storing fp32 directly: reached may be the larger set)
+    assert units <= reached | excluded, sorted(units - reached - excluded)
+    assert reached_reduces == GEMM_REDUCE_KERNELS
+    assert _geglu_symbols() == GEMM_GEGLU_KERNELS and len(GEMM_GEGLU_KERNELS) == 11

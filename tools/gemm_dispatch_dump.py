@@ -22,6 +22,9 @@ E4T_CONV_NOSTRIP, ...) are read once per process: one run per setting.
     --record           rewrite tests/gemm_dispatch_record.txt (what tests/test_gemm_dispatch.py compares against) from this library
     --conv-check       hold e4t_conv3x3_kernel against the launch log: for every conv item of the corpus and of conv_geometry_corpus() the symbol
                        and split-K of the query equal the first field and the splitk of the log line (or both refuse with the same code)
+    --gemm-check       hold e4t_gemm_kernel / e4t_gemm_tn_kernel against the launch log: for every gemm and tn item of the corpus (the step table's
+                       included) the symbol, the split-K and the reduce kernel of the query equal the first field and the splitk of the launch's
+                       log line and the first field of its reduce line (or both refuse with the same code and text)
     --attn-launches    the 'attn' group as the launch log alone tells it (kernel symbols; workspace floats from
                        e4t_attention_bwd_workspace_floats): needs no e4t_attention_plan, so E4T_LIB may be a library older than that entry point
     --attn-check FILE  hold such a dump against e4t_attention_plan of this library; prints every row that differs (the record's 'attn' group
@@ -284,6 +287,16 @@ class Dumper:
             return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
         return "%s splitk%d" % (sym.value.decode(), sk.value)
 
+    def gemm_kernel(self, item, d=None):
+        """what e4t_gemm_kernel / e4t_gemm_tn_kernel say the launch of a gemm / tn item will run:
+        "<kernel symbol> splitk<n> <store path> [<reduce symbol>] [tail<r>] [colstats]" (pure host code, like the plan)"""
+        k = _C.GemmKernel()
+        rc = (self.lib.e4t_gemm_kernel if item.kind == "gemm" else self.lib.e4t_gemm_tn_kernel)(C.byref(d or make_desc(item)), C.byref(k))
+        if rc != 0:
+            return "rc %d %s" % (rc, self.lib.e4t_last_error().decode())
+        return " ".join(["%s splitk%d %s" % (k.symbol.decode(), k.splitk, _C.STORE_NAMES[k.store])] + ([k.reduce.decode()] if k.reduce else []) +
+                        (["tail%d" % k.tail_rows] if k.tail_rows else []) + (["colstats"] if k.colstats else []))
+
     def launch(self, item, d=None):
         """(rc, error text, [log lines])"""
         if item.kind == "attn":
@@ -367,6 +380,39 @@ def conv_check(dumper):
     return bad
 
 
+def gemm_check(dumper):
+    """rows on which e4t_gemm_kernel / e4t_gemm_tn_kernel and the launch log of e4t_gemm_nt / e4t_gemm_tn disagree, over every gemm and tn item of
+    the corpus.  The log carries the symbol, the split-K and the reduce kernel; store path, tail rows and colstats come from the same function
+    (gemm.hip: decide_launch / resolve_tn) and are counted here per (symbol, store path)."""
+    n = bad = refused = 0
+    seen = collections.Counter()
+    for item in corpus():
+        if item.kind not in ("gemm", "tn"):
+            continue
+        d = make_desc(item)
+        said = dumper.gemm_kernel(item, d)
+        rc, err, lines = dumper.launch(item, d)
+        if lines:
+            m = re.match(r"([^|]+)\|gemm\w* .* splitk(\d+) flags\d+\|", lines[0])
+            ran = ["%s splitk%s" % m.groups()] if m else [lines[0]]
+            ran += [l.split("|")[0] for l in lines[1:]]
+            f = said.split(" ") if not said.startswith("rc ") else [said]
+            i = next((j for j, w in enumerate(f) if w.startswith("splitk") and w[6:].isdigit()), 0)
+            got = [" ".join(f[:i + 1])] + [w for w in f[i + 2:] if w.startswith("splitk_reduce")]
+            seen[" ".join(f[:i]) + " | " + (f[i + 1] if len(f) > i + 1 else "?")] += 1
+        else:
+            ran, got = ["rc %d %s" % (rc, err)], [said]
+            refused += got == ran
+        n += 1
+        if got != ran:
+            bad += 1
+            print("DIFF %s %s: query %s, launch %s" % (item.kind, describe(item.kw), said, ran))
+    for sym, k in sorted(seen.items()):
+        print("%8d  %s" % (k, sym))
+    print("gemm: %d rows (%d refused alike), %d differ; %d (symbol, store path) pairs" % (n, refused, bad, len(seen)))
+    return bad
+
+
 def attn_launch_lines(dumper):
     """the 'attn' group as the launch log tells it: descriptor -> forward | dQ | dK/dV symbol | the workspace floats the library asks for"""
     for item in attn_corpus():
@@ -428,6 +474,7 @@ def main():
     ap.add_argument("--anchor", action="store_true")
     ap.add_argument("--record", action="store_true")
     ap.add_argument("--conv-check", action="store_true")
+    ap.add_argument("--gemm-check", action="store_true")
     ap.add_argument("--attn-launches", action="store_true")
     ap.add_argument("--attn-check", metavar="FILE")
     args = ap.parse_args()
@@ -450,6 +497,10 @@ def main():
             if not d.log:
                 sys.exit("--conv-check needs the launch half")
             return 1 if conv_check(d) else 0
+        if args.gemm_check:
+            if not d.log:
+                sys.exit("--gemm-check needs the launch half")
+            return 1 if gemm_check(d) else 0
         if args.attn_launches:
             if not d.log:
                 sys.exit("--attn-launches needs the launch half")
