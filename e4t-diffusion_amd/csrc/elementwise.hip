@@ -807,6 +807,46 @@ __global__ __launch_bounds__(256) void masked_mse_bwd_kernel(const float* __rest
   const float k = g[0] * 2.f / stats[1];
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) dpred[i] = k * wd[i];
 }
+
+// The scheduled pseudo-Huber / smooth-L1 loss (e4t_robust_loss_fwd): masked_mse_partial_kernel<true>'s sibling, the same
+// pixel walk and the same two partial rows, so masked_mse_final_kernel finishes it.  Per image c = ctab[t] (t = timesteps[b] clamped into
+// the table as diffuse_kernel clamps it; timesteps null = ctab[0]) and, with r = sqrt(d^2 + c^2), h = d^2 / (r + c) — which is r - c
+// without the cancellation that costs the textbook form up to 2e-2 at c = 1e3 —
+//   huber (kind 1): l = 2 c h, dl/dd = 2 c d / r;   smooth_l1 (kind 2): l = 2 h, dl/dd = 2 d / r.
+// With kh = k / 2 = c | 1 the row sums 2 * lam * w * kh * h and wd = lam * w * kh * d / r, half the gradient's numerator, which is what
+// masked_mse_bwd_kernel (g * 2 / den * wd) expects.  sqrtf and `/` are the IEEE ones; d == 0 gives h = 0 and wd = 0 as c > 0.
+__global__ __launch_bounds__(256) void robust_loss_partial_kernel(const float* __restrict__ pred, const float* __restrict__ target, const float* __restrict__ w,
+                                                                  const float* __restrict__ lam, const float* __restrict__ ctab,
+                                                                  const long long* __restrict__ timesteps, float* __restrict__ wd,
+                                                                  float* __restrict__ partial, int B, int C, int HW, int T, int kind, int nhwc) {
+  __shared__ float red[32];
+  const long long npix = (long long)B * HW;
+  float se = 0.f, sw = 0.f;
+  for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < npix; q += (long long)gridDim.x * 256) {
+    const long long b = q / HW;
+    const int p = (int)(q - b * HW);
+    long long t = timesteps ? timesteps[b] : 0;
+    t = t < 0 ? 0 : (t > T - 1 ? T - 1 : t);
+    const float cb = ctab[t], c2 = cb * cb;
+    float wq = w ? w[q] : 1.f;
+    sw += wq;
+    if (lam) wq = lam[b] * wq;
+    if (kind == 1) wq = wq * cb;                              // lam * w * k / 2
+    const float wq2 = 2.f * wq;
+    for (int c = 0; c < C; ++c) {
+      const long long it = (b * C + c) * HW + p;
+      const long long ip = nhwc ? q * C + c : it;
+      const float d = pred[ip] - target[it];
+      const float d2 = d * d;
+      const float r = sqrtf(d2 + c2);
+      if (wd) wd[ip] = wq * d / r;
+      se = fmaf(wq2, d2 / (r + cb), se);
+    }
+  }
+  se = block_sum(se, red);
+  sw = block_sum(sw, red + 16);
+  if (threadIdx.x == 0) { partial[blockIdx.x] = se; partial[gridDim.x + blockIdx.x] = sw; }
+}
 }  // namespace
 
 extern "C" int e4t_masked_mse_fwd(const float* pred, const float* target, const float* w, float* wd, float* stats, int B, int C, int HW, int pred_nhwc,
@@ -829,6 +869,22 @@ extern "C" int e4t_weighted_mse_fwd(const float* pred, const float* target, cons
   const int nb = (int)min(cdivl((long long)B * HW, 256), (long long)MMSE_MAX_BLOCKS);
   hipLaunchKernelGGL(masked_mse_partial_kernel<true>, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, lam, wd, stats + 2, B, C, HW, pred_nhwc);
   E4T_CHECK_LAUNCH("weighted_mse_partial_kernel");
+  hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)(stats + 2), nb, C, stats);
+  E4T_CHECK_LAUNCH("masked_mse_final_kernel");
+  return 0;
+}
+// the scheduled pseudo-Huber / smooth-L1 loss in the same two launches; the backward is e4t_masked_mse_bwd on the saved
+// lam * w * (k / 2) * d / r, as for the weighted loss
+extern "C" int e4t_robust_loss_fwd(const float* pred, const float* target, const float* w, const float* lam, const float* ctab, const long long* timesteps,
+                                   float* wd, float* stats, int B, int C, int HW, int T, int kind, int pred_nhwc, e4t_stream s) {
+  E4T_REQUIRE(pred && target && ctab && stats && B > 0 && C > 0 && HW > 0,
+              "robust_loss_fwd: bad arguments (pred, target, ctab, stats non-null; B, C, HW > 0)");
+  E4T_REQUIRE(T >= 1, "robust_loss_fwd: T = %d, the table needs at least one entry", T);
+  E4T_REQUIRE(kind == E4T_LOSS_HUBER || kind == E4T_LOSS_SMOOTH_L1, "robust_loss_fwd: kind = %d must be 1 (huber) or 2 (smooth_l1)", kind);
+  const int nb = (int)min(cdivl((long long)B * HW, 256), (long long)MMSE_MAX_BLOCKS);
+  hipLaunchKernelGGL(robust_loss_partial_kernel, dim3(nb), dim3(256), 0, (hipStream_t)s, pred, target, w, lam, ctab, timesteps, wd, stats + 2, B, C, HW, T,
+                     kind, pred_nhwc);
+  E4T_CHECK_LAUNCH("robust_loss_partial_kernel");
   hipLaunchKernelGGL(masked_mse_final_kernel, dim3(1), dim3(256), 0, (hipStream_t)s, (const float*)(stats + 2), nb, C, stats);
   E4T_CHECK_LAUNCH("masked_mse_final_kernel");
   return 0;

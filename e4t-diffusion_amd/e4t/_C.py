@@ -119,6 +119,7 @@ SIGNATURES = {
     "e4t_masked_mse_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "e4t_masked_mse_bwd": (i32, [vp, vp, vp, vp, i64, vp]),
     "e4t_weighted_mse_fwd": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "e4t_robust_loss_fwd": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "e4t_diffuse": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, vp]),
     "e4t_softmax_rows": (i32, [vp, i64, i32, i32, vp]),
     "e4t_im2col3_rgb": (i32, [vp, vp, i32, i32, i32, vp]),
@@ -154,6 +155,7 @@ CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 1, 2, 3, 4, 5
 WO_STORE_F32, WO_OFFSETS_ONLY = 1, 2
 SAMPLER_MAX_HIST, SAMPLER_ROW = 4, 16
 MASKED_MSE_STATS = 2050
+LOSS_HUBER, LOSS_SMOOTH_L1 = 1, 2      # e4t_robust_loss_fwd's kind
 COMM_F32, COMM_BF16 = 0, 1
 COMM_SUM, COMM_AVG, COMM_MIN, COMM_MAX = 0, 1, 2, 3
 OP_SILU, OP_SILU_BWD, OP_GELU, OP_GELU_BWD, OP_LRELU, OP_LRELU_BWD, OP_QGELU, OP_QGELU_BWD = range(8)

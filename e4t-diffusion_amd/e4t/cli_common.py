@@ -271,7 +271,7 @@ def apply_tome_args(unet, args):
     return tome.apply_tome(unet, args.tome_ratio, use_rand=not args.tome_no_rand, generator=g)
 
 
-# ---- the diffusion objective's options (E4TTrainer(snr_gamma=..., noise_offset=...)): properties of the run, so config.json
+# ---- the diffusion objective's options (E4TTrainer(snr_gamma=..., noise_offset=..., loss_type=...)): properties of the run, so config.json
 # records them like reg_lambda; tuning_e4t.py takes its own flags and inherits neither from the pre-trained run's config.json ----
 def add_objective_args(p):
     p.add_argument("--snr_gamma", type=float, default=None,
@@ -280,6 +280,15 @@ def add_objective_args(p):
     p.add_argument("--noise_offset", type=float, default=0.0,
                    help="noise offset: a per-(image, channel) N(0, 1) constant times this scale is added to the noise (0.05 - 0.1 is usual); "
                         "must be >= 0, default 0 = off")
+    p.add_argument("--loss_type", choices=("l2", "huber", "smooth_l1"), default="l2",
+                   help="the diffusion loss: l2 (default, squared error), or the scheduled pseudo-Huber loss / its smooth-L1 form, quadratic "
+                        "for small residuals and linear for large ones (DESIGN §2.4b)")
+    p.add_argument("--huber_c", type=float, default=0.1,
+                   help="the Huber parameter: the transition point under --huber_schedule constant, its floor at the noisiest timestep "
+                        "otherwise; finite and > 0, and <= 1 unless the schedule is constant (default 0.1)")
+    p.add_argument("--huber_schedule", choices=("constant", "exponential", "snr"), default="snr",
+                   help="how the Huber parameter depends on the timestep: constant, exponential (1 at t = 0 decaying to huber_c) or snr "
+                        "((1 - huber_c) / (1 + sigma_t)^2 + huber_c, default)")
 
 
 def check_objective_args(p, args):
@@ -287,6 +296,17 @@ def check_objective_args(p, args):
         p.error("--snr_gamma must be > 0")
     if not args.noise_offset >= 0.0:
         p.error("--noise_offset must be >= 0")
+    if not (args.huber_c > 0.0 and args.huber_c != float("inf")):
+        p.error("--huber_c must be finite and > 0")
+    if args.huber_schedule != "constant" and args.huber_c > 1.0:
+        p.error(f"--huber_c must be <= 1 with --huber_schedule {args.huber_schedule}")
+
+
+def objective_kwargs(args):
+    """the E4TTrainer keyword arguments of add_objective_args' flags (a namespace without them: all off)"""
+    return dict(snr_gamma=getattr(args, "snr_gamma", None), noise_offset=getattr(args, "noise_offset", 0.0),
+                loss_type=getattr(args, "loss_type", "l2"), huber_c=getattr(args, "huber_c", 0.1),
+                huber_schedule=getattr(args, "huber_schedule", "snr"))
 
 
 # ---- EMA of the trained weights (E4TTrainer(ema_decay=...)): like ToMe a choice of the command line, config.json does not record it --------------

@@ -705,6 +705,35 @@ class HipBackend:
         """dpred = g * 2 * wd / den for weighted_mse's wd = lam * w * d: masked_mse_bwd's arithmetic, and its entry point"""
         return self.masked_mse_bwd(wd, stats, g)
 
+    def robust_loss(self, pred, target, ctab, timesteps, kind, lam=None, w=None, save=True):
+        """The scheduled pseudo-Huber (kind "huber" / 1) or smooth-L1 ("smooth_l1" / 2) loss of functional.robust_loss ->
+        (loss (0-dim), wd, stats): weighted_mse's operands and layouts plus ctab fp32 [T] and timesteps int64 [B] (None = ctab[0] for
+        every image), both read on the device.  wd = lam * w * (k / 2) * d / sqrt(d^2 + c^2) in pred's layout is what robust_loss_bwd needs."""
+        B, Cn = pred.shape[0], pred.shape[1]
+        HW = pred.numel() // (B * Cn)
+        kind = {"huber": _C.LOSS_HUBER, "smooth_l1": _C.LOSS_SMOOTH_L1}.get(kind, kind)
+        assert pred.dtype == f32 and target.dtype == f32 and pred.dim() == 4 and target.shape == pred.shape
+        assert ctab.dtype == f32 and ctab.dim() == 1 and ctab.device == pred.device
+        assert timesteps is None or (timesteps.dtype == torch.int64 and timesteps.numel() == B and timesteps.device == pred.device)
+        assert w is None or (w.dtype == f32 and w.numel() == B * HW)
+        assert lam is None or (lam.dtype == f32 and lam.numel() == B)
+        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
+        if not nhwc:
+            pred = pred.contiguous()
+        target, ctab = target.contiguous(), ctab.contiguous()
+        timesteps = None if timesteps is None else timesteps.contiguous()
+        w = None if w is None else w.contiguous()
+        lam = None if lam is None else lam.contiguous()
+        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
+        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
+        _C.check(self.lib.e4t_robust_loss_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(lam), _ptr(ctab), _ptr(timesteps), _ptr(wd), _ptr(stats), B, Cn, HW,
+                                              ctab.numel(), int(kind), int(nhwc), _stream()), "e4t_robust_loss_fwd")
+        return stats[0], wd, stats
+
+    def robust_loss_bwd(self, wd, stats, g):
+        """dpred = g * 2 * wd / den for robust_loss's wd: masked_mse_bwd's arithmetic, and its entry point"""
+        return self.masked_mse_bwd(wd, stats, g)
+
     def diffuse(self, x0, noise, timesteps, coef, z=None, offset=0.0, v_prediction=False):
         """(noisy, target, lam) of functional.diffusion_objective in one launch: x0, noise fp32 [B, C, h, w]; timesteps int64 [B] and
         coef fp32 [T, 3] on the device (nothing is read on the host); z fp32 [B, C] with offset > 0"""

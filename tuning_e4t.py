@@ -114,7 +114,7 @@ def setup(args, dev):
     tr = E4TTrainer(unet, enc, text, vae, lr=lr, domain_embed_scale=args.domain_embed_scale, reg_lambda=args.reg_lambda,
                     prediction_type=getattr(pretrained_args, "prediction_type", None) or "epsilon", class_token_id=class_token_id,
                     empty_prompt_ids=empty_ids.to(dev), device=dev, tuning=True, max_grad_norm=args.max_grad_norm,
-                    snr_gamma=getattr(args, "snr_gamma", None), noise_offset=getattr(args, "noise_offset", 0.0))    # its own flags, not the pre-trained run's
+                    **cc.objective_kwargs(args))    # its own flags, not the pre-trained run's
     tr.prepare(args.train_batch_size)
     print(f"Number of Trainable Parameters: {tr.flat.numel * 1.e-6:.2f} M")
     import random
