@@ -268,6 +268,108 @@ __global__ __launch_bounds__(256) void ema_update_kernel(float* ema, const float
   }
 }
 
+// ---- AdamW with block-wise 8-bit moments (the format is DEFINED by e4t/optimization.py: quantize_blockwise) ----
+// m and v live as one byte each (an index into a sorted 256-entry codebook: signed for m, unsigned for v) plus one fp32 scale per 256
+// elements: 16.06 B of HBM traffic per parameter instead of 28 (24.06 / 36 with the EMA) -- though as measured the kernel is bound by its per-element
+// work (divisions, the two searches), not by HBM, and buys memory rather than time.  One wave64 owns one 256-element block, four
+// consecutive elements per lane (a float4 of p and g, one packed word of each code buffer); the block maxima are wave reductions, so
+// there is no barrier in the loop.  Per workgroup the two codebooks sit in LDS twice: sorted (dequantisation, the neighbour comparison)
+// and as an implicit search tree in breadth-first order (node k's children are 2k and 2k + 1), whose level l occupies 2^l consecutive
+// words: the eight reads of a search then fall on distinct banks or on one address, where a binary search over the sorted table would
+// read words 128 / 64 / 32 apart (one bank) in its first levels.
+// rank(y) = #{j < 255: code[j] < y}; q = rank or rank - 1, whichever is nearer in fp32, the lower index on a tie.
+__device__ __forceinline__ int adam8_quant(const float* code, const float* tree, float x, float a) {
+  const float y = a > 0.f ? x / a : 0.f;
+  int k = 1;
+#pragma unroll
+  for (int l = 0; l < 8; ++l) k = 2 * k + (tree[k] < y ? 1 : 0);
+  const int hi = k - 256, lo = hi > 0 ? hi - 1 : 0;
+  return (y - code[lo] <= code[hi] - y) ? lo : hi;
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adamw8_kernel(float* p, const float* g, unsigned char* qm, unsigned char* qv, float* am, float* av, float* ema,
+                                                     long long n, const float* code_m, const float* code_v, float lr, float b1, float b2, float eps,
+                                                     float wd, float bc1, float bc2_sqrt, float gscale, float ema_w, const float* hyper) {
+  __shared__ float s_cm[256], s_cv[256], s_tm[256], s_tv[256];
+  {
+    const int t = threadIdx.x;
+    // tree node t (1..255) at level L = floor(log2 t), offset j = t - 2^L, is the sorted entry (2j + 1) * 2^(7 - L) - 1; node 0 is unused
+    const int L = 31 - __clz(t | 1), idx = t ? (((2 * (t - (1 << L)) + 1) << (7 - L)) - 1) : 0;
+    s_cm[t] = code_m[t]; s_cv[t] = code_v[t];
+    s_tm[t] = code_m[idx]; s_tv[t] = code_v[idx];
+  }
+  __syncthreads();
+  if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; gscale = hyper[3]; if constexpr (EMA) ema_w = hyper[4]; }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const long long nblk = (n + 255) / 256;
+  for (long long blk = (long long)blockIdx.x * 4 + wave; blk < nblk; blk += (long long)gridDim.x * 4) {      // wave-uniform trip count
+    const long long i = blk * 256 + lane * 4;
+    const int cnt = i >= n ? 0 : (n - i >= 4 ? 4 : (int)(n - i));      // valid elements of this lane: 4, or fewer in the short last block
+    const float a_m = am[blk], a_v = av[blk];
+    float pp[4] = {0.f, 0.f, 0.f, 0.f}, gg[4] = {0.f, 0.f, 0.f, 0.f}, ee[4] = {0.f, 0.f, 0.f, 0.f};
+    unsigned wm = 0, wv = 0;
+    if (cnt == 4) {
+      const float4 P = *(const float4*)(p + i), G = *(const float4*)(g + i);
+      pp[0] = P.x; pp[1] = P.y; pp[2] = P.z; pp[3] = P.w;
+      gg[0] = G.x * gscale; gg[1] = G.y * gscale; gg[2] = G.z * gscale; gg[3] = G.w * gscale;
+      wm = *(const unsigned*)(qm + i); wv = *(const unsigned*)(qv + i);
+      if constexpr (EMA) { const float4 E = *(const float4*)(ema + i); ee[0] = E.x; ee[1] = E.y; ee[2] = E.z; ee[3] = E.w; }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (k >= cnt) break;
+        pp[k] = p[i + k]; gg[k] = g[i + k] * gscale;
+        wm |= (unsigned)qm[i + k] << (8 * k); wv |= (unsigned)qv[i + k] << (8 * k);
+        if constexpr (EMA) ee[k] = ema[i + k];
+      }
+    }
+    float mm[4], vv[4], xm = 0.f, xv = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const bool ok = k < cnt;      // a lane's missing elements carry zeros: they leave the block maxima alone
+      mm[k] = ok ? s_cm[(wm >> (8 * k)) & 255] * a_m : 0.f;
+      vv[k] = ok ? s_cv[(wv >> (8 * k)) & 255] * a_v : 0.f;
+      // adamw_kernel.inc's arithmetic, in its order, with the contractions adamw_kernel compiles to (-ffp-contract=fast) written out: the decay
+      // 1 - lr * wd, b * moment + (1 - b) * gradient term and decay * p - step are one fma each, and no other product feeds a sum, so nothing is
+      // left for the compiler to fuse one way in one instantiation and another way in the other; p moves by the unquantised new moments
+      mm[k] = fmaf(b1, mm[k], (1.f - b1) * gg[k]);
+      vv[k] = fmaf(b2, vv[k], (1.f - b2) * gg[k] * gg[k]);
+      const float denom = sqrtf(vv[k]) / bc2_sqrt + eps;
+      // (adamw_kernel's last partial quad goes through its scalar loop, where decay * p - step stayed a product and a difference: the lane that
+      // holds such a quad here is the same lane of the same buffer, and does the same, so that from zero moments EVERY p' is e4t_adamw's.
+      // The empty asm keeps the backend from fusing that product: -ffp-contract=fast is a property of the whole file.)
+      const float decay = fmaf(-lr, wd, 1.f), upd = (lr / bc1) * mm[k] / denom;
+      float prod = decay * pp[k];
+      asm volatile("" : "+v"(prod));
+      pp[k] = cnt == 4 ? fmaf(decay, pp[k], -upd) : prod - upd;
+      xm = fmaxf(xm, fabsf(mm[k])); xv = fmaxf(xv, vv[k]);
+    }
+    xm = wave_max(xm); xv = wave_max(xv);
+    wm = 0; wv = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      wm |= (unsigned)adam8_quant(s_cm, s_tm, mm[k], xm) << (8 * k);
+      wv |= (unsigned)adam8_quant(s_cv, s_tv, vv[k], xv) << (8 * k);
+    }
+    if (cnt == 4) {
+      *(float4*)(p + i) = make_float4(pp[0], pp[1], pp[2], pp[3]);
+      *(unsigned*)(qm + i) = wm; *(unsigned*)(qv + i) = wv;
+      if constexpr (EMA)
+        *(float4*)(ema + i) = make_float4(ema_f(ee[0], pp[0], ema_w), ema_f(ee[1], pp[1], ema_w), ema_f(ee[2], pp[2], ema_w), ema_f(ee[3], pp[3], ema_w));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        if (k >= cnt) break;
+        p[i + k] = pp[k];
+        qm[i + k] = (unsigned char)(wm >> (8 * k)); qv[i + k] = (unsigned char)(wv >> (8 * k));
+        if constexpr (EMA) ema[i + k] = ema_f(ee[k], pp[k], ema_w);
+      }
+    }
+    if (lane == 0) { am[blk] = xm; av[blk] = xv; }
+  }
+}
+
 // ---- AdamW of the E4T head's stacked first_linears weights with the gradient formed IN REGISTERS (round 6) ----
 // The n = 129 weight gradients are rank-K products dW_i[r][c] = sum_k G[k][r] * Z[k][i*cols + c] (K = images of the step: the batch, or
 // under data parallelism every rank's rows gathered; encoder.py:159-162): 845 MB of fp32 that the step used to write (batched GEMM), read
@@ -538,6 +640,31 @@ extern "C" int e4t_adamw_ema(float* p, const float* g, float* m, float* v, float
   hipLaunchKernelGGL(adamw_ema_kernel, dim3(grid_for((n + 3) / 4, 4096)), dim3(256), 0, (hipStream_t)s, p, g, m, v, ema, n, hyper_dev ? 0.f : lr, beta1, beta2, eps,
                      weight_decay, bc1, bc2, hyper_dev ? 1.f : grad_scale, hyper_dev ? 0.f : ema_w, hyper_dev);
   E4T_CHECK_LAUNCH("adamw_ema_kernel");
+  return 0;
+}
+extern "C" int e4t_adamw8(float* p, const float* g, void* qm, void* qv, float* absmax_m, float* absmax_v, float* ema, long long n, const float* code_m,
+                          const float* code_v, float lr, float beta1, float beta2, float eps, float weight_decay, int step, float grad_scale, float ema_w,
+                          const float* hyper_dev, e4t_stream s) {
+  E4T_REQUIRE(p && g && qm && qv && absmax_m && absmax_v && code_m && code_v && n > 0 && (hyper_dev || step >= 1), "adamw8: bad arguments");
+  E4T_REQUIRE((((uintptr_t)p | (uintptr_t)g | (uintptr_t)ema | (uintptr_t)hyper_dev) & 15) == 0, "adamw8: p, g, ema and hyper_dev must be 16-B aligned");
+  E4T_REQUIRE((((uintptr_t)qm | (uintptr_t)qv | (uintptr_t)absmax_m | (uintptr_t)absmax_v | (uintptr_t)code_m | (uintptr_t)code_v) & 3) == 0,
+              "adamw8: codes, scales and codebooks must be 4-B aligned");
+  const float bc1 = hyper_dev ? 1.f : 1.f - powf(beta1, (float)step), bc2 = hyper_dev ? 1.f : sqrtf(1.f - powf(beta2, (float)step));
+  const int grid = grid_for((n + 3) / 4, 4096);      // 1024 elements (four blocks of 256, one per wave) per workgroup and trip, as adamw_kernel
+  const double bytes = 16.0 * (double)n + 16.0 * (double)((n + 255) / 256) + (ema ? 8.0 * (double)n : 0.0);
+#define E4T_ADAMW8_ARGS                                                                                                                                      \
+  p, g, (unsigned char*)qm, (unsigned char*)qv, absmax_m, absmax_v, ema, n, code_m, code_v, hyper_dev ? 0.f : lr, beta1, beta2, eps, weight_decay, bc1, bc2, \
+      hyper_dev ? 1.f : grad_scale, hyper_dev ? 0.f : ema_w, hyper_dev
+  if (ema) {
+    E4T_LOG_LAUNCH("adamw8_ema_kernel|n%lld grid%d|%.0f|0", (long long)n, grid, bytes);
+    hipLaunchKernelGGL(adamw8_kernel<true>, dim3(grid), dim3(256), 0, (hipStream_t)s, E4T_ADAMW8_ARGS);
+    E4T_CHECK_LAUNCH("adamw8_ema_kernel");
+  } else {
+    E4T_LOG_LAUNCH("adamw8_kernel|n%lld grid%d|%.0f|0", (long long)n, grid, bytes);
+    hipLaunchKernelGGL(adamw8_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)s, E4T_ADAMW8_ARGS);
+    E4T_CHECK_LAUNCH("adamw8_kernel");
+  }
+#undef E4T_ADAMW8_ARGS
   return 0;
 }
 extern "C" int e4t_adamw_rank_ema(float* p, float* m, float* v, float* ema, const void* G, const void* Z, int n, int rows, int cols, int K, int ldg,

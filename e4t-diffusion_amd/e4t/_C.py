@@ -131,6 +131,7 @@ SIGNATURES = {
     "e4t_adamw_ema": (i32, [vp, vp, vp, vp, vp, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, vp]),
     "e4t_adamw_rank_ema": (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, f32, f32, f32, f32, f32, i32, f32, f32, vp, vp]),
     "e4t_ema_update": (i32, [vp, vp, i64, f32, vp, vp]),
+    "e4t_adamw8": (i32, [vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, f32, f32, f32, f32, f32, i32, f32, f32, vp, vp]),
     "e4t_sumsq_partial": (i32, [vp, i64, vp, i32, vp]),
     "e4t_tome_plan_ints": (sz, [i32, i32]),
     "e4t_tome_match": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),

@@ -289,6 +289,9 @@ def add_objective_args(p):
     p.add_argument("--huber_schedule", choices=("constant", "exponential", "snr"), default="snr",
                    help="how the Huber parameter depends on the timestep: constant, exponential (1 at t = 0 decaying to huber_c) or snr "
                         "((1 - huber_c) / (1 + sigma_t)^2 + huber_c, default)")
+    p.add_argument("--optimizer_state_bits", type=int, choices=(32, 8), default=32,
+                   help="AdamW's moments: 32 (default, two fp32 buffers) or 8 (block-wise 8-bit: one byte per moment plus one fp32 scale per 256 "
+                        "elements, about 2 instead of 8 bytes of optimiser state per parameter; DESIGN §2.3d)")
 
 
 def check_objective_args(p, args):
@@ -303,10 +306,10 @@ def check_objective_args(p, args):
 
 
 def objective_kwargs(args):
-    """the E4TTrainer keyword arguments of add_objective_args' flags (a namespace without them: all off)"""
+    """the E4TTrainer keyword arguments of add_objective_args' flags (a namespace without them: all off, 32-bit optimiser state)"""
     return dict(snr_gamma=getattr(args, "snr_gamma", None), noise_offset=getattr(args, "noise_offset", 0.0),
                 loss_type=getattr(args, "loss_type", "l2"), huber_c=getattr(args, "huber_c", 0.1),
-                huber_schedule=getattr(args, "huber_schedule", "snr"))
+                huber_schedule=getattr(args, "huber_schedule", "snr"), optimizer_state_bits=getattr(args, "optimizer_state_bits", 32))
 
 
 # ---- EMA of the trained weights (E4TTrainer(ema_decay=...)): like ToMe a choice of the command line, config.json does not record it --------------

@@ -796,6 +796,20 @@ class HipBackend:
         self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_ema_update(_ptr(ema), _ptr(p), p.numel(), ema_w, _ptr(w_dev), _stream()), "e4t_ema_update"),
                     12.0 * p.numel())
 
+    def adamw8(self, p, g, qm, qv, absmax_m, absmax_v, code_m, code_v, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, ema=None, ema_w=0.0, hyper=None):
+        """adamw over block-wise 8-bit moments (optimization.quantize_blockwise is the format): qm / qv uint8 [n], absmax_* fp32 [ceil(n / 256)],
+        code_* the fp32 [256] codebooks on the device.  ema: the average, moved in the same pass; hyper: device fp32 [4] ([8] with ema) as in adamw_ema."""
+        n = p.numel()
+        nb = -(-n // 256)
+        assert p.dtype == f32 and g.dtype == f32 and g.numel() == n and qm.dtype == torch.uint8 and qv.dtype == torch.uint8
+        assert qm.numel() == n and qv.numel() == n and absmax_m.dtype == f32 and absmax_v.dtype == f32 and absmax_m.numel() == nb and absmax_v.numel() == nb
+        assert code_m.dtype == f32 and code_v.dtype == f32 and code_m.numel() == 256 and code_v.numel() == 256
+        assert ema is None or (ema.dtype == f32 and ema.numel() == n)
+        assert hyper is None or hyper.numel() == (8 if ema is not None else 4)
+        self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_adamw8(
+            _ptr(p), _ptr(g), _ptr(qm), _ptr(qv), _ptr(absmax_m), _ptr(absmax_v), _ptr(ema), n, _ptr(code_m), _ptr(code_v), lr, beta1, beta2, eps, wd,
+            int(step), grad_scale, ema_w, _ptr(hyper), _stream()), "e4t_adamw8"), 16.0 * n + 16.0 * nb + (8.0 * n if ema is not None else 0.0))
+
     def im2col_T(self, x, B, Hin, Win, Hout, Wout, mode):
         """bf16 [B*Hin*Win, C] -> [9*C, ld] with ld = B*Hout*Wout rounded up to 8 (zero padded): B operand of the wgrad GEMM"""
         assert x.is_contiguous()

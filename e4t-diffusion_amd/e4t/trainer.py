@@ -27,7 +27,7 @@ import torch.nn.functional as F
 from . import functional as Fn
 from . import ops
 from . import tome
-from .optimization import ema_weight
+from .optimization import ADAM8_BLOCK, Adam8State, dequantize_blockwise, dynamic_codebook, ema_weight
 
 f32 = torch.float32
 
@@ -155,7 +155,7 @@ class E4TTrainer:
                  empty_prompt_ids: Optional[torch.Tensor] = None, process_group=None, device=None, tuning=False,
                  max_grad_norm: Optional[float] = None, head_factor_exchange=True, collectives="torch", ema_decay: Optional[float] = None,
                  snr_gamma: Optional[float] = None, noise_offset: float = 0.0, loss_type: str = "l2", huber_c: float = 0.1,
-                 huber_schedule: str = "snr"):
+                 huber_schedule: str = "snr", optimizer_state_bits: int = 32):
         self.unet, self.encoder, self.text_encoder, self.vae = unet, e4t_encoder, text_encoder, vae
         # data parallel: all-gather the two small factors of the 129-slot head's weight gradient instead of all-reducing the 845 MB
         # stack (_exchange_head_factors); needs the same per-rank batch size on every rank.  False = the stack rides the all-reduce.
@@ -225,6 +225,12 @@ class E4TTrainer:
             assert bool(((self.acp > 0) & (self.acp < 1)).all()), "the Huber schedules need 0 < alphas_cumprod < 1"
             self.huber_tab = huber_table(self.acp, huber_c, huber_schedule)
         self.max_grad_norm = max_grad_norm
+        # AdamW's moments: 32 = two flat fp32 buffers (the default path, unchanged); 8 = one byte each plus one fp32 scale per 256
+        # elements (optimization.Adam8State), updated by e4t_adamw8 in every branch of optimizer_step.  exp_avg / exp_avg_sq are then None.
+        if optimizer_state_bits not in (32, 8):
+            raise ValueError(f"optimizer_state_bits={optimizer_state_bits!r}: 32 or 8")
+        self.state_bits = int(optimizer_state_bits)
+        self.adam8 = None
         self.tuning = tuning
         self._armed = False
         named = select_trainable(unet, e4t_encoder, tuning=tuning, text_encoder=text_encoder)
@@ -257,8 +263,12 @@ class E4TTrainer:
         self._head_factors = None
         self._accum_pending = False          # a non-synchronising step has left gradients behind (graph replay and the factored update assume none)
         self._setup_overlap(named, n)
-        self.exp_avg = torch.zeros_like(self.flat.data)
-        self.exp_avg_sq = torch.zeros_like(self.flat.data)
+        if self.state_bits == 8:
+            self.exp_avg = self.exp_avg_sq = None
+            self.adam8 = Adam8State(self.flat.numel, self.flat.data.device)
+        else:
+            self.exp_avg = torch.zeros_like(self.flat.data)
+            self.exp_avg_sq = torch.zeros_like(self.flat.data)
         # replica consistency (the reference gets it from the DDP constructor, which broadcasts rank 0's parameters and buffers when
         # accelerate wraps the models, pretrain_e4t.py:410-412): every rank starts from rank 0's weights — trainable AND frozen —
         # whatever its own seed / checkpoint read produced, and a checksum of the trainable state is compared every
@@ -286,7 +296,8 @@ class E4TTrainer:
         bc = lambda t: torch.distributed.broadcast(t, src=torch.distributed.get_global_rank(self.pg, 0) if self.pg is not None else 0, group=self.pg)
         bc(self.flat.data)
         if include_moments:
-            bc(self.exp_avg); bc(self.exp_avg_sq)
+            for b in self._moment_buffers():
+                bc(b)
             if self.ema is not None:
                 bc(self.ema)
             cnt = torch.tensor([self.step_count], dtype=torch.int64, device=self.device)
@@ -307,18 +318,32 @@ class E4TTrainer:
                             bc(t)
         ops.bump_weights_epoch()
 
+    def _moment_buffers(self):
+        """the buffers that hold AdamW's moments: exp_avg and exp_avg_sq, or the 8-bit state's two code and two scale buffers"""
+        return (self.exp_avg, self.exp_avg_sq) if self.adam8 is None else self.adam8.buffers()
+
+    @staticmethod
+    def _byte_checksums(q, chunk=1 << 24):
+        """sum and sum of squares of a uint8 buffer as float64 scalars (exact: integer arithmetic, in chunks that keep the temporaries small)"""
+        s2 = torch.zeros((), dtype=torch.int64, device=q.device)
+        for o in range(0, q.numel(), chunk):
+            w = q[o:o + chunk].to(torch.int32)
+            s2 += (w * w).sum()
+        return q.sum(dtype=torch.int64).double(), s2.double()
+
     def check_replicas(self):
         """every rank must hold bit-identical trainable state (deterministic kernels + the same all-reduced gradient): compare a
         checksum vector — sum and sum of squares of the parameters, of exp_avg and of exp_avg_sq (and of the EMA, when on) — across ranks (MIN == MAX);
         raises on every rank when they differ.  A non-finite state is reported as such, not as divergence (NaN != NaN)."""
         if self.world <= 1:
             return True
-        bufs = (self.flat.data, self.exp_avg, self.exp_avg_sq) + ((self.ema,) if self.ema is not None else ())
+        bufs = (self.flat.data,) + self._moment_buffers() + ((self.ema,) if self.ema is not None else ())
         if self.flat.data.is_cuda:
             be = ops.backend()
-            c = torch.stack([x for b in bufs for x in (b.sum(dtype=torch.float64), be.sumsq(b).double())])
+            sums = lambda b: (b.sum(dtype=torch.float64), be.sumsq(b).double())
         else:
-            c = torch.stack([x for b in bufs for x in (b.double().sum(), b.double().pow(2).sum())])
+            sums = lambda b: (b.double().sum(), b.double().pow(2).sum())
+        c = torch.stack([x for b in bufs for x in (self._byte_checksums(b) if b.dtype == torch.uint8 else sums(b))])
         finite = torch.isfinite(c).all().to(torch.int32)
         torch.distributed.all_reduce(finite, op=torch.distributed.ReduceOp.MIN, group=self.pg)
         if not bool(finite):
@@ -629,6 +654,8 @@ class E4TTrainer:
         the stack: a synchronising step, no accumulated micro-batches, no gradient clip."""
         if not (self.factored_head_update and self._armed and not self._accum_pending and self.max_grad_norm is None and self._stack_shape):
             return False
+        if self.adam8 is not None:          # no 8-bit form of adamw_rank_kernel: the stack's gradient is materialised and goes through e4t_adamw8
+            return False
         if self.world > 1 and "W" not in self._done:          # local factors only: the stack has to ride the all-reduce
             return False
         self._head_factors = (gb, Z)
@@ -708,6 +735,8 @@ class E4TTrainer:
         if self._ema_swapped:
             raise RuntimeError("optimizer_step inside ema_weights(): the flat buffer holds the average, not the trained weights")
         ema = self.ema
+        if self.adam8 is not None:
+            return self._optimizer_step8(deferred)
         if self._hyper is not None:
             # step-graph mode: lr / bias corrections / gradient scale live in device memory (refreshed by the host before every step, eager
             # or replayed), so the captured launch is the same launch at every step
@@ -772,6 +801,45 @@ class E4TTrainer:
                 w.wait()
             self._mark("late_wait_end")
             adamw(lo, hi)
+        ops.bump_weights_epoch()
+
+    def _optimizer_step8(self, deferred):
+        """optimizer_step with 8-bit moments: every branch is e4t_adamw8 (device scalars or not, EMA or not).  A launch covers whole 256-element
+        blocks, so the split around a deferred region [lo, hi) is rounded outwards to block boundaries: [0, lo & ~255) and [ceil256(hi), n) run
+        under the all-reduce, the rest after the wait; every block is updated by exactly one launch and the split still changes no bit."""
+        st, ema, B, n = self.adam8, self.ema, ADAM8_BLOCK, self.flat.numel
+        if self._hyper is not None:
+            if not self._capturing:
+                self.step_count += 1
+                self._write_hyper()
+            scalars = dict(lr=0.0, step=0, hyper=self._hyper)
+        else:
+            self.step_count += 1
+            scalars = dict(lr=self.lr, step=self.step_count, grad_scale=1.0 / self.world,
+                           ema_w=ema_weight(self.ema_decay, self.step_count) if ema is not None else 0.0)
+        assert self._head_factors is None
+
+        def adamw(lo, hi):
+            assert lo % B == 0 and (hi % B == 0 or hi == n)
+            b0, b1 = lo // B, -(-hi // B)
+            ops.backend().adamw8(self.flat.data[lo:hi], self.flat.grad[lo:hi], st.qm[lo:hi], st.qv[lo:hi], st.absmax_m[b0:b1], st.absmax_v[b0:b1],
+                                 st.code_m, st.code_v, beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, wd=self.wd,
+                                 ema=None if ema is None else ema[lo:hi], **scalars)
+        if deferred is None:
+            adamw(0, n)
+        else:
+            (lo, hi), handles = deferred
+            lo, hi = lo // B * B, min(-(-hi // B) * B, n)
+            if lo > 0:
+                adamw(0, lo)
+            if hi < n:
+                adamw(hi, n)
+            self._mark("late_wait_begin")
+            for w in handles:
+                w.wait()
+            self._mark("late_wait_end")
+            if hi > lo:
+                adamw(lo, hi)
         ops.bump_weights_epoch()
 
     # ---- the whole step as ONE HIP graph ----------------------------------------------------------------------------------------
@@ -952,8 +1020,13 @@ class E4TTrainer:
     def state_dict(self):
         if self._ema_swapped:
             raise RuntimeError("state_dict inside ema_weights(): the flat buffer holds the average, not the trained weights")
-        sd = dict(params=self.flat.data.detach().cpu().clone(), exp_avg=self.exp_avg.cpu().clone(), exp_avg_sq=self.exp_avg_sq.cpu().clone(),
-                  step_count=self.step_count, lr=self.lr)
+        if self.adam8 is not None:
+            # 8-bit moments: the four buffers as they are, marked with the format (a 32-bit trainer dequantises them on load)
+            sd = dict(params=self.flat.data.detach().cpu().clone(), step_count=self.step_count, lr=self.lr, state_bits=8, block=self.adam8.block,
+                      **{k: b.cpu().clone() for k, b in zip(Adam8State.BUFFERS, self.adam8.buffers())})
+        else:
+            sd = dict(params=self.flat.data.detach().cpu().clone(), exp_avg=self.exp_avg.cpu().clone(), exp_avg_sq=self.exp_avg_sq.cpu().clone(),
+                      step_count=self.step_count, lr=self.lr)
         if self.ema is not None:
             sd.update(ema=self.ema.cpu().clone(), ema_decay=self.ema_decay)
         return sd
@@ -961,9 +1034,23 @@ class E4TTrainer:
     def load_state_dict(self, sd):
         if sd["params"].numel() != self.flat.data.numel():
             raise RuntimeError(f"training state holds {sd['params'].numel()} parameters, this trainer {self.flat.data.numel()}")
+        # either kind of moments into either trainer: fp32 moments are quantised (quantize_blockwise), 8-bit ones dequantised
+        if int(sd.get("state_bits", 32)) == 8:
+            if int(sd["block"]) != ADAM8_BLOCK:
+                raise RuntimeError(f"training state holds 8-bit moments in blocks of {sd['block']}, this build uses blocks of {ADAM8_BLOCK}")
+            if self.adam8 is not None:
+                for k, b in zip(Adam8State.BUFFERS, self.adam8.buffers()):
+                    b.copy_(sd[k])
+            else:
+                code_m, code_v = dynamic_codebook(True), dynamic_codebook(False)
+                self.exp_avg.copy_(dequantize_blockwise(sd["qm"], sd["absmax_m"], code_m))
+                self.exp_avg_sq.copy_(dequantize_blockwise(sd["qv"], sd["absmax_v"], code_v))
+        elif self.adam8 is not None:
+            self.adam8.quantize_from(sd["exp_avg"], sd["exp_avg_sq"])
+        else:
+            self.exp_avg.copy_(sd["exp_avg"])
+            self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.flat.data.copy_(sd["params"])
-        self.exp_avg.copy_(sd["exp_avg"])
-        self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         self.step_count = int(sd["step_count"])
         if self.ema is not None:
             if "ema" in sd:

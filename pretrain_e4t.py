@@ -89,7 +89,7 @@ def parse_args():
     if args.train_mask_dataset and (args.webdataset or args.iterable_dataset or args.synthetic_data):
         p.error("--train_mask_dataset needs image directories: it cannot be combined with --webdataset, --iterable_dataset or --synthetic_data")
     if args.use_8bit_adam:
-        p.error("--use_8bit_adam (bitsandbytes) is CUDA-only and not part of the MI355X path; the fused fp32 AdamW kernel is used")
+        p.error("--use_8bit_adam (bitsandbytes) is not part of the MI355X path; --optimizer_state_bits 8 selects the native block-wise 8-bit AdamW state")
     if args.mixed_precision == "fp16":
         p.error("the native kernels compute in bf16 with fp32 accumulation; use --mixed_precision bf16")
     if args.gradient_accumulation_steps < 1:

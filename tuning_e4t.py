@@ -67,7 +67,7 @@ def parse_args():
     if a.train_mask_path and not a.train_image_path:
         p.error("--train_mask_path needs --train_image_path")
     if a.use_8bit_adam:
-        p.error("--use_8bit_adam (bitsandbytes) is CUDA-only; the fused fp32 AdamW kernel is used")
+        p.error("--use_8bit_adam (bitsandbytes) is not part of the MI355X path; --optimizer_state_bits 8 selects the native block-wise 8-bit AdamW state")
     if a.gradient_accumulation_steps < 1:
         p.error("--gradient_accumulation_steps must be >= 1")
     return a
