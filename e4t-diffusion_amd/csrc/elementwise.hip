@@ -470,6 +470,83 @@ extern "C" int e4t_guided_step(const float* pred, const float* sample, const flo
   E4T_CHECK_LAUNCH("guided_step_kernel");
   return 0;
 }
+// Per-image statistics of the guided value for guidance rescale (e4t_guidance_stats in the header): one workgroup of 1024
+// threads per image, two passes over the image's N = C*HW values (means, then squared deviations from them; the second pass
+// reads what the first left in L2).  A one-pass sum / sum of squares loses the deviation of an image whose mean is large
+// against it.  An image's slab is the same N contiguous values in NCHW and NHWC, and a sum does not care which element is
+// which, so both layouts walk the slab in storage order.  Every thread adds its strided elements in index order and block_sum
+// combines in a fixed order: no atomics, the same bits on every call.  V = 4: 16-byte loads (N % 4 == 0, aligned pred).
+__device__ __forceinline__ float guide_e0(float u, float t, float c, float g, float g_id, int branches) {
+  if (branches == 3) return __fmaf_rn(g_id, c - t, __fmaf_rn(g, t - u, u));
+  return u + g * (t - u);                                  // branches == 2: t is c; sampler_step_kernel's expression
+}
+template <int V>
+__global__ __launch_bounds__(1024) void guidance_stats_kernel(const float* __restrict__ pred, const float* __restrict__ gp, float* __restrict__ gstat,
+                                                              long long n, int N, int branches) {
+  __shared__ float red[32];
+  const float g = gp[0], g_id = gp[1], phi = gp[2];
+  const float* u = pred + (long long)blockIdx.x * N;       // branch 0 of this image; branch r is at u + r*n
+  const float* c = u + (branches - 1) * n;
+  float vu[V], vt[V], vc[V];
+  float se = 0.f, sc = 0.f;
+  for (int i = threadIdx.x * V; i < N; i += 1024 * V) {
+    if constexpr (V == 4) {
+      *(float4*)vu = *(const float4*)(u + i);
+      *(float4*)vt = *(const float4*)(u + n + i);
+      *(float4*)vc = *(const float4*)(c + i);
+    } else {
+      vu[0] = u[i], vt[0] = u[n + i], vc[0] = c[i];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      se += guide_e0(vu[v], vt[v], vc[v], g, g_id, branches);
+      sc += vc[v];
+    }
+  }
+  const float me = block_sum(se, red) / (float)N, mc = block_sum(sc, red + 16) / (float)N;
+  float qe = 0.f, qc = 0.f;
+  for (int i = threadIdx.x * V; i < N; i += 1024 * V) {
+    if constexpr (V == 4) {
+      *(float4*)vu = *(const float4*)(u + i);
+      *(float4*)vt = *(const float4*)(u + n + i);
+      *(float4*)vc = *(const float4*)(c + i);
+    } else {
+      vu[0] = u[i], vt[0] = u[n + i], vc[0] = c[i];
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+      const float de = guide_e0(vu[v], vt[v], vc[v], g, g_id, branches) - me, dc = vc[v] - mc;
+      qe = __fmaf_rn(de, de, qe);
+      qc = __fmaf_rn(dc, dc, qc);
+    }
+  }
+  qe = block_sum(qe, red);
+  qc = block_sum(qc, red + 16);
+  if (threadIdx.x == 0) {
+    const float s_e = sqrtf(qe / (float)(N - 1)), s_c = sqrtf(qc / (float)(N - 1));
+    const float ratio = s_c / s_e;
+    const float f = (s_e == 0.f || !isfinite(ratio)) ? 1.f : (1.f - phi) + phi * ratio;
+    float* o = gstat + (long long)blockIdx.x * E4T_GUIDE_STATS;
+    o[0] = f, o[1] = s_c, o[2] = s_e, o[3] = me;
+  }
+}
+extern "C" int e4t_guidance_stats(const float* pred, const float* gp, float* gstat, int B, int C, int HW, int branches, int pred_nhwc, e4t_stream s) {
+  E4T_REQUIRE(pred, "guidance_stats: pred is null");
+  E4T_REQUIRE(gp, "guidance_stats: gp is null");
+  E4T_REQUIRE(gstat, "guidance_stats: gstat is null");
+  E4T_REQUIRE(branches == 2 || branches == 3, "guidance_stats: branches = %d (2: [u | c], 3: [u | k | c])", branches);
+  E4T_REQUIRE(B > 0 && C > 0 && HW > 0 && (long long)C * HW <= 0x7fffffffLL, "guidance_stats: B = %d, C = %d, HW = %d", B, C, HW);
+  E4T_REQUIRE((long long)C * HW >= 2, "guidance_stats: N = C*HW = %lld values per image (an unbiased deviation needs N >= 2)", (long long)C * HW);
+  (void)pred_nhwc;                                         // storage order: see the kernel
+  const int N = C * HW;
+  const long long n = (long long)B * N;
+  if (N % 4 == 0 && ((uintptr_t)pred & 15) == 0)
+    hipLaunchKernelGGL(guidance_stats_kernel<4>, dim3(B), dim3(1024), 0, (hipStream_t)s, pred, gp, gstat, n, N, branches);
+  else
+    hipLaunchKernelGGL(guidance_stats_kernel<1>, dim3(B), dim3(1024), 0, (hipStream_t)s, pred, gp, gstat, n, N, branches);
+  E4T_CHECK_LAUNCH("guidance_stats_kernel");
+  return 0;
+}
 // Guidance + one step of any linear sampler (DDIM, PLMS, LMS, Euler, Euler-ancestral, DPM-Solver++ 2M) in a single pass.
 // The row contract is the header's (e4t_sampler_step).  Every thread owns one element index across x, out, hist, saved
 // and x_in, so reading the old values before writing the new ones needs no synchronisation and x may alias out.
@@ -478,16 +555,20 @@ extern "C" int e4t_guided_step(const float* pred, const float* sample, const flo
 // BLEND (e4t_sampler_step_edit): the finished o is mixed with the original latent re-noised to the level of the row's output,
 // y = a_keep*x0 + s_keep*n0 with (a_keep, s_keep) = row[14], row[15], weighted by keep; both entry points are instances of
 // this one body, and everything up to the mix is the same code, so the plain entry point's arithmetic cannot drift.
-template <bool BLEND>
+// GUIDED (e4t_sampler_step_guided): g comes from gp instead of row[0], a third branch [u | k | c] adds the identity term
+// g_id*(c - k), and the guided value is scaled by the image's rescale factor gstat[b][0] (e4t_guidance_stats) when gstat is
+// given.  With branches == 2 and no gstat the guidance line is the one the plain entry points run, so the bits are theirs.
+template <bool BLEND, bool GUIDED>
 __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restrict__ pred, const float* x, float* out, float* hist, float* saved,
                                                            const float* __restrict__ noise, float* x_in, const float* __restrict__ row,
                                                            const float* __restrict__ keep, const float* __restrict__ x0, const float* __restrict__ n0,
+                                                           const float* __restrict__ gp, const float* __restrict__ gstat,
                                                            int B, int C, int HW, int K, int cfg, int nhwc, int x_in_copies,
-                                                           int keep_per_image, int x0_per_image) {
+                                                           int keep_per_image, int x0_per_image, int branches) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long n = (long long)B * C * HW;
   if (i >= n) return;
-  const float g = row[0], a_e = row[1], a_x = row[2], c_x = row[3], c_s = row[4], c_m = row[5], c_n = row[6], k_in = row[7];
+  const float g = GUIDED ? gp[0] : row[0], a_e = row[1], a_x = row[2], c_x = row[3], c_s = row[4], c_m = row[5], c_n = row[6], k_in = row[7];
   const int w = (int)row[8], save_x = row[9] != 0.f;
   long long j = i;
   if (nhwc) {
@@ -497,7 +578,11 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
   float e = pred[j];
   if (cfg) {
     const float t = pred[j + n];
-    e = e + g * (t - e);
+    if (GUIDED && branches == 3) e = __fmaf_rn(gp[1], pred[j + 2 * n] - t, __fmaf_rn(g, t - e, e));
+    else e = e + g * (t - e);
+  }
+  if constexpr (GUIDED) {
+    if (gstat) e *= gstat[(i / ((long long)C * HW)) * E4T_GUIDE_STATS];
   }
   const float xv = x[i];
   float m = a_e * e;
@@ -522,6 +607,7 @@ __global__ __launch_bounds__(256) void sampler_step_kernel(const float* __restri
     const float v = k_in * o;
     x_in[i] = v;
     if (x_in_copies > 1) x_in[n + i] = v;
+    if (x_in_copies > 2) x_in[2 * n + i] = v;
   }
 }
 extern "C" int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
@@ -530,8 +616,8 @@ extern "C" int e4t_sampler_step(const float* pred, const float* x, float* out, f
   E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
   E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 2 && (x_in_copies == 0 || x_in), "sampler_step: x_in_copies = %d (0..2, x_in required when > 0)", x_in_copies);
   const long long n = (long long)B * C * HW;
-  hipLaunchKernelGGL(sampler_step_kernel<false>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
-                     nullptr, nullptr, nullptr, B, C, HW, K, cfg, pred_nhwc, x_in_copies, 0, 0);
+  hipLaunchKernelGGL((sampler_step_kernel<false, false>), dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
+                     nullptr, nullptr, nullptr, nullptr, nullptr, B, C, HW, K, cfg, pred_nhwc, x_in_copies, 0, 0, 2);
   E4T_CHECK_LAUNCH("sampler_step_kernel");
   return 0;
 }
@@ -545,9 +631,31 @@ extern "C" int e4t_sampler_step_edit(const float* pred, const float* x, float* o
   E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step_edit: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
   E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 2 && (x_in_copies == 0 || x_in), "sampler_step_edit: x_in_copies = %d (0..2, x_in required when > 0)", x_in_copies);
   const long long n = (long long)B * C * HW;
-  hipLaunchKernelGGL(sampler_step_kernel<true>, dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
-                     keep, x0, n0, B, C, HW, K, cfg, pred_nhwc, x_in_copies, keep_per_image, x0_per_image);
+  hipLaunchKernelGGL((sampler_step_kernel<true, false>), dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in, row,
+                     keep, x0, n0, nullptr, nullptr, B, C, HW, K, cfg, pred_nhwc, x_in_copies, keep_per_image, x0_per_image, 2);
   E4T_CHECK_LAUNCH("sampler_step_edit_kernel");
+  return 0;
+}
+extern "C" int e4t_sampler_step_guided(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
+                                       const float* row, const float* gp, const float* gstat, const float* keep, const float* x0, const float* n0,
+                                       int B, int C, int HW, int K, int branches, int pred_nhwc, int x_in_copies, int keep_per_image,
+                                       int x0_per_image, e4t_stream s) {
+  E4T_REQUIRE(pred && x && out && row && gp && B > 0 && C > 0 && HW > 0, "sampler_step_guided: bad arguments");
+  E4T_REQUIRE(branches == 2 || branches == 3, "sampler_step_guided: branches = %d (2: [u | c], 3: [u | k | c])", branches);
+  const bool blend = keep && x0 && n0;
+  E4T_REQUIRE(blend || (!keep && !x0 && !n0), "sampler_step_guided: keep, x0 and n0 are given together or not at all");
+  E4T_REQUIRE((keep_per_image == 0 || keep_per_image == 1) && (x0_per_image == 0 || x0_per_image == 1),
+              "sampler_step_guided: keep_per_image = %d, x0_per_image = %d (0 or 1)", keep_per_image, x0_per_image);
+  E4T_REQUIRE(K >= 0 && K <= E4T_SAMPLER_MAX_HIST && (K == 0 || hist), "sampler_step_guided: K = %d history slots (0..%d, hist required when K > 0)", K, E4T_SAMPLER_MAX_HIST);
+  E4T_REQUIRE(x_in_copies >= 0 && x_in_copies <= 3 && (x_in_copies == 0 || x_in), "sampler_step_guided: x_in_copies = %d (0..3, x_in required when > 0)", x_in_copies);
+  const long long n = (long long)B * C * HW;
+  if (blend)
+    hipLaunchKernelGGL((sampler_step_kernel<true, true>), dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in,
+                       row, keep, x0, n0, gp, gstat, B, C, HW, K, 1, pred_nhwc, x_in_copies, keep_per_image, x0_per_image, branches);
+  else
+    hipLaunchKernelGGL((sampler_step_kernel<false, true>), dim3((unsigned)cdivl(n, 256)), dim3(256), 0, (hipStream_t)s, pred, x, out, hist, saved, noise, x_in,
+                       row, nullptr, nullptr, nullptr, gp, gstat, B, C, HW, K, 1, pred_nhwc, x_in_copies, 0, 0, branches);
+  E4T_CHECK_LAUNCH("sampler_step_guided_kernel");
   return 0;
 }
 extern "C" int e4t_transpose(const void* in, void* out, int batch, int R, int C, int ldi, int ldo, long long bsi, long long bso, e4t_stream s) {

@@ -114,6 +114,8 @@ SIGNATURES = {
     "e4t_guided_step": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, vp]),
     "e4t_sampler_step": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp]),
     "e4t_sampler_step_edit": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
+    "e4t_guidance_stats": (i32, [vp, vp, vp, i32, i32, i32, i32, i32, vp]),
+    "e4t_sampler_step_guided": (i32, [vp] * 13 + [i32] * 9 + [vp]),
     "e4t_image_prep": (i32, [vp, vp, vp, i32, i32, vp]),
     "e4t_mask_prep": (i32, [vp, vp, vp, vp, i32, i32, vp]),
     "e4t_masked_mse_fwd": (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
@@ -155,6 +157,7 @@ STORE_NAMES = ("bf16-staged", "f32-direct", "scalar", "splitk-partial")      # E
 CONV_S1, CONV_S2, CONV_UP2, CONV_S2T, CONV_S2A = 1, 2, 3, 4, 5
 WO_STORE_F32, WO_OFFSETS_ONLY = 1, 2
 SAMPLER_MAX_HIST, SAMPLER_ROW = 4, 16
+GUIDE_PARAMS, GUIDE_STATS = 4, 4       # gp = {g, g_id, phi, 0}; gstat[b] = {f, s_c, s_e, mean_e}
 MASKED_MSE_STATS = 2050
 LOSS_HUBER, LOSS_SMOOTH_L1 = 1, 2      # e4t_robust_loss_fwd's kind
 COMM_F32, COMM_BF16 = 0, 1

@@ -597,14 +597,14 @@ class HipBackend:
                  "e4t_guided_step")
         return out
 
-    def sampler_step(self, pred, x, row, hist=None, saved=None, noise=None, x_in=None, cfg=True, pred_nhwc=False, out=None, edit=None):
-        """guidance + one linear sampler update (the row contract of e4t_sampler_step in include/e4t_hip.h); row = device fp32
-        [16]; hist = [K, *x.shape] (K <= 4); x_in = [x.shape[0] or 2*x.shape[0], ...] receives k_in*out once or twice.
-        Returns out (x may be passed as out: in place).  edit = (keep, x0, n0): sampler_step_edit's operands."""
+    @staticmethod
+    def _sampler_operands(pred, x, row, branches, hist, saved, noise, x_in, out, edit):
+        """the shape and dtype checks the sampler-step entry points share -> (B, C, HW, K, copies, out, keep, x0, n0, keep_per_image,
+        x0_per_image); pred holds `branches` batches of x's shape"""
         B, Cn = x.shape[0], x.shape[1]
         HW = x.numel() // (B * Cn)
         assert pred.dtype == f32 and x.dtype == f32 and row.dtype == f32 and row.numel() == _C.SAMPLER_ROW and row.is_contiguous()
-        assert pred.is_contiguous() and x.is_contiguous() and pred.numel() == x.numel() * (2 if cfg else 1)
+        assert pred.is_contiguous() and x.is_contiguous() and pred.numel() == x.numel() * branches
         for t in (saved, noise):
             assert t is None or (t.dtype == f32 and t.is_contiguous() and t.shape == x.shape)
         K = 0
@@ -618,14 +618,22 @@ class HipBackend:
         if out is None:
             out = torch.empty_like(x)
         assert out.dtype == f32 and out.is_contiguous() and out.shape == x.shape
+        if edit is None:
+            return B, Cn, HW, K, copies, out, None, None, None, 0, 0
+        keep, x0, n0 = edit
+        for t in edit:
+            assert t.dtype == f32 and t.is_contiguous() and t.device == x.device
+        assert keep.numel() in (HW, B * HW) and x0.numel() in (Cn * HW, B * Cn * HW) and n0.shape == x.shape
+        return B, Cn, HW, K, copies, out, keep, x0, n0, int(B > 1 and keep.numel() == B * HW), int(B > 1 and x0.numel() == B * Cn * HW)
+
+    def sampler_step(self, pred, x, row, hist=None, saved=None, noise=None, x_in=None, cfg=True, pred_nhwc=False, out=None, edit=None):
+        """guidance + one linear sampler update (the row contract of e4t_sampler_step in include/e4t_hip.h); row = device fp32
+        [16]; hist = [K, *x.shape] (K <= 4); x_in = [x.shape[0] or 2*x.shape[0], ...] receives k_in*out once or twice.
+        Returns out (x may be passed as out: in place).  edit = (keep, x0, n0): sampler_step_edit's operands."""
+        B, Cn, HW, K, copies, out, keep, x0, n0, kpi, xpi = self._sampler_operands(pred, x, row, 2 if cfg else 1, hist, saved, noise, x_in, out, edit)
         if edit is not None:
-            keep, x0, n0 = edit
-            for t in edit:
-                assert t.dtype == f32 and t.is_contiguous() and t.device == x.device
-            assert keep.numel() in (HW, B * HW) and x0.numel() in (Cn * HW, B * Cn * HW) and n0.shape == x.shape
             _C.check(self.lib.e4t_sampler_step_edit(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
-                                                    _ptr(keep), _ptr(x0), _ptr(n0), B, Cn, HW, K, int(cfg), int(pred_nhwc), copies,
-                                                    int(B > 1 and keep.numel() == B * HW), int(B > 1 and x0.numel() == B * Cn * HW), _stream()),
+                                                    _ptr(keep), _ptr(x0), _ptr(n0), B, Cn, HW, K, int(cfg), int(pred_nhwc), copies, kpi, xpi, _stream()),
                      "e4t_sampler_step_edit")
             return out
         _C.check(self.lib.e4t_sampler_step(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
@@ -637,6 +645,37 @@ class HipBackend:
         (1 - keep)*out with (a_keep, s_keep) = row[14:16]; keep = fp32 [HW] (shared) or [B, HW], x0 = fp32 [C, HW] (shared) or
         [B, C, HW], n0 = fp32 of x's shape; trailing dimensions may be split as (H, W)."""
         return self.sampler_step(pred, x, row, edit=(keep, x0, n0), **kw)
+
+    def guidance_stats(self, pred, gp, branches, pred_nhwc, out=None):
+        """per-image statistics of the guided value for guidance rescale (e4t_guidance_stats in include/e4t_hip.h): pred = fp32
+        [branches*B, C, H, W] ([.., H, W, C] when pred_nhwc), gp = device fp32 [g, g_id, phi, 0] -> out = fp32 [B, 4] =
+        {f, s_c, s_e, mean_e} per image"""
+        assert branches in (2, 3) and pred.dim() == 4 and pred.shape[0] % branches == 0
+        B = pred.shape[0] // branches
+        Cn = pred.shape[3] if pred_nhwc else pred.shape[1]
+        HW = pred.numel() // (pred.shape[0] * Cn)
+        assert pred.dtype == f32 and pred.is_contiguous()
+        assert gp.dtype == f32 and gp.is_contiguous() and gp.numel() == _C.GUIDE_PARAMS and gp.device == pred.device and gp.data_ptr() % 16 == 0
+        if out is None:
+            out = torch.empty((B, _C.GUIDE_STATS), dtype=f32, device=pred.device)
+        assert out.dtype == f32 and out.is_contiguous() and tuple(out.shape) == (B, _C.GUIDE_STATS) and out.device == pred.device
+        _C.check(self.lib.e4t_guidance_stats(_ptr(pred), _ptr(gp), _ptr(out), B, Cn, HW, branches, int(pred_nhwc), _stream()), "e4t_guidance_stats")
+        return out
+
+    def sampler_step_guided(self, pred, x, row, gp, gstat=None, branches=2, hist=None, saved=None, noise=None, x_in=None, pred_nhwc=False,
+                            out=None, edit=None):
+        """sampler_step with the guidance of e4t_sampler_step_guided (include/e4t_hip.h): pred = [u | c] or [u | k | c] (branches),
+        gp = device fp32 [g, g_id, phi, 0] (row[0] is ignored), gstat = guidance_stats' [B, 4] or None (no rescale); x_in receives
+        k_in*out up to three times; edit = (keep, x0, n0) or None.  Returns out (x may be passed as out: in place)."""
+        assert branches in (2, 3)
+        B, Cn, HW, K, copies, out, keep, x0, n0, kpi, xpi = self._sampler_operands(pred, x, row, branches, hist, saved, noise, x_in, out, edit)
+        assert gp.dtype == f32 and gp.is_contiguous() and gp.numel() == _C.GUIDE_PARAMS and gp.device == x.device and gp.data_ptr() % 16 == 0
+        assert gstat is None or (gstat.dtype == f32 and gstat.is_contiguous() and tuple(gstat.shape) == (B, _C.GUIDE_STATS) and gstat.device == x.device)
+        _C.check(self.lib.e4t_sampler_step_guided(_ptr(pred), _ptr(x), _ptr(out), _ptr(hist), _ptr(saved), _ptr(noise), _ptr(x_in), _ptr(row),
+                                                  _ptr(gp), _ptr(gstat), _ptr(keep), _ptr(x0), _ptr(n0), B, Cn, HW, K, branches, int(pred_nhwc), copies,
+                                                  kpi, xpi, _stream()),
+                 "e4t_sampler_step_guided")
+        return out
 
     def image_prep(self, pool, table, B, S, out=None):
         """raw uint8 RGB images packed in `pool` + int64 [B,8] plan `table` (both on the device) -> fp32 [B,3,S,S]"""

@@ -28,6 +28,12 @@ every step.  The definition is the generic loop (``step`` + the torch blend belo
 step kernel (``e4t_sampler_step_edit``, rows of ``fused_plan(blend=True)``), so an edited step is still one UNet pass + one
 update launch inside the replayed graph.  The CPU op emulation takes the generic loop.
 
+Guidance rescale and identity guidance (not in the reference): ``guidance_rescale=`` scales every image's guided
+output towards the conditional branch's standard deviation, ``identity_guidance_scale=`` adds a third UNet branch, the prompt
+with the plain class word, and weighs subject against prompt.  The definition is ``schedulers.combine_guidance`` in the generic
+loop; on the fused path the step is ``e4t_sampler_step_guided`` (the same kernel body), preceded by one ``e4t_guidance_stats``
+launch when rescaling, both inside the replayed graph.  A call with neither option runs the launches it ran before.
+
 The tokenizer is whatever object the caller passes (``transformers.CLIPTokenizer`` in inference.py): it needs
 ``__call__(text, padding=, truncation=, max_length=, return_tensors="pt", add_special_tokens=)``, ``add_tokens``,
 ``convert_tokens_to_ids``, ``model_max_length`` and ``__len__``.  The safety checker is not built (the reference runs the
@@ -43,7 +49,7 @@ import torch
 
 from . import ops
 from . import tome
-from .schedulers import DDIMScheduler
+from .schedulers import DDIMScheduler, combine_guidance
 
 
 @dataclass
@@ -191,7 +197,8 @@ class StableDiffusionE4TPipeline:
 
     # ---- one denoising step -----------------------------------------------------------------------------------------
     def _model_step(self, latents, t, s, x_in=None):
-        """eps (or v) prediction for guidance: returns the UNet output tensor of the [uncond | cond] (or cond-only) batch.
+        """eps (or v) prediction for guidance: returns the UNet output tensor of the [uncond | cond] (or cond-only) batch,
+        [uncond | class word | cond] with s["ctx_k"] (identity guidance).
         x_in: the scaled UNet input when the caller already has it, as the [x_in | x_in] batch under guidance (the fused
         loop: e4t_sampler_step writes it); None -> scheduler.scale_model_input(latents, t)."""
         bsz = latents.shape[0]
@@ -210,10 +217,20 @@ class StableDiffusionE4TPipeline:
         emb = s["inputs_embeds"].expand(bsz, -1, -1).clone()
         emb[:, s["idx"], :] = domain.to(emb.dtype)                                                       # :195-196
         ctx = self.text_encoder(inputs_embeds=emb)[0].to(ctx_e.dtype)                                    # :198
+        if s.get("ctx_k") is not None:                   # identity guidance: [uncond | class word | cond]
+            x_cat = torch.cat([x_in] * 3) if x_cat is None else x_cat
+            return self.unet(x_cat, t, torch.cat([ctx_e, s["ctx_k"].expand(bsz, -1, -1).to(ctx_e.dtype), ctx])).sample
         if s["cfg"]:
             x_cat = torch.cat([x_in] * 2) if x_cat is None else x_cat
             return self.unet(x_cat, t, torch.cat([ctx_e, ctx])).sample                                     # :199-206
         return self.unet(x_in, t, ctx).sample
+
+    def class_word_context(self, e4t):
+        """the context of the prompt with the plain class word at the placeholder (what the conditional branch is at
+        domain_embed_scale = 0): the middle branch of identity guidance, constant over the steps and the images"""
+        emb = e4t["inputs_embeds"].clone()
+        emb[:, e4t["placeholder_token_id_idx"], :] = self.class_embed.to(emb.dtype)
+        return self.text_encoder(inputs_embeds=emb)[0].to(e4t["encoder_hidden_states_for_e4t"].dtype)
 
     def _fused_update(self, pred, latents, coef, cfg):
         """guidance + linear scheduler update in one kernel, in place on `latents`"""
@@ -230,10 +247,17 @@ class StableDiffusionE4TPipeline:
         kw = dict(hist=bufs["hist"], saved=bufs["saved"], noise=bufs["noise"], x_in=bufs["x_in"], cfg=cfg, out=latents)
         if bufs.get("edit") is not None:                 # masked editing: the blend with the re-noised original, in the same kernel
             kw["edit"] = bufs["edit"]
-        if nhwc.is_contiguous():                         # the native UNet hands out an NCHW view of NHWC storage
-            ops.backend().sampler_step(nhwc, latents, row, pred_nhwc=True, **kw)
-        else:
-            ops.backend().sampler_step(pred.contiguous(), latents, row, pred_nhwc=False, **kw)
+        is_nhwc = nhwc.is_contiguous()                   # the native UNet hands out an NCHW view of NHWC storage
+        p = nhwc if is_nhwc else pred.contiguous()
+        if bufs.get("gp") is None:
+            ops.backend().sampler_step(p, latents, row, pred_nhwc=is_nhwc, **kw)
+            return
+        # guidance rescale / identity guidance: the per-image statistics only when rescaling, then the guided step
+        del kw["cfg"]
+        branches = p.shape[0] // latents.shape[0]
+        if bufs["gstat"] is not None:
+            ops.backend().guidance_stats(p, bufs["gp"], branches, is_nhwc, out=bufs["gstat"])
+        ops.backend().sampler_step_guided(p, latents, row, bufs["gp"], gstat=bufs["gstat"], branches=branches, pred_nhwc=is_nhwc, **kw)
 
     # ---- the call -------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -242,9 +266,22 @@ class StableDiffusionE4TPipeline:
                  eta: float = 0.0, generator=None, latents: Optional[torch.Tensor] = None, prompt_embeds=None, negative_prompt_embeds=None,
                  output_type: Optional[str] = "pil", return_dict: bool = True, callback: Optional[Callable] = None, callback_steps: int = 1,
                  cross_attention_kwargs=None, image=None, domain_embed_scale: Optional[float] = None, use_graph: Optional[bool] = None,
-                 init_image=None, strength: float = 0.8, mask_image=None):
+                 init_image=None, strength: float = 0.8, mask_image=None, guidance_rescale: float = 0.0,
+                 identity_guidance_scale: Optional[float] = None):
         """image: the conditioning image (the subject).  init_image: the photograph to edit (img2img: re-noised to `strength` of
-        the schedule and denoised from there); mask_image: white = repaint, everything else is held to init_image at every step."""
+        the schedule and denoised from there); mask_image: white = repaint, everything else is held to init_image at every step.
+        guidance_rescale: phi in [0, 1], the guided output of every image is pulled to the conditional branch's standard deviation
+        (v-prediction models over-expose without it).  identity_guidance_scale: g_id of the three-branch guidance
+        u + g*(k - u) + g_id*(c - k) with k the prompt with the plain class word; above guidance_scale it favours the subject,
+        below it the prompt.  Both: DESIGN §2.5b, ``schedulers.combine_guidance`` is the definition."""
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"`guidance_rescale` has to lie in [0, 1] but is {guidance_rescale}")
+        if identity_guidance_scale is not None and identity_guidance_scale < 0.0:
+            raise ValueError(f"`identity_guidance_scale` must not be negative but is {identity_guidance_scale}")
+        guided = guidance_rescale > 0.0 or identity_guidance_scale is not None
+        if guided and guidance_scale <= 1.0:
+            raise ValueError("`guidance_rescale` and `identity_guidance_scale` need `guidance_scale` > 1: there is no unconditional "
+                             f"branch at guidance_scale = {guidance_scale}")
         scale = self.domain_embed_scale if domain_embed_scale is None else domain_embed_scale
         height = height or self.unet.config.sample_size * self.vae_scale_factor
         width = width or self.unet.config.sample_size * self.vae_scale_factor
@@ -286,6 +323,9 @@ class StableDiffusionE4TPipeline:
             vision = (cls.expand(bsz, -1), tokens.expand(bsz, -1, -1))
         s = dict(ctx_e=e4t["encoder_hidden_states_for_e4t"], inputs_embeds=e4t["inputs_embeds"], idx=e4t["placeholder_token_id_idx"],
                  pixels=pixels.expand(bsz, -1, -1, -1), vision=vision, scale=scale, cfg=cfg)
+        branches = 2
+        if identity_guidance_scale is not None:          # the class-word branch: one text-encoder pass per call
+            s["ctx_k"], branches = self.class_word_context(e4t), 3
 
         sch = self.scheduler
         native = device.type == "cuda" and hasattr(ops.backend(), "sampler_step")
@@ -294,6 +334,8 @@ class StableDiffusionE4TPipeline:
             plan = sch.fused_plan(guidance_scale, eta, blend=True) if keep is not None else sch.fused_plan(guidance_scale, eta)
         if plan is not None and not native and (edit or not (isinstance(sch, DDIMScheduler) and eta == 0.0)):
             plan = None                  # without e4t_sampler_step only plain DDIM with eta == 0 is fused (through e4t_guided_step)
+        if plan is not None and guided and not (native and hasattr(ops.backend(), "sampler_step_guided")):
+            plan = None                  # e4t_guided_step knows u + g*(c - u) only: the generic loop, also for DDIM with eta == 0
         if use_graph is None:       # measured (SD-1.4, 512 px, 50 steps, DDIM): 13.6 -> 11.8 ms/step at 1 image, no gain from 4 images up
             use_graph = plan is not None and device.type == "cuda" and bsz <= 2
         if use_graph and plan is None:
@@ -309,11 +351,15 @@ class StableDiffusionE4TPipeline:
                 bufs = dict(hist=torch.zeros((plan.K,) + tuple(latents.shape), dtype=torch.float32, device=device) if plan.K else None,
                             saved=torch.zeros_like(latents) if plan.saves_x else None,
                             noise=torch.zeros_like(latents) if any(plan.noisy) else None,
-                            x_in=torch.empty(((2 if cfg else 1) * bsz,) + tuple(latents.shape[1:]), dtype=torch.float32, device=device))
+                            x_in=torch.empty(((branches if cfg else 1) * bsz,) + tuple(latents.shape[1:]), dtype=torch.float32, device=device))
+                if guided:               # e4t_sampler_step_guided's scalars and the statistics' output: allocated before capture
+                    g_id = guidance_scale if identity_guidance_scale is None else identity_guidance_scale
+                    bufs["gp"] = torch.tensor([guidance_scale, g_id, guidance_rescale, 0.0], dtype=torch.float32, device=device)
+                    bufs["gstat"] = torch.empty((bsz, 4), dtype=torch.float32, device=device) if guidance_rescale > 0.0 else None
                 x_in = bufs["x_in"]
                 torch.mul(latents, plan.k_in, out=x_in[:bsz])
-                if cfg:
-                    x_in[bsz:].copy_(x_in[:bsz])
+                for r in range(1, branches if cfg else 1):
+                    x_in[r * bsz:(r + 1) * bsz].copy_(x_in[:bsz])
                 state = [latents] + [bufs[k] for k in ("hist", "saved", "x_in") if bufs[k] is not None]
                 if keep is not None:     # fixed, read-only operands of e4t_sampler_step_edit: outside the captured state
                     bufs["edit"] = (keep, x0, n0)
@@ -355,9 +401,8 @@ class StableDiffusionE4TPipeline:
             for i, t in enumerate(timesteps):
                 tome.new_step(self.unet)
                 pred = self._model_step(latents, t, s)
-                if cfg:
-                    u, c = pred.chunk(2)
-                    pred = u + guidance_scale * (c - u)                              # :209-211
+                if cfg:                                                             # :209-211, and DESIGN §2.5b
+                    pred = combine_guidance(pred.chunk(branches), guidance_scale, identity_guidance_scale, guidance_rescale)
                 latents = sch.step(pred.float(), t, latents, **extra).prev_sample    # :214
                 if keep is not None:     # the definition of masked editing: hold the kept region at the next timestep's noise level
                     a, sg = sch.noise_level(timesteps[i + 1]) if i + 1 < len(timesteps) else (1.0, 0.0)

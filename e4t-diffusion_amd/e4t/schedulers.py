@@ -106,6 +106,27 @@ def _blend(sch, plan, blend):
     return plan
 
 
+def combine_guidance(branches, g, g_id=None, rescale=0.0):
+    """The guided model output from its branches: the definition, in the dtype of ``branches``.
+    branches = (u, c): e0 = u + g*(c - u).  branches = (u, k, c) (k: the prompt with the plain class word):
+    e0 = u + g*(k - u) + g_id*(c - k), g_id = g when None; g_id = g is plain guidance on c.
+    rescale = phi > 0 (Lin et al. 2023 §3.4): every image's e0 is scaled by f = (1 - phi) + phi * std(c) / std(e0), the unbiased
+    standard deviations over that image's values; f = 1 where std(e0) is 0 or the ratio is not finite."""
+    if len(branches) == 2:
+        u, c = branches
+        e0 = u + g * (c - u)
+    else:
+        u, k, c = branches
+        e0 = u + g * (k - u) + (g if g_id is None else g_id) * (c - k)
+    if rescale == 0.0:
+        return e0
+    dims = tuple(range(1, e0.dim()))
+    s_e, s_c = e0.std(dim=dims, keepdim=True), c.std(dim=dims, keepdim=True)
+    ratio = s_c / s_e
+    f = torch.where((s_e == 0) | ~torch.isfinite(ratio), torch.ones_like(ratio), (1.0 - rescale) + rescale * ratio)
+    return f * e0
+
+
 @dataclass
 class DDIMSchedulerOutput:
     prev_sample: torch.Tensor

@@ -350,6 +350,34 @@ int e4t_sampler_step(const float* pred, const float* x, float* out, float* hist,
 int e4t_sampler_step_edit(const float* pred, const float* x, float* out, float* hist, float* saved, const float* noise, float* x_in,
                           const float* row, const float* keep, const float* x0, const float* n0, int B, int C, int HW, int K, int cfg,
                           int pred_nhwc, int x_in_copies, int keep_per_image, int x0_per_image, e4t_stream stream);
+/* Guidance beyond e = u + g*(c - u) (not in the reference): a separate identity scale over three branches and
+ * guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", §3.4).  Both entry points
+ * read pred = [u | c] (branches = 2) or [u | k | c] (branches = 3: u the empty prompt, k the prompt with the class word, c the
+ * prompt with the predicted embedding), each branch [B][C][HW], or [B][HW][C] when pred_nhwc, and the scalars from
+ * gp: DEVICE float[4], 16-byte aligned = {g, g_id, phi, 0} (so a captured graph replays with new values).  With n = B*C*HW,
+ * per element in fp32:
+ *   branches = 2: e0 = u + g*(c - u)                         e4t_sampler_step's expression, so its bits
+ *   branches = 3: e0 = fma(g_id, c - k, fma(g, k - u, u))    g_id = g is plain guidance on c
+ * e4t_guidance_stats, per image b over its N = C*HW >= 2 values: mean_e and s_e are the mean and the unbiased (N - 1) standard
+ * deviation of e0[b], s_c the unbiased standard deviation of c[b], and f = (1 - phi) + phi*(s_c/s_e), or 1 when s_e == 0 or
+ * the ratio is not finite.  It writes gstat[b] = {f, s_c, s_e, mean_e} and nothing else.  The deviations are taken from the
+ * mean in a second pass (a sum of squares would cancel), in a fixed order without atomics: the same bits on every call.
+ * Errors (-22, e4t_last_error names the argument): branches not 2 or 3, N < 2, a NULL pred / gp / gstat. */
+#define E4T_GUIDE_PARAMS 4   /* gp: DEVICE float[4], 16-byte aligned = {g, g_id, phi, 0} */
+#define E4T_GUIDE_STATS  4   /* gstat: DEVICE float[B][4] = {f, s_c, s_e, mean_e} */
+int e4t_guidance_stats(const float* pred, const float* gp, float* gstat,
+                       int B, int C, int HW, int branches, int pred_nhwc, e4t_stream stream);
+/* e4t_sampler_step with that guidance: e = gstat ? gstat[b][0]*e0 : e0 (gstat may be NULL: no rescale), then everything from
+ * m on is e4t_sampler_step's: same row contract (row[0] is ignored, g is gp[0]), same element ownership, out may alias x.
+ * keep, x0 and n0 all NULL: no blend; all three given: e4t_sampler_step_edit's blend with row[14..15]; anything else is an
+ * error.  x_in receives k_in*out x_in_copies (0..3) times back to back ([x_in | x_in | x_in] = the three-branch UNet batch).
+ * With branches = 2, gstat NULL and gp[0] == row[0] the results are e4t_sampler_step's (cfg = 1), or with the blend
+ * e4t_sampler_step_edit's, bit for bit: all three are instances of one kernel body. */
+int e4t_sampler_step_guided(const float* pred, const float* x, float* out, float* hist, float* saved,
+                            const float* noise, float* x_in, const float* row, const float* gp,
+                            const float* gstat, const float* keep, const float* x0, const float* n0,
+                            int B, int C, int HW, int K, int branches, int pred_nhwc, int x_in_copies,
+                            int keep_per_image, int x0_per_image, e4t_stream stream);
 /* Data path (pretrain_e4t.py:137-144 make_transforms = SmallestMaxSize(interpolation=3: cv2.INTER_AREA) -> RandomCrop ->
  * HorizontalFlip, and :174-177 image/127.5-1, HWC->CHW): a batch of raw decoded uint8 RGB images in one device pool ->
  * out fp32 [B][3][S][S].  table: int64 [B][8] (device) = {byte offset of the image in pool, H, W, newH, newW (the

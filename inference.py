@@ -13,6 +13,10 @@ All six samplers of the reference are available, each with the fused, graph-repl
 
 places the subject into an existing photograph: img2img from the re-noised photograph, and with a mask (white = repaint)
 everything outside it is held to the photograph at every denoising step.
+
+    python inference.py ... --guidance_scale 7.5 --guidance_rescale 0.7 [--identity_guidance_scale 10]
+
+rescales the guided output against over-exposure and weighs the subject against the prompt.
 """
 import argparse
 import json
@@ -57,12 +61,24 @@ def parse_args(argv=None):
                    help="share of the schedule an --init_image is re-noised by, in (0, 1]: 1 keeps little of it, small values stay close to it")
     p.add_argument("--mask_image", type=str, default=None,
                    help="inpainting mask for --init_image: white is repainted, black is held to the photograph at every step (soft values blend)")
+    p.add_argument("--guidance_rescale", type=float, default=0.0,
+                   help="in [0, 1]: pull every image's guided output to the conditional branch's standard deviation (v-prediction models "
+                        "over-expose at usual guidance scales; 0.7 is the paper's value); needs --guidance_scale > 1")
+    p.add_argument("--identity_guidance_scale", type=float, default=None,
+                   help="guidance scale of the subject against the prompt with the plain class word (a third UNet branch): above "
+                        "--guidance_scale it favours the subject, below it the prompt; needs --guidance_scale > 1")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
     cc.add_ema_args(p, training=False)
     args = p.parse_args(argv)
     cc.check_tome_args(p, args)
     cc.check_ema_args(p, args)
+    if not 0.0 <= args.guidance_rescale <= 1.0:
+        p.error("--guidance_rescale must lie in [0, 1]")
+    if args.identity_guidance_scale is not None and args.identity_guidance_scale < 0.0:
+        p.error("--identity_guidance_scale must not be negative")
+    if (args.guidance_rescale > 0.0 or args.identity_guidance_scale is not None) and args.guidance_scale <= 1.0:
+        p.error("--guidance_rescale and --identity_guidance_scale need --guidance_scale > 1")
     if not 0.0 < args.strength <= 1.0:
         p.error("--strength must lie in (0, 1]")
     if args.mask_image is not None and args.init_image is None:
@@ -172,7 +188,8 @@ def main():
     all_images = []
     for prompt in prompts:
         all_images.extend(pipe(prompt, num_inference_steps=args.num_inference_steps, guidance_scale=args.guidance_scale, generator=generator,
-                               image=image, num_images_per_prompt=args.num_images_per_prompt, height=args.height, width=args.width, **edit_kw).images)
+                               image=image, num_images_per_prompt=args.num_images_per_prompt, height=args.height, width=args.width,
+                               guidance_rescale=args.guidance_rescale, identity_guidance_scale=args.identity_guidance_scale, **edit_kw).images)
     image_grid(all_images, len(prompts), args.num_images_per_prompt).save(args.output)
     print(f"DONE! See `{args.output}` for the results!")
 

@@ -4,7 +4,9 @@ call, plus the VAE decode.  Random-init weights, word-level stand-in tokenizer.
 
     python tools/bench_inference.py --scheduler ddim dpm_solver++ euler_ancestral plms      (STEPS=50 by default)
     python tools/bench_inference.py --edit --repeats 3       masked inpainting (strength 1: every step runs) next
-                                                             to plain sampling, fused legs only, each leg timed --repeats times"""
+                                                             to plain sampling, fused legs only, each leg timed --repeats times
+    python tools/bench_inference.py --images 1 --legs graph --guidance_rescale 0.7 --identity_guidance_scale 10
+                                                             guidance rescale and / or the three-branch identity guidance (§2.5b)"""
 import argparse, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,7 +23,15 @@ ap.add_argument("--scheduler", nargs="+", default=["ddim"], choices=sorted(SCHED
 ap.add_argument("--images", nargs="+", type=int, default=[1, 4])
 ap.add_argument("--edit", action="store_true", help="time masked inpainting (init_image + mask, strength 1) next to plain sampling; fused legs only")
 ap.add_argument("--repeats", type=int, default=1, help="timed calls per leg (their spread is the tool's run-to-run spread)")
+ap.add_argument("--guidance_rescale", type=float, default=0.0, help="passed to the pipeline (DESIGN §2.5b)")
+ap.add_argument("--identity_guidance_scale", type=float, default=None, help="passed to the pipeline: the three-branch step (DESIGN §2.5b)")
+ap.add_argument("--legs", nargs="+", default=None, choices=["generic", "fused eager", "graph"], help="time these legs only")
 args = ap.parse_args()
+guide_kw = {}
+if args.guidance_rescale > 0.0:
+    guide_kw["guidance_rescale"] = args.guidance_rescale
+if args.identity_guidance_scale is not None:
+    guide_kw["identity_guidance_scale"] = args.identity_guidance_scale
 
 dev = torch.device("cuda:0")
 steps = int(os.environ.get("STEPS", "50"))
@@ -46,9 +56,11 @@ for name in args.scheduler:
     for n in args.images:
         for mode, edit_kw in modes:
             for leg, fused, graph in (legs[1:] if args.edit else legs):
+                if args.legs is not None and leg not in args.legs:
+                    continue
                 pipe._fused_sampling = fused
                 kw = dict(num_inference_steps=steps, guidance_scale=7.5, num_images_per_prompt=n, image=image, output_type="np", use_graph=graph,
-                          **edit_kw)
+                          **edit_kw, **guide_kw)
                 pipe("a painting of *s", **dict(kw, num_inference_steps=2))
                 for _ in range(args.repeats):
                     torch.cuda.synchronize(); t0 = time.perf_counter()
