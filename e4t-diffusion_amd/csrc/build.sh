@@ -4,7 +4,7 @@ set -e
 cd "$(dirname "$0")"
 OUT=../e4t/libe4t_hip.so
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result"
-SRCS="core gemm attention norm wo elementwise image comm tome"
+SRCS="core gemm attention norm wo elementwise image comm tome freeu"
 mkdir -p obj
 pids=()
 for f in $SRCS; do

@@ -139,6 +139,8 @@ SIGNATURES = {
     "e4t_tome_match": (i32, [vp, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
     "e4t_tome_merge": (i32, [vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
     "e4t_tome_unmerge": (i32, [vp, i32, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "e4t_freeu_stats": (i32, [vp, i32, vp, i32, vp, i32, i32, i32, i32, i32, i32, vp]),
+    "e4t_freeu_apply": (i32, [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, f32, f32, i32, vp]),
     "e4t_probe_mfma_layout": (i32, [vp, vp, vp]),
     "e4t_comm_unique_id": (i32, [vp]),
     "e4t_comm_init": (i32, [C.POINTER(vp), vp, i32, i32]),
@@ -160,6 +162,7 @@ SAMPLER_MAX_HIST, SAMPLER_ROW = 4, 16
 GUIDE_PARAMS, GUIDE_STATS = 4, 4       # gp = {g, g_id, phi, 0}; gstat[b] = {f, s_c, s_e, mean_e}
 MASKED_MSE_STATS = 2050
 LOSS_HUBER, LOSS_SMOOTH_L1 = 1, 2      # e4t_robust_loss_fwd's kind
+FREEU_COEFS, FREEU_MM_CHUNKS = 7, 64   # e4t_freeu_stats' workspace: coef [B][7][C_k] | msum [B][HW] | mm [B][64][2]
 COMM_F32, COMM_BF16 = 0, 1
 COMM_SUM, COMM_AVG, COMM_MIN, COMM_MAX = 0, 1, 2, 3
 OP_SILU, OP_SILU_BWD, OP_GELU, OP_GELU_BWD, OP_LRELU, OP_LRELU_BWD, OP_QGELU, OP_QGELU_BWD = range(8)

@@ -271,6 +271,47 @@ def apply_tome_args(unet, args):
     return tome.apply_tome(unet, args.tome_ratio, use_rand=not args.tome_no_rand, generator=g)
 
 
+# ---- FreeU (e4t/freeu.py): like ToMe a runtime choice of the command line (inference.py), config.json does not record it ---------------------------
+FREEU_ARGS = ("freeu", "freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2", "freeu_version")
+
+
+def add_freeu_args(p):
+    p.add_argument("--freeu", action="store_true",
+                   help="FreeU at the UNet's decoder concatenations: amplify half of the backbone channels and damp the skip connections' "
+                        "lowest frequencies (no training, no weights; DESIGN §2.5c)")
+    p.add_argument("--freeu_b1", type=float, default=None, help="backbone factor of stage 1 (the widest maps), >= 1; default 1.3 (version 1: 1.2)")
+    p.add_argument("--freeu_b2", type=float, default=None, help="backbone factor of stage 2, >= 1; default 1.4")
+    p.add_argument("--freeu_s1", type=float, default=None, help="skip factor of stage 1, in [0, 1]; default 0.9")
+    p.add_argument("--freeu_s2", type=float, default=None, help="skip factor of stage 2, in [0, 1]; default 0.2")
+    p.add_argument("--freeu_version", type=int, choices=(1, 2), default=2,
+                   help="2 (default): the backbone factor follows the normalised channel mean of every pixel; 1: a constant factor")
+
+
+def check_freeu_args(p, args):
+    from .freeu import DEFAULTS
+    given = [n for n in ("freeu_b1", "freeu_b2", "freeu_s1", "freeu_s2") if getattr(args, n) is not None]
+    if given and not args.freeu:
+        p.error(f"--{given[0]} needs --freeu")
+    for n, dflt in DEFAULTS[args.freeu_version].items():
+        if getattr(args, "freeu_" + n) is None:
+            setattr(args, "freeu_" + n, dflt)
+    for n in ("freeu_b1", "freeu_b2"):
+        v = getattr(args, n)
+        if not (v >= 1.0 and v != float("inf")):
+            p.error(f"--{n} must be finite and >= 1")
+    for n in ("freeu_s1", "freeu_s2"):
+        if not 0.0 <= getattr(args, n) <= 1.0:
+            p.error(f"--{n} must lie in [0, 1]")
+
+
+def apply_freeu_args(unet, args):
+    """--freeu: mark the UNet (e4t.freeu.apply_freeu); returns the state or None"""
+    if not getattr(args, "freeu", False):
+        return None
+    from . import freeu
+    return freeu.apply_freeu(unet, args.freeu_b1, args.freeu_b2, args.freeu_s1, args.freeu_s2, version=args.freeu_version)
+
+
 # ---- the diffusion objective's options (E4TTrainer(snr_gamma=..., noise_offset=..., loss_type=...), DESIGN §2.4a-b): properties of the run, so config.json
 # records them like reg_lambda; tuning_e4t.py takes its own flags and inherits neither from the pre-trained run's config.json ----
 def add_objective_args(p):

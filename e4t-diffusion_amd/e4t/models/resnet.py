@@ -40,6 +40,8 @@ class FMap:
 
 
 class ResnetBlock2D(nn.Module):
+    _freeu = None     # e4t.freeu.apply_freeu puts (state, stage) here on the up-block ResBlocks it marks (sampling only, opt-in)
+
     def __init__(self, *, in_channels, out_channels=None, temb_channels=512, groups=32, eps=1e-6, dropout=0.0,
                  time_embedding_norm="default", non_linearity="swish", output_scale_factor=1.0, pre_norm=True, **unused):
         super().__init__()

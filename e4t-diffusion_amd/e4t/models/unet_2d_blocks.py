@@ -108,6 +108,8 @@ class CrossAttnUpBlock2D(nn.Module):
     def forward_nhwc(self, m, skips, temb_act, ctx, upsample_size=None):
         for r, a in zip(self.resnets, self.attentions):
             s, skips = skips[-1], skips[:-1]
+            if r._freeu is not None:               # FreeU (e4t/freeu.py, opt-in): the pair is transformed where it is handed over
+                m, s = r._freeu[0].transform(r._freeu[1], m, s)
             m = a.forward_nhwc(r.forward_nhwc(m, s, temb_act), ctx)
         if self.upsamplers is not None:
             m = self.upsamplers[0].forward_nhwc(m, upsample_size)
@@ -126,6 +128,8 @@ class UpBlock2D(nn.Module):
     def forward_nhwc(self, m, skips, temb_act, ctx=None, upsample_size=None):
         for r in self.resnets:
             s, skips = skips[-1], skips[:-1]
+            if r._freeu is not None:
+                m, s = r._freeu[0].transform(r._freeu[1], m, s)
             m = r.forward_nhwc(m, s, temb_act)
         if self.upsamplers is not None:
             m = self.upsamplers[0].forward_nhwc(m, upsample_size)

@@ -164,6 +164,19 @@ class TomePlan:
         return TomePlan(self.buf[:n].to(device), self.B, self.T, self.r)
 
 
+def freeu_ws_floats(B: int, HW: int, Ck: int) -> int:
+    """floats of e4t_freeu_stats' workspace (include/e4t_hip.h): coef [B][7][C_k] | msum [B][HW] | mm [B][64][2]"""
+    return B * (_C.FREEU_COEFS * Ck + HW + 2 * _C.FREEU_MM_CHUNKS)
+
+
+def freeu_ws_views(ws: torch.Tensor, B: int, HW: int, Ck: int) -> dict:
+    """the workspace's fields as views: coef [B, 7, C_k], msum [B, HW] (channel sums), mm [B, 64, 2] ((min, max) of msum per 1/64 of the rows)"""
+    n0 = B * _C.FREEU_COEFS * Ck
+    n1 = n0 + B * HW
+    return {"coef": ws[:n0].view(B, _C.FREEU_COEFS, Ck), "msum": ws[n0:n1].view(B, HW),
+            "mm": ws[n1:n1 + B * 2 * _C.FREEU_MM_CHUNKS].view(B, _C.FREEU_MM_CHUNKS, 2)}
+
+
 class HipBackend:
     """The one and only product backend: libe4t_hip.so on the current CUDA(HIP) device."""
 
@@ -967,6 +980,39 @@ class HipBackend:
             _ptr(y), y.stride(0), _ptr(plan.buf), _ptr(residual), _ptr(x), d, B, T, r, d, int(scale), _stream()), "e4t_tome_unmerge"),
             2.0 * B * ((3 if residual is not None else 2) * T - r) * d)
         return x
+
+    # ------------------------------------------------------------------ FreeU (csrc/freeu.hip)
+    def freeu_stats(self, h, k, B, H, W, version=2, ws=None):
+        """the statistics FreeU needs of a (hidden, skip) pair (e4t_freeu_stats in include/e4t_hip.h): h [B*H*W, C_h], k [B*H*W, C_k] (bf16)
+        -> fp32 workspace of freeu_ws_floats(B, H*W, C_k) floats (freeu_ws_views names its fields).  One launch."""
+        _rowmajor(h, "freeu_stats h"); _rowmajor(k, "freeu_stats k")
+        assert h.dtype == bf16 and k.dtype == bf16 and h.shape[0] == B * H * W and k.shape[0] == B * H * W
+        Ch, Ck = h.shape[1], k.shape[1]
+        n = freeu_ws_floats(B, H * W, Ck)
+        if ws is None:
+            ws = torch.empty(n, dtype=f32, device=h.device)
+        assert ws.dtype == f32 and ws.dim() == 1 and ws.is_contiguous() and ws.numel() >= n and ws.device == h.device
+        self._timed("freeu_stats", 14.0 * B * H * W * Ck, lambda: _C.check(self.lib.e4t_freeu_stats(
+            _ptr(h), h.stride(0), _ptr(k), k.stride(0), _ptr(ws), B, H, W, Ch, Ck, version, _stream()), "e4t_freeu_stats"),
+            2.0 * B * H * W * (Ck + (Ch if version == 2 else 0)))
+        return ws
+
+    def freeu_apply(self, h, k, ws, B, H, W, b, s, version=2, out_h=None, out_k=None):
+        """(h', k') of FreeU from the pair and freeu_stats' workspace (e4t_freeu_apply): new buffers, neither input is written.  One launch."""
+        _rowmajor(h, "freeu_apply h"); _rowmajor(k, "freeu_apply k")
+        assert h.dtype == bf16 and k.dtype == bf16 and h.shape[0] == B * H * W and k.shape[0] == B * H * W
+        Ch, Ck = h.shape[1], k.shape[1]
+        assert ws.dtype == f32 and ws.is_contiguous() and ws.numel() >= freeu_ws_floats(B, H * W, Ck) and ws.device == h.device
+        if out_h is None:
+            out_h = torch.empty((B * H * W, Ch), dtype=bf16, device=h.device)
+        if out_k is None:
+            out_k = torch.empty((B * H * W, Ck), dtype=bf16, device=h.device)
+        _rowmajor(out_h, "freeu_apply out_h"); _rowmajor(out_k, "freeu_apply out_k")
+        assert out_h.dtype == bf16 and out_k.dtype == bf16 and tuple(out_h.shape) == tuple(h.shape) and tuple(out_k.shape) == tuple(k.shape)
+        self._timed("freeu_apply", 14.0 * B * H * W * Ck, lambda: _C.check(self.lib.e4t_freeu_apply(
+            _ptr(h), h.stride(0), _ptr(k), k.stride(0), _ptr(ws), _ptr(out_h), out_h.stride(0), _ptr(out_k), out_k.stride(0), B, H, W, Ch, Ck,
+            float(b), float(s), version, _stream()), "e4t_freeu_apply"), 4.0 * B * H * W * (Ch + Ck))
+        return out_h, out_k
 
     def probe_mfma(self, device):
         rows = torch.zeros((64, 16), dtype=f32, device=device)

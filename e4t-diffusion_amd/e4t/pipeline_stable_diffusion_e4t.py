@@ -116,6 +116,21 @@ class StableDiffusionE4TPipeline:
     def enable_xformers_memory_efficient_attention(self, attention_op=None):
         self.unet.enable_xformers_memory_efficient_attention()          # selects the native fused-attention processor
 
+    def enable_freeu(self, b1=None, b2=None, s1=None, s2=None, version: int = 2):
+        """FreeU at the UNet's decoder concatenations (e4t/freeu.py): backbone factors b1, b2 >= 1 and skip factors s1, s2
+        in [0, 1] of the two stages; None = the authors' SD-1.4 values of the version.  Acts in every later call, fused and generic,
+        eager and replayed, in every branch of a guided batch.  Returns the state (which ResBlocks were marked)."""
+        from . import freeu
+        if version not in freeu.DEFAULTS:
+            raise ValueError(f"freeu version must be 1 or 2, got {version}")
+        kw = dict(freeu.DEFAULTS[version])
+        kw.update({k: v for k, v in dict(b1=b1, b2=b2, s1=s1, s2=s2).items() if v is not None})
+        return freeu.apply_freeu(self.unet, version=version, **kw)
+
+    def disable_freeu(self):
+        from . import freeu
+        freeu.remove_freeu(self.unet)
+
     def set_progress_bar_config(self, **kw):
         self._progress = kw
 

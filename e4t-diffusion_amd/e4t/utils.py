@@ -43,8 +43,8 @@ def save_e4t_encoder(encoder, save_dir, filename="encoder.pt"):
 
 
 def save_config(args_dict, save_dir):
-    from .cli_common import EMA_ARGS, TOME_ARGS
-    args_dict = {k: v for k, v in args_dict.items() if k not in TOME_ARGS + EMA_ARGS}      # token merging and the EMA are runtime choices, not part of the run
+    from .cli_common import EMA_ARGS, FREEU_ARGS, TOME_ARGS
+    args_dict = {k: v for k, v in args_dict.items() if k not in TOME_ARGS + EMA_ARGS + FREEU_ARGS}      # token merging, the EMA and FreeU are runtime choices, not part of the run
     os.makedirs(save_dir, exist_ok=True)
     with open(os.path.join(save_dir, "config.json"), "w") as f:
         json.dump(args_dict, f, indent=2, default=str)

@@ -519,6 +519,30 @@ int e4t_tome_merge(const void* x, int ldx, const int* plan, void* y, int ldy, in
 int e4t_tome_unmerge(const void* y, int ldy, const int* plan, const void* residual, void* x_out, int ldx, int B, int T, int r, int d,
                      int scale_inv_count, e4t_stream stream);
 
+/* ---------------------------------------------------------------- FreeU (freeu.hip) ---------- */
+/* FreeU (Si et al., "FreeU: Free Lunch in Diffusion U-Net", 2023) on the (hidden, skip) pair an up block hands to a ResBlock, sampling only; not in
+ * the reference.  Call site: e4t/models/unet_2d_blocks.py, CrossAttnUpBlock2D / UpBlock2D.forward_nhwc (e4t/freeu.py).  h [B*H*W][ldh] with C_h
+ * channels and k [B*H*W][ldk] with C_k channels are NHWC matrices, bf16; arithmetic is fp32, outputs are rounded once to bf16:
+ *   backbone  h' = h * ((b - 1) m^ + 1) on channels [0, C_h/2), the rest copied; version 2: m = the mean of the pixel's C_h channels,
+ *             m^ = (m - min) / (max - min) per image (0 where max == min: the authors' code divides by zero there); version 1: m^ = 1
+ *   skip      k' = k + (s - 1) LP(k), LP = the four frequencies {0, -1} x {0, -1} of the image's 2-D DFT transformed back (what fftn -> fftshift
+ *             -> scale the centre box of threshold 1 -> ifftshift -> ifftn -> real leaves of the usual recipe)
+ * b = 1 and s = 1 reproduce the inputs bit for bit.
+ * e4t_freeu_stats (one launch) fills the fp32 workspace ws, B * (7 C_k + H W + 2 * 64) floats:
+ *   coef [B][7][C_k]   X[0,0], Re X[-1,0], Im X[-1,0], Re X[0,-1], Im X[0,-1], Re X[-1,-1], Im X[-1,-1] with
+ *                      X[ky,kx] = sum_{y,x} k[y,x] exp(-2 pi i (ky y / H + kx x / W))
+ *   msum [B][H W]      (version 2) the SUM of the pixel's C_h channels: m^ is the same for the sum and the mean, and the sum is not rounded again
+ *   mm   [B][64][2]    (version 2) (min, max) of msum over each 1/64 of the image's rows ((+inf, -inf) for a part without rows); the image's
+ *                      min / max is their min / max, which e4t_freeu_apply takes
+ * Every reduction runs in a fixed order, no atomics: two runs agree to the bit.  e4t_freeu_apply (one launch) writes h_out and k_out, which must
+ * not be the inputs, from h, k and ws.  16-byte accesses: -22 before any launch unless C_h % 16 == 0, C_k % 8 == 0, H, W >= 2, H + W <= 4096,
+ * version in {1, 2}, rows 16-byte aligned. */
+#define E4T_FREEU_COEFS 7
+#define E4T_FREEU_MM_CHUNKS 64
+int e4t_freeu_stats(const void* h, int ldh, const void* k, int ldk, float* ws, int B, int H, int W, int Ch, int Ck, int version, e4t_stream stream);
+int e4t_freeu_apply(const void* h, int ldh, const void* k, int ldk, const float* ws, void* h_out, int ldho, void* k_out, int ldko, int B, int H, int W,
+                    int Ch, int Ck, float b, float s, int version, e4t_stream stream);
+
 /* ---------------------------------------------------------------- data-parallel collectives (comm.hip) ---------- */
 /* An RCCL communicator owned by the library, for a host that does not bring torch.distributed: replaces the DDP reducer accelerate wraps
  * the reference's models with (pretrain_e4t.py:410-412 `accelerator.prepare`, :648 `accelerator.backward`; tuning_e4t.py:197-200, :328).

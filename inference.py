@@ -17,6 +17,10 @@ everything outside it is held to the photograph at every denoising step (DESIGN.
     python inference.py ... --guidance_scale 7.5 --guidance_rescale 0.7 [--identity_guidance_scale 10]
 
 rescales the guided output against over-exposure and weighs the subject against the prompt.
+
+    python inference.py ... --freeu [--freeu_b1 1.3 --freeu_b2 1.4 --freeu_s1 0.9 --freeu_s2 0.2 --freeu_version 2]
+
+applies FreeU at the UNet's decoder concatenations.
 """
 import argparse
 import json
@@ -69,9 +73,11 @@ def parse_args(argv=None):
                         "--guidance_scale it favours the subject, below it the prompt; needs --guidance_scale > 1")
     from e4t import cli_common as cc
     cc.add_tome_args(p)
+    cc.add_freeu_args(p)
     cc.add_ema_args(p, training=False)
     args = p.parse_args(argv)
     cc.check_tome_args(p, args)
+    cc.check_freeu_args(p, args)
     cc.check_ema_args(p, args)
     if not 0.0 <= args.guidance_rescale <= 1.0:
         p.error("--guidance_rescale must lie in [0, 1]")
@@ -164,6 +170,7 @@ def setup(args, dev):
     unet.requires_grad_(False)
     enc.requires_grad_(False)
     cc.apply_tome_args(unet, args)
+    cc.apply_freeu_args(unet, args)
     if args.enable_xformers_memory_efficient_attention:
         pipe.enable_xformers_memory_efficient_attention()
     return dict(pipe=pipe, unet=unet, enc=enc, text=text, vae=vae, vae_encoder=pipe.vae_encoder, tokenizer=tok, scheduler=sched, base_dir=base if not args.random_init else None)

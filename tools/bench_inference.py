@@ -6,7 +6,9 @@ call, plus the VAE decode.  Random-init weights, word-level stand-in tokenizer.
     python tools/bench_inference.py --edit --repeats 3       masked inpainting (strength 1: every step runs) next
                                                              to plain sampling, fused legs only, each leg timed --repeats times
     python tools/bench_inference.py --images 1 --legs graph --guidance_rescale 0.7 --identity_guidance_scale 10
-                                                             guidance rescale and / or the three-branch identity guidance (§2.5b)"""
+                                                             guidance rescale and / or the three-branch identity guidance (§2.5b)
+    python tools/bench_inference.py --images 1 4 --legs graph --freeu [--freeu_version 1]
+                                                             FreeU at the decoder concatenations, the default factors (§2.5c)"""
 import argparse, os, sys, time
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,6 +27,8 @@ ap.add_argument("--edit", action="store_true", help="time masked inpainting (ini
 ap.add_argument("--repeats", type=int, default=1, help="timed calls per leg (their spread is the tool's run-to-run spread)")
 ap.add_argument("--guidance_rescale", type=float, default=0.0, help="passed to the pipeline (DESIGN §2.5b)")
 ap.add_argument("--identity_guidance_scale", type=float, default=None, help="passed to the pipeline: the three-branch step (DESIGN §2.5b)")
+ap.add_argument("--freeu", action="store_true", help="enable FreeU with the default factors (DESIGN §2.5c)")
+ap.add_argument("--freeu_version", type=int, choices=(1, 2), default=2)
 ap.add_argument("--legs", nargs="+", default=None, choices=["generic", "fused eager", "graph"], help="time these legs only")
 args = ap.parse_args()
 guide_kw = {}
@@ -42,6 +46,8 @@ with torch.device(dev):
 tok = WordTokenizer(base_size=49408, model_max_length=77)
 pipe = StableDiffusionE4TPipeline(vae=vae, text_encoder=text, tokenizer=tok, unet=unet, e4t_encoder=enc, scheduler=DDIMScheduler.stable_diffusion(),
                                   e4t_config=dict(placeholder_token="*s", domain_class_token="art", domain_embed_scale=0.1), already_added_placeholder_token=False)
+if args.freeu:
+    pipe.enable_freeu(version=args.freeu_version)
 image = torch.rand(1, 3, 512, 512) * 2 - 1
 modes = [("plain", {})]
 if args.edit:
