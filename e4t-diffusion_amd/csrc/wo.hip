@@ -251,7 +251,8 @@ __global__ __launch_bounds__(256) void wo_bwd_final_kernel(const e4t_wo_desc* de
 
 }  // namespace
 
-extern "C" size_t e4t_wo_vecs_floats(int row, int col) { return (size_t)4 * row + (size_t)5 * col; }
+// a, vx, da [row] and b, s, vy, db, ds [col]: exactly what V_a .. V_ds address, every word written by forward + backward
+extern "C" size_t e4t_wo_vecs_floats(int row, int col) { return (size_t)3 * row + (size_t)5 * col; }
 extern "C" size_t e4t_wo_partial_floats(int row, int col) {
   const size_t ncb = (col + 31) / 32, nrc = (row + 31) / 32;
   return ncb * row * 2 + nrc * row + ncb * col;
@@ -279,6 +280,7 @@ extern "C" int e4t_weight_prepare(const e4t_wo_desc* descs_dev, int n, int max_r
 
 extern "C" int e4t_wo_backward(const e4t_wo_desc* descs_dev, int n, int max_row, int max_col, int accumulate, e4t_stream stream) {
   E4T_REQUIRE(descs_dev && n > 0 && max_row > 0 && max_col > 0, "wo_backward: bad arguments");
+  E4T_REQUIRE(max_row % 4 == 0 && max_col % 4 == 0, "wo_backward: dims must be multiples of 4");  // float4 reads of W, dweff, a, bc along row
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(wo_bwd_row_kernel, dim3(cdiv(max_col, 4), n), dim3(256), 0, st, descs_dev, accumulate);
   E4T_CHECK_LAUNCH("wo_bwd_row_kernel");

@@ -270,7 +270,19 @@ int e4t_layernorm_param_grad(const void* x, const void* dy, const float* mean_rs
 /* ---------------------------------------------------------------- weight offsets (wo.hip) ---- */
 /* One descriptor per WeightOffsets instance (weightoffsets.py:5-23) + the projection weight it
  * modulates (cross_attention.py:506,516,518).  row = in_features, col = out_features.
- * Descriptors live in DEVICE memory (array of n); wc == NULL marks a plain weight (cast only). */
+ * Descriptors live in DEVICE memory (array of n); wc == NULL marks a plain weight (cast only).
+ * What the kernels assume of every descriptor, and the entry points cannot check (they see max_row / max_col only, which they
+ * refuse unless both are multiples of 4):
+ *  - row and col are multiples of 4, max_row / max_col are the largest of the table;
+ *  - every pointer is 16-byte aligned (float4 reads of the parameters, W, dweff and vecs), weff / weffT are 8-byte aligned with
+ *    ld_weff, ld_weffT multiples of 4 (bf16 quads; fp32 weff: 16-byte aligned), ld_dweff is a multiple of 4.  weff, weffT and dweff
+ *    may be row / column slices of a wider matrix (a fused q|k|v group): only [col][row] resp. [row][col] elements are touched;
+ *  - a table is either all weight offsets or all plain weights: e4t_wo_forward and e4t_wo_backward dereference v, wc and the
+ *    other parameters of every descriptor unconditionally, so every descriptor they get has wc != NULL (and vecs, partial, and for
+ *    the backward dweff and the nine gradients); plain weights (wc == NULL) go through e4t_weight_prepare only;
+ *  - the backward forms G = dweff o W whatever the mode: with E4T_WO_OFFSETS_ONLY its gradients are those of the offsets only
+ *    if W is all ones (what WeightOffsets.forward() passes), and g_W has no meaning;
+ *  - e4t_wo_backward reads a, b, s, vx, vy from vecs as the preceding e4t_wo_forward of the same table left them. */
 #define E4T_WO_STORE_F32 1    /* weff is fp32 [col][ld_weff] instead of bf16 */
 #define E4T_WO_OFFSETS_ONLY 2 /* weff receives the offsets themselves (WeightOffsets.forward()), not W o (1+offsets) */
 typedef struct {

@@ -8,9 +8,9 @@ bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumu
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
 
-Importable without a GPU: the attention, conv, norm and GEMM case lists, slices(), conv_slices(), norm_slices() and gemm_slices(), norm_plan() and the
-fp64 norm and GEMM references are shared with CPU tests (test_gemm_dispatch.py, test_attention_slices_cpu.py, test_conv_slices_cpu.py,
-test_norm_slices_cpu.py, test_norm_plan_cpu.py, test_gemm_slices_cpu.py).
+Importable without a GPU: the attention, conv, norm, GEMM and weight-offset case lists, slices(), conv_slices(), norm_slices(), gemm_slices() and
+wo_slices(), norm_plan() and the fp64 norm, GEMM and weight-offset references are shared with CPU tests (test_gemm_dispatch.py,
+test_attention_slices_cpu.py, test_conv_slices_cpu.py, test_norm_slices_cpu.py, test_norm_plan_cpu.py, test_gemm_slices_cpu.py, test_wo_slices_cpu.py).
 """
 from __future__ import annotations
 
@@ -1781,6 +1781,373 @@ def check_wo(hip, emu, dev, ops_mod):
     return out
 
 
+# ---- wo_forms, wo_guards: the weight-offset kernels against the fp64 DEFINITION (the two-Linear module of oracle/e4t_oracle.py) ------------
+WO_F32, WO_OFF = 1, 2      # E4T_WO_STORE_F32, E4T_WO_OFFSETS_ONLY (include/e4t_hip.h)
+WO_PNAMES = ("v", "w1", "b1", "w2", "b2", "wc", "bc", "wr", "br")
+WO_VNAMES = ("a", "b", "s", "vx", "vy", "da", "db", "ds")      # the vecs scratch, in its order (wo.hip: V_a .. V_ds)
+# Tolerance per class of row = 2 x the worst row of the CPU model of the kernels' fp32 arithmetic (tests/test_wo_slices_cpu.py: lane-strided chains
+# of stride 256, wave tree, 32-chunk partials in chunk order, multiply-adds fused where the compiled kernels fuse them, bf16 / fp32 stores) against
+# wo_ref64, over every row of every case of WO_CASES and WO_GUARD_CASES and the inputs of tests/test_wo_gpu.py; measured there (it prints them):
+# bf16 matrix 2.17e-3 (the 16 elements of the 4->4 weff), fp32 matrix 4.3e-7 (a 32x256 block of a g_wc), fp32 vector 1.35e-6 (a last quad of g_w2
+# whose four values cancel to a fifth of the vector's), scalar g_v 7.7e-8 of the sum of its absolute terms.  The former bound on every gradient was
+# 2e-4 on the whole tensor; no fp32 class gets more than 2.7e-6 now, and the bf16 rows stay under TOL1.
+WO_TOL = {"bf16": 4.4e-3, "f32": 8.7e-7, "vec": 2.7e-6, "scalar": 1.6e-7}
+WO_TOL["outer"] = WO_TOL["f32"]
+WoCase = namedtuple("WoCase", "name groups mode weff weffT seed")      # groups: ((row, (col, ...)), ...) as WOBank._build lays a fused projection out;
+#                                                                        weff / weffT False: that output pointer is NULL
+
+
+def _wo1(row, col, mode=0, weff=True, weffT=True, name=None):
+    return WoCase(name or f"{row}->{col}", ((row, (col,)),), mode, weff, weffT, 0)
+
+
+WO_TAIL_DIMS = [(4, 4), (36, 100), (100, 36), (260, 68), (68, 260), (516, 1028)]      # the minimum; across 32 and 64; 4 past 256; 4 past 512 and 1024
+WO_REAL_DIMS = [(640, 640), (768, 640), (768, 1280)]
+WO_MIXED = WoCase("mixed table", ((4, (4,)), (768, (320,)), (320, (1280,)), (260, (68,))), 0, True, True, 0)      # max_row, max_col from different entries
+WO_RAGGED = WoCase("ragged group 36->(100|36|4)", ((36, (100, 36, 4)),), 0, True, True, 0)
+WO_PRODUCT = [WoCase("q|k|v 320->3x320", ((320, (320, 320, 320)),), 0, True, True, 0),
+              WoCase("k|v 768->2x640 + ragged 36->(100|36|4)", ((768, (640, 640)), (36, (100, 36, 4))), 0, True, True, 0)]
+WO_MODES = [("offsets only, fp32, weffT NULL (WeightOffsets.forward())", WO_OFF | WO_F32, True, False), ("fp32 weff, bf16 weffT", WO_F32, True, True),
+            ("offsets only, bf16", WO_OFF, True, True), ("weff NULL", 0, False, True)]
+WO_MODE_DIMS = [(36, 100), (320, 320)]
+WO_CASES = ([_wo1(r, c) for r, c in WO_TAIL_DIMS + WO_REAL_DIMS] + [WO_MIXED] + WO_PRODUCT
+            + [_wo1(r, c, m, we, wt, f"{r}->{c} {nm}") for r, c in WO_MODE_DIMS for nm, m, we, wt in WO_MODES])
+WO_CASES = [c._replace(seed=2100 + i) for i, c in enumerate(WO_CASES)]
+WO_GUARD_CASES = [c._replace(seed=2200 + i) for i, c in enumerate([_wo1(36, 100), _wo1(260, 68), WO_RAGGED])]
+
+
+class WoValues:
+    """the inputs of one entry as dense tensors: what wo_ref64 and the CPU model read (row, col, W, params, dweff, mode as a WOEntry has them)"""
+
+    def __init__(self, row, col, W, params, dweff, mode):
+        self.row, self.col, self.W, self.params, self.dweff, self.mode = row, col, W, params, dweff, mode
+
+    def to(self, dev):
+        return WoValues(self.row, self.col, self.W.to(dev), {k: t.to(dev) for k, t in self.params.items()}, self.dweff.to(dev), self.mode)
+
+
+def wo_values(case, dev):
+    """one WoValues per entry of the case, in table order: make_wo_entry's distributions (offsets of mean magnitude ~0.3).  With OFFSETS_ONLY W is all
+    ones, as WeightOffsets.forward() passes it: the backward forms G = dweff o W whatever the mode.  Drawn on the CPU and copied: the GPU rows and
+    the CPU model that sets their tolerances (tests/test_wo_slices_cpu.py) see the same numbers."""
+    g = gen(case.seed, "cpu")
+    s = lambda *sh, sc=1.0: rnd(g, *sh, scale=sc, dtype=f32, dev="cpu").to(dev)
+    out = []
+    for row, cols in case.groups:
+        for col in cols:
+            params = dict(v=torch.full((1,), 0.8, device=dev), w1=s(row, 1, sc=0.5), b1=s(row, sc=0.5), w2=s(col, 1, sc=0.5), b2=s(col, sc=0.5),
+                          wc=s(row, row, sc=row ** -0.5), bc=s(row, sc=0.1), wr=s(col, col, sc=col ** -0.5), br=s(col, sc=0.1))
+            W = torch.ones(col, row, dtype=f32, device=dev) if case.mode & WO_OFF else s(col, row, sc=row ** -0.5)
+            out.append(WoValues(row, col, W, params, s(col, row), case.mode))
+    return out
+
+
+
+# the Python paths (tests/test_wo_gpu.py): modules with torch's default initialisation, as the trainer meets them; the CPU model holds these too
+WO_MODULE_DIMS = [(48, 80), (36, 100)]
+WO_BANK_GROUPS = ((36, (36, 36, 36)), (100, (36, 36)))      # a self-attention q|k|v and a cross-attention k|v at tiny dims
+
+
+def _wo_module_params(m):
+    return {k: t.detach() for k, t in dict(v=m.v, w1=m.linear1.weight, b1=m.linear1.bias, w2=m.linear2.weight, b2=m.linear2.bias, wc=m.linear_column.weight,
+                                           bc=m.linear_column.bias, wr=m.linear_row.weight, br=m.linear_row.bias).items()}
+
+
+def wo_module_values(row, col, seed=5):
+    """-> (state dict of a default-initialised oracle WeightOffsets(row, col), its WoValues with W = ones and a random upstream gradient in the
+    mode of WeightOffsets.forward()); on the CPU, the global generator left alone"""
+    import e4t_oracle as orc
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        m = orc.WeightOffsets(row, col)
+        g = torch.randn(col, row)
+    return m.state_dict(), WoValues(row, col, torch.ones(col, row), _wo_module_params(m), g, WO_OFF | WO_F32)
+
+
+def wo_bank_values(seed=11):
+    """per entry of WO_BANK_GROUPS, in table order: (state dict of its default-initialised WeightOffsets, [WoValues of step 1, of step 2]): the
+    projection weight is a default nn.Linear's, each step has a dW_eff of its own"""
+    import e4t_oracle as orc
+    out = []
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(seed)
+        for row, cols in WO_BANK_GROUPS:
+            for col in cols:
+                m, W = orc.WeightOffsets(row, col), torch.nn.Linear(row, col, bias=False).weight.detach()
+                out.append((m.state_dict(), [WoValues(row, col, W, _wo_module_params(m), torch.randn(col, row), 0) for _ in range(2)]))
+    return out
+
+
+def wo_ref64(e):
+    """The definition in fp64: the entry's nine parameters loaded into the literal two-Linear WeightOffsets of oracle/e4t_oracle.py, W_eff = W o (1 + m())
+    (m() itself with OFFSETS_ONLY), dweff[:, :row] backpropagated with autograd.  -> dict: weff [col][row]; g_<parameter> (the parameter's shape);
+    g_W (None with OFFSETS_ONLY); g_v_terms = sum |dvx w1| + sum |dvy w2| (what g_v is measured against: it cancels); vecs = {a, b, s, vx, vy, da,
+    db, ds} from their formulas in the header of wo.hip — the only use of the closed form on this side, for the rows that localise a failure."""
+    import e4t_oracle as orc
+    dev = e.W.device
+    m = orc.WeightOffsets(e.row, e.col).double().to(dev)
+    plist = [m.v, m.linear1.weight, m.linear1.bias, m.linear2.weight, m.linear2.bias, m.linear_column.weight, m.linear_column.bias, m.linear_row.weight, m.linear_row.bias]
+    with torch.no_grad():
+        for p, k in zip(plist, WO_PNAMES):
+            p.copy_(e.params[k].to(f64).reshape(p.shape))
+    W = e.W.to(f64).clone().requires_grad_(True)
+    off = m()
+    only = bool(e.mode & WO_OFF)
+    weff = off if only else W * (1.0 + off)
+    grads = torch.autograd.grad(weff, plist + ([] if only else [W]), e.dweff[:, :e.row].to(f64))
+    ref = {"weff": weff.detach(), "g_W": None if only else grads[-1]}
+    for k, g in zip(WO_PNAMES, grads):
+        ref["g_" + k] = g.reshape(e.params[k].shape)
+    p = {k: t.to(f64) for k, t in e.params.items()}
+    vx, vy = p["w1"][:, 0] * p["v"] + p["b1"], p["w2"][:, 0] * p["v"] + p["b2"]
+    a, b, s = p["wc"] @ vx, p["wr"] @ vy, p["wr"].sum(1)
+    G = e.dweff[:, :e.row].to(f64) * e.W.to(f64)
+    da, db, ds = G.t() @ b, G @ a, G @ p["bc"]
+    ref["vecs"] = dict(a=a, b=b, s=s, vx=vx, vy=vy, da=da, db=db, ds=ds)
+    ref["g_v_terms"] = float(((p["wc"].t() @ da) * p["w1"][:, 0]).abs().sum() + ((p["wr"].t() @ db) * p["w2"][:, 0]).abs().sum())
+    return ref
+
+
+def wo_slices(tag, got, ref, kind, norm=None, tol=None):
+    """Rows along the kernels' own decomposition (ref float64); each is the relative L2 of its slice.
+    kind 'bf16' / 'f32': a matrix in 64x64 tiles (wo_apply_kernel; g_W shares the grid of its rows): whole, the first tile, the last tile row and the
+    last tile column (the remainders col % 64 and row % 64 where there are any), their corner, the worst tile.
+    kind 'outer': blocks of 32 rows x 256 columns (wo_bwd_outer_kernel): whole, the last 32-chunk, the last 256-block, the worst block.
+    kind 'vec': blocks of 256: whole, the last block, the last quad, the worst block.
+    kind 'scalar': |got - ref| / norm (g_v cancels: norm is the fp64 sum of the absolute terms, ref['g_v_terms'])."""
+    tol = WO_TOL[kind] if tol is None else tol
+    g, r = got.to(f64), ref.to(f64)
+    fin = lambda e: float(torch.nan_to_num(torch.as_tensor(e, dtype=f64), nan=float("inf")))
+    if kind == "scalar":
+        return [(f"{tag}: |error| / sum of |terms|", fin((g - r).abs().sum() / norm), tol)]
+    out, seen = [], set()
+    if kind == "vec":
+        g, r = g.reshape(1, -1), r.reshape(1, -1)
+        bh, bw = 1, 256
+    else:
+        bh, bw = (32, 256) if kind == "outer" else (64, 64)
+    R, C = r.shape
+    d2, r2 = (g - r) ** 2, r * r
+
+    def row(label, rs, cs):
+        key = (rs.indices(R), cs.indices(C))
+        if key not in seen and d2[rs, cs].numel():
+            seen.add(key)
+            out.append((f"{tag}: {label}", fin((d2[rs, cs].sum() / (r2[rs, cs].sum() + 1e-300)).sqrt()), tol))
+    A = slice(None)
+    r_last, c_last = (R - 1) // bh * bh, (C - 1) // bw * bw
+    row("whole", A, A)
+    if kind == "vec":
+        row(f"elements {c_last}-{C - 1} (the last block of 256)", A, slice(c_last, C))
+        row(f"elements {C - 4}-{C - 1} (the last quad)", A, slice(C - 4, C))
+    elif kind == "outer":
+        row(f"rows {r_last}-{R - 1} (the last 32-chunk)", slice(r_last, R), A)
+        row(f"columns {c_last}-{C - 1} (the last 256-block)", A, slice(c_last, C))
+    else:
+        row("the first tile", slice(0, bh), slice(0, bw))
+        row(f"rows {r_last}-{R - 1} (the last tile row)", slice(r_last, R), A)
+        row(f"columns {c_last}-{C - 1} (the last tile column)", A, slice(c_last, C))
+        row("the corner tile (last tile row x last tile column)", slice(r_last, R), slice(c_last, C))
+    pad = lambda t: torch.nn.functional.pad(t, (0, -C % bw, 0, -R % bh)).reshape(-(-R // bh), bh, -(-C // bw), bw).sum(dim=(1, 3))
+    e = (pad(d2) / (pad(r2) + 1e-300)).sqrt()
+    e = torch.where(torch.isnan(e), torch.full_like(e, float("inf")), e)
+    out.append((f"{tag}: worst {'block of 256' if kind == 'vec' else f'{bh}x{bw} block'} of {e.numel()}", float(e.max()), tol))
+    return out
+
+
+def wo_value_rows(tag, got, ref, mode=0):
+    """every value row of one entry: got holds any of weff, weffT, the nine g_<parameter>, g_W and vecs (a dict); all against wo_ref64"""
+    out = []
+    if got.get("weff") is not None:
+        out += wo_slices(f"{tag} weff", got["weff"], ref["weff"], "f32" if mode & WO_F32 else "bf16")
+    if got.get("weffT") is not None:
+        out += wo_slices(f"{tag} weffT", got["weffT"], ref["weff"].t(), "bf16")
+    for k in WO_PNAMES:
+        if got.get("g_" + k) is None:
+            continue
+        if k == "v":
+            out += wo_slices(f"{tag} g_v", got["g_v"], ref["g_v"], "scalar", norm=ref["g_v_terms"])
+        else:
+            out += wo_slices(f"{tag} g_{k}", got["g_" + k], ref["g_" + k], "outer" if k in ("wc", "wr") else "vec")
+    if got.get("g_W") is not None:
+        out += wo_slices(f"{tag} g_W", got["g_W"], ref["g_W"], "f32")
+    for k, t in (got.get("vecs") or {}).items():
+        out += wo_slices(f"{tag} vecs.{k}", t, ref["vecs"][k], "vec")
+    return out
+
+
+def wo_transpose_row(tag, weff, weffT):
+    """weffT is weff (rounded to bf16 where it is stored in fp32) transposed, bit for bit: both come from one f2bf / pack4 of the same fp32 value"""
+    return [(f"{tag}: elements of weffT that are not weff{'.to(bf16)' if weff.dtype == f32 else ''} transposed", float(_neq(weffT.contiguous(), weff.to(bf16).t().contiguous())), 0.0)]
+
+
+def wo_accumulate_rows(tag, acc, g0, g):
+    """accumulate = 1 onto g0 gives g0 + g in fp32, bit for bit (g: the accumulate = 0 result of the same inputs): the nine gradients, and g_W"""
+    keys = [k for k in acc if acc[k] is not None]
+    out = [(f"{tag} accumulate = 1: elements of the nine gradients that are not G0 + g", float(sum(_neq(acc[k], g0[k] + g[k]) for k in keys if k != "g_W")), 0.0)]
+    if "g_W" in keys:
+        out.append((f"{tag} accumulate = 1: elements of g_W that are not G0 + g", float(_neq(acc["g_W"], g0["g_W"] + g["g_W"])), 0.0))
+    return out
+
+
+class _WoBuffers:
+    """Every buffer of a case's table, laid out exactly as WOBank._build lays a projection group out: one weff [tot][row], one weffT [row][tot] and
+    one dweff [tot][row] per group, the entries row slices of weff / dweff and COLUMN slices of weffT.  Every output (weff, weffT, the nine gradients,
+    g_W) lies between sentinel rows; vecs and partial are exactly e4t_wo_vecs_floats / e4t_wo_partial_floats long with sentinels behind them."""
+
+    def __init__(self, lib, ops_mod, case, vals, dev):
+        self.case, self.guards, self.scratch, self.entries, self.grads = case, [], [], [], []
+        mode, i = case.mode, 0
+        for row, cols in case.groups:
+            tot = sum(cols)
+            weff = _Guarded(tot, row, f32 if mode & WO_F32 else bf16, dev) if case.weff else None
+            weffT = _Guarded(row, tot, bf16, dev) if case.weffT else None
+            self.guards += [b for b in (weff, weffT) if b is not None]
+            dweff = torch.cat([vals[i + j].dweff for j in range(len(cols))])
+            off = 0
+            for col in cols:
+                v = vals[i]
+                G = {"g_" + k: _Guarded(p.shape[0], p.shape[1], f32, dev) if k in ("wc", "wr") else _Guarded(1, p.numel(), f32, dev) for k, p in v.params.items()}
+                if not mode & WO_OFF:
+                    G["g_W"] = _Guarded(col, row, f32, dev)
+                vecs, part = _Workspace(4 * lib.e4t_wo_vecs_floats(row, col), dev), _Workspace(4 * lib.e4t_wo_partial_floats(row, col), dev)
+                self.guards += list(G.values())
+                self.scratch += [vecs, part]
+                self.grads.append({k: b.view.reshape(v.params[k[2:]].shape) if k != "g_W" else b.view for k, b in G.items()})
+                self.entries.append(ops_mod.WOEntry(
+                    row=row, col=col, W=v.W, params=v.params, weff=weff.view[off:off + col] if weff else None, weffT=weffT.view[:, off:off + col] if weffT else None,
+                    dweff=dweff[off:off + col], grads={k: t for k, t in self.grads[-1].items() if k != "g_W"}, g_W=self.grads[-1].get("g_W"),
+                    vecs=vecs.buf.view(f32)[:vecs.n], partial=part.buf.view(f32)[:part.n], mode=mode))
+                off += col
+                i += 1
+        self.table = ops_mod.WOTable(self.entries)
+
+    def forward_outputs(self):
+        return [dict(weff=None if e.weff is None else e.weff.clone(), weffT=None if e.weffT is None else e.weffT.clone()) for e in self.entries]
+
+    def backward_outputs(self):
+        return [{k: t.clone() for k, t in g.items()} for g in self.grads]
+
+    def vecs(self):
+        out = []
+        for e in self.entries:
+            sizes = dict(a=e.row, b=e.col, s=e.col, vx=e.row, vy=e.col, da=e.row, db=e.col, ds=e.col)
+            out.append(dict(zip(WO_VNAMES, e.vecs.clone().split([sizes[k] for k in WO_VNAMES]))))
+        return out
+
+    def poison(self):
+        """NaN into every output and every word of the scratch"""
+        for e, g in zip(self.entries, self.grads):
+            for t in [e.weff, e.weffT, e.vecs, e.partial] + list(g.values()):
+                if t is not None:
+                    t.fill_(float("nan"))
+
+    def prefill(self, g):
+        """random G0 into the nine gradients and g_W of every entry -> copies of it"""
+        for gr in self.grads:
+            for t in gr.values():
+                t.copy_(torch.randn(t.shape, generator=g, device=t.device, dtype=f32))
+        return self.backward_outputs()
+
+    def scratch_nans(self):
+        return sum(int(torch.isnan(t).sum()) for e in self.entries for t in (e.vecs, e.partial))
+
+    def sentinels_changed(self):
+        return sum(b.outside() for b in self.guards) + sum(w.outside() for w in self.scratch)
+
+    def touched(self):
+        return sum(b.touched() for b in self.guards) + sum(int((w.buf != SENT32).sum()) for w in self.scratch)
+
+
+def _sync(dev):
+    if torch.device(dev).type == "cuda":
+        torch.cuda.synchronize()
+
+
+def _wo_case_rows(hip, ops_mod, case, dev, poison=False):
+    """One case: forward twice, backward (accumulate = 0) twice, backward with accumulate = 1 onto random G0; every entry of a table of several once
+    more alone.  Value rows against wo_ref64 (wo_value_rows), the exact rows (tolerance 0.0), sentinels.  poison: NaN in every output and all of
+    the scratch before the first launch; no NaN may be left in the scratch after the first backward."""
+    lib = hip.lib
+    vals = wo_values(case, dev)
+    B = _WoBuffers(lib, ops_mod, case, vals, dev)
+    if poison:
+        B.poison()
+    tag = "wo " + case.name + (" poisoned" if poison else "")
+    hip.wo_forward(B.table)
+    f1 = B.forward_outputs()
+    hip.wo_forward(B.table)
+    f2 = B.forward_outputs()
+    hip.wo_backward(B.table, False)
+    g1, vecs, nans = B.backward_outputs(), B.vecs(), B.scratch_nans()
+    hip.wo_backward(B.table, False)
+    g2 = B.backward_outputs()
+    g0 = B.prefill(gen(case.seed + 50000, dev))
+    hip.wo_backward(B.table, True)
+    g3 = B.backward_outputs()
+    _sync(dev)
+    out = [(f"{tag}: sentinel words changed around weff, weffT, the gradients, g_W, behind vecs and partial", float(B.sentinels_changed()), 0.0)]
+    if poison:
+        out.append((f"{tag}: NaN words left in vecs / partial after forward + backward (every word is written)", float(nans), 0.0))
+    both = lambda a, b: sum(_neq(a[k], b[k]) for k in a if a[k] is not None)
+    for i, v in enumerate(vals):
+        et = tag if len(vals) == 1 else f"{tag} [{i}] {v.row}->{v.col}"
+        out += wo_value_rows(et, {**f1[i], **g1[i], "vecs": vecs[i]}, wo_ref64(v), case.mode)
+        if f1[i]["weff"] is not None and f1[i]["weffT"] is not None:
+            out += wo_transpose_row(et, f1[i]["weff"], f1[i]["weffT"])
+        out.append((f"{et}: elements a second forward launch changes", float(both(f1[i], f2[i])), 0.0))
+        out.append((f"{et}: elements a second backward launch changes", float(both(g1[i], g2[i])), 0.0))
+        out += wo_accumulate_rows(et, g3[i], g0[i], g1[i])
+        if len(vals) > 1:      # the same entry alone in a table of one, dense buffers of its own: bit for bit what it gave inside the table
+            one = _WoBuffers(lib, ops_mod, _wo1(v.row, v.col, case.mode, case.weff, case.weffT), [v], dev)
+            hip.wo_forward(one.table)
+            hip.wo_backward(one.table, False)
+            _sync(dev)
+            diff = both(f1[i], one.forward_outputs()[0]) + both(g1[i], one.backward_outputs()[0])
+            out.append((f"{et}: elements that differ from the same entry run alone", float(diff + one.sentinels_changed()), 0.0))
+    return out
+
+
+def check_wo_forms(hip, emu, dev, ops_mod):
+    """WO_CASES: tail dims, the projection shapes check_wo leaves out, a mixed table, fused groups in WOBank's layout, every mode bit and NULL output;
+    every kernel of wo.hip against the fp64 definition along its own blocks, g_W and accumulate = 0 / 1 on every case"""
+    out = []
+    for c in WO_CASES:
+        out += _wo_case_rows(hip, ops_mod, c, dev)
+    return out
+
+
+def _wo_rejections(hip, dev, ops_mod):
+    """calls the three entry points must refuse (-22, an error text) before launching anything: every guarded buffer keeps its sentinels"""
+    from e4t.ops import _stream
+    lib, out = hip.lib, []
+    case = WO_GUARD_CASES[0]
+    B = _WoBuffers(lib, ops_mod, case, wo_values(case, dev), dev)
+    hip._pack_table(B.table, dev)
+    T, st = B.table.dev.data_ptr(), _stream()
+    calls = {"e4t_wo_forward": lambda *a: lib.e4t_wo_forward(*a, st), "e4t_weight_prepare": lambda *a: lib.e4t_weight_prepare(*a, st),
+             "e4t_wo_backward": lambda *a: lib.e4t_wo_backward(*a, 0, st)}
+    for name, fn in calls.items():
+        for what, args, word in (("n = 0", (T, 0, 36, 100), "bad arguments"), ("a null table", (None, 1, 36, 100), "bad arguments"),
+                                 ("max_row = 6", (T, 1, 6, 100), "multiples of 4"), ("max_col = 34", (T, 1, 36, 34), "multiples of 4")):
+            code = fn(*args)
+            _sync(dev)
+            err = _last_error(lib)
+            out.append((f"rejected: {name} with {what}: return code + 22", float(code + 22), 0.0))
+            out.append((f"rejected: {name} with {what}: error text names {word!r} (got {err!r})", float(word not in err or name[4:] not in err), 0.0))
+            out.append((f"rejected: {name} with {what}: output / scratch words changed", float(B.touched()), 0.0))
+    return out
+
+
+def check_wo_guards(hip, emu, dev, ops_mod):
+    """WO_GUARD_CASES with NaN in every output and in all of the exactly sized scratch before the first launch: outputs finite and within tolerance
+    of fp64 (a NaN anywhere makes its row infinite), no NaN left in the scratch, no sentinel changed; then the argument checks of the entry points"""
+    out = []
+    for c in WO_GUARD_CASES:
+        out += _wo_case_rows(hip, ops_mod, c, dev, poison=True)
+    return out + _wo_rejections(hip, dev, ops_mod)
+
+
 def check_image_prep(hip, emu, dev):
     """data path (N2): byte-exact against the numpy restatement of SmallestMaxSize(INTER_AREA)+crop+flip+normalise,
     every resize branch (untouched / integer box / 2x2 / general area / enlarging fixed point), ragged sizes in one batch"""
@@ -2486,4 +2853,6 @@ def all_checks(hip, emu, dev, ops_mod):
     yield "norm_guards", lambda: check_norm_guards(hip, emu, dev)
     yield "streaming", lambda: check_streaming(hip, emu, dev)
     yield "wo", lambda: check_wo(hip, emu, dev, ops_mod)
+    yield "wo_forms", lambda: check_wo_forms(hip, emu, dev, ops_mod)
+    yield "wo_guards", lambda: check_wo_guards(hip, emu, dev, ops_mod)
     yield "image_prep", lambda: check_image_prep(hip, emu, dev)
