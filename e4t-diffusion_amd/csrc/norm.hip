@@ -13,6 +13,7 @@
 // open_clip ViT (e4t/encoder.py:154).
 #include "common.h"
 #include <stdlib.h>
+#include <type_traits>
 #include "../../include/e4t_hip.h"
 
 namespace {
@@ -28,10 +29,6 @@ constexpr int GN_U = 4;          // (one-slot kernels; the two-slot ones, C > 20
 struct GNSrc {
   const bf16_t* x1; const bf16_t* x2; int C1, C2;
 };
-__device__ __forceinline__ uint4 gn_load8(const GNSrc& s, size_t pix, int c) {
-  if (c < s.C1) return *(const uint4*)(s.x1 + pix * s.C1 + c);
-  return *(const uint4*)(s.x2 + pix * s.C2 + (c - s.C1));
-}
 struct GNMap {
   int QW, PG, pg, nslot;
   int ch[GN_MAXS];      // chunk index per slot, -1 = inactive
@@ -111,6 +108,11 @@ __device__ __forceinline__ void gn_stage_stats(float* mr, const float* mean_rstd
   for (int i = threadIdx.x; i < G * 2; i += 256) mr[i] = mean_rstd_b[i];
   __syncthreads();
 }
+// the end of the chunk of pixels that starts at p0: the last chunk that holds any may be ragged, the ones after it are empty (p0 >= p1)
+__device__ __forceinline__ int gn_chunk_end(int p0, int pix_per_chunk, int HW) {
+  int p1 = p0 + pix_per_chunk; if (p1 > HW) p1 = HW;
+  return p1;
+}
 
 // partial[b][chunk][g][2] = (sum, sumsq) of x over this chunk's pixels and group g's channels
 template <int NS>
@@ -145,8 +147,7 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GNSrc s, int HW, int G, i
   const int C = s.C1 + s.C2;
   const GNMap m(C);
   const int b = blockIdx.y, chunk = blockIdx.x;
-  const int p0 = chunk * pix_per_chunk;
-  int p1 = p0 + pix_per_chunk; if (p1 > HW) p1 = HW;
+  const int p0 = chunk * pix_per_chunk, p1 = gn_chunk_end(p0, pix_per_chunk, HW);
   float sm[GN_MAXS][8], sq[GN_MAXS][8];
 #pragma unroll
   for (int i = 0; i < GN_MAXS; ++i)
@@ -156,24 +157,37 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(GNSrc s, int HW, int G, i
   gn_block_reduce(m, C, G, sm, sq, lds, nullptr, partial + ((size_t)b * gridDim.x + chunk) * G * 2, nullptr);
 }
 
-// mean_rstd[b][g] = (mean, rstd).  One wave per (b, g): lane c sums chunks c, c+64, ... in double, then a fixed-order
-// butterfly (a single thread walking the 64 chunk partials was a 13-us chain of dependent loads, 110 times per step).
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
+// The walk over the chunk partials of one (batch, group), by one wave: lane c sums chunks c, c+64, ... in double, then a fixed-order
+// butterfly (a single thread walking the 64 chunk partials was a 13-us chain of dependent loads, 110 times per step).  Every consumer of
+// the partials sums them here, so the stand-alone finalize and the fused ones are bitwise identical.
+// CENTRED partials (gn_stats_cols_kernel) are (s_c, M2_c = q_c - s_c^2 / n_c) per chunk of n_c values; their walk also gives ss = sum s_c^2:
+// with equal n_c the raw second moment is Q = sum M2_c + sum s_c^2 / n_c, formed in double by the caller.
+template <bool CENTRED>
+__device__ __forceinline__ void gn_wave_sum_partials(const float* partial /* [...][nchunk][G][2] */, int b /* 0: partial points at the batch entry's own */,
+                                                     int nchunk, int G, int g, double& s, double& q, double& ss) {
+  s = 0.0; q = 0.0; ss = 0.0;
+  for (int c = threadIdx.x & 63; c < nchunk; c += 64) {
+    const float2 pp = *(const float2*)(partial + (((size_t)b * nchunk + c) * G + g) * 2);
+    s += pp.x; q += pp.y;
+    if (CENTRED) ss += (double)pp.x * (double)pp.x;
+  }
+  s = wave_sum_f64(s); q = wave_sum_f64(q);
+  if (CENTRED) ss = wave_sum_f64(ss);
+}
+
+// mean_rstd[b][g] = (mean, rstd).  One wave per (b, g).
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* partial, int nchunk, int G, int BG, double inv_n, float eps,
                                                           float* mean_rstd) {
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (i >= BG) return;
   const int b = i / G, g = i - b * G;
-  double s = 0.0, q = 0.0;
-  for (int c = lane; c < nchunk; c += 64) {
-    const float2 pp = *(const float2*)(partial + (((size_t)b * nchunk + c) * G + g) * 2);
-    s += pp.x; q += pp.y;
-  }
-  s = wave_sum_f64(s); q = wave_sum_f64(q);
+  double s, q, ss;
+  gn_wave_sum_partials<false>(partial, b, nchunk, G, g, s, q, ss);
   if (lane == 0) {
     const double mean = s * inv_n;
     double var = q * inv_n - mean * mean;
@@ -184,36 +198,14 @@ __global__ __launch_bounds__(256) void gn_finalize_kernel(const float* partial, 
 }
 
 // Block-cooperative finalize (fused into the consumers: saves one launch per GroupNorm call each way): every wave walks
-// groups wave, wave+4, ...; lane c sums chunks c, c+64, ... in double, fixed-order butterfly — the same order as the
-// stand-alone gn_finalize_kernel, so both paths are bitwise identical; fin(g, sum0, sum1) runs on lane 0 of the wave.
-template <typename Fin>
-__device__ __forceinline__ void gn_block_sum_partials(const float* partial_b /* [nchunk][G][2] of this batch */, int nchunk, int G, Fin fin) {
+// groups wave, wave+4, ...; fin(g, s, q, ss) runs on lane 0 of the wave (ss = 0 unless CENTRED).
+template <bool CENTRED, typename Fin>
+__device__ __forceinline__ void gn_block_sum_partials(const float* partial_b, int nchunk, int G, Fin fin) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
   for (int g = wave; g < G; g += nw) {
-    double s = 0.0, q = 0.0;
-    for (int c = lane; c < nchunk; c += 64) {
-      const float2 pp = *(const float2*)(partial_b + ((size_t)c * G + g) * 2);
-      s += pp.x; q += pp.y;
-    }
-    s = wave_sum_f64(s); q = wave_sum_f64(q);
-    if (lane == 0) fin(g, s, q);
-  }
-  __syncthreads();
-}
-
-// The same walk over CENTRED partials (gn_stats_cols_kernel): partial = (s_c, M2_c = q_c - s_c^2 / n_c) per chunk of n_c values.  fin gets
-// (g, sum s_c, sum M2_c, sum s_c^2): with equal n_c the raw second moment is Q = sum M2_c + sum s_c^2 / n_c, formed in double by the caller.
-template <typename Fin>
-__device__ __forceinline__ void gn_block_sum_centred(const float* partial_b, int nchunk, int G, Fin fin) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-  for (int g = wave; g < G; g += nw) {
-    double s = 0.0, m2 = 0.0, ss = 0.0;
-    for (int c = lane; c < nchunk; c += 64) {
-      const float2 pp = *(const float2*)(partial_b + ((size_t)c * G + g) * 2);
-      s += pp.x; m2 += pp.y; ss += (double)pp.x * (double)pp.x;
-    }
-    s = wave_sum_f64(s); m2 = wave_sum_f64(m2); ss = wave_sum_f64(ss);
-    if (lane == 0) fin(g, s, m2, ss);
+    double s, q, ss;
+    gn_wave_sum_partials<CENTRED>(partial_b, 0, nchunk, G, g, s, q, ss);
+    if (lane == 0) fin(g, s, q, ss);
   }
   __syncthreads();
 }
@@ -284,14 +276,13 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(GNSrc s, const float* mea
       if (blockIdx.x == 0) { mean_rstd_out[((size_t)b * G + g) * 2] = mf; mean_rstd_out[((size_t)b * G + g) * 2 + 1] = rf; }
     };
     if (centred_nc > 0.0)
-      gn_block_sum_centred(partial + (size_t)b * npart * G * 2, npart, G,
-                           [&](int g, double sm, double m2, double ss) { fin(g, sm, m2 + ss / centred_nc); });
-    else gn_block_sum_partials(partial + (size_t)b * npart * G * 2, npart, G, fin);
+      gn_block_sum_partials<true>(partial + (size_t)b * npart * G * 2, npart, G,
+                                  [&](int g, double sm, double m2, double ss) { fin(g, sm, m2 + ss / centred_nc); });
+    else gn_block_sum_partials<false>(partial + (size_t)b * npart * G * 2, npart, G, [&](int g, double sm, double sq, double) { fin(g, sm, sq); });
   } else {
     gn_stage_stats(mr_lds, mean_rstd + (size_t)b * G * 2, G);
   }
-  const int p0 = blockIdx.x * pix_per_chunk;
-  int p1 = p0 + pix_per_chunk; if (p1 > HW) p1 = HW;
+  const int p0 = blockIdx.x * pix_per_chunk, p1 = gn_chunk_end(p0, pix_per_chunk, HW);
   if (p0 >= p1) return;
   if (silu) gn_apply_body<NS, true>(s, m, b, HW, C, cpg, p0, p1, mr_lds, gamma, beta, y, silu);
   else gn_apply_body<NS, false>(s, m, b, HW, C, cpg, p0, p1, mr_lds, gamma, beta, y, silu);
@@ -356,8 +347,7 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(GNSrc s, const bf16_t
   const int C = s.C1 + s.C2, cpg = C / G;
   const GNMap m(C);
   const int b = blockIdx.y, chunk = blockIdx.x;
-  const int p0 = chunk * pix_per_chunk;
-  int p1 = p0 + pix_per_chunk; if (p1 > HW) p1 = HW;
+  const int p0 = chunk * pix_per_chunk, p1 = gn_chunk_end(p0, pix_per_chunk, HW);
   gn_stage_stats(mr_lds, mean_rstd + (size_t)b * G * 2, G);
   float s1[GN_MAXS][8], s2[GN_MAXS][8];
 #pragma unroll
@@ -447,14 +437,13 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_kernel(GNSrc s, const bf16_t
   const int b = blockIdx.y;
   __shared__ float gs_lds[512];
   __shared__ float mr_lds[512];
-  if (!gsum) gn_block_sum_partials(partial + (size_t)b * gridDim.x * G * 2, gridDim.x, G,
-                                   [&](int g, double sm, double sq) { gs_lds[g * 2] = (float)sm; gs_lds[g * 2 + 1] = (float)sq; });
+  if (!gsum) gn_block_sum_partials<false>(partial + (size_t)b * gridDim.x * G * 2, gridDim.x, G,
+                                          [&](int g, double sm, double sq, double) { gs_lds[g * 2] = (float)sm; gs_lds[g * 2 + 1] = (float)sq; });
   else {
     for (int i = threadIdx.x; i < G * 2; i += 256) gs_lds[i] = gsum[(size_t)b * G * 2 + i];
   }
   gn_stage_stats(mr_lds, mean_rstd + (size_t)b * G * 2, G);
-  const int p0 = blockIdx.x * pix_per_chunk;
-  int p1 = p0 + pix_per_chunk; if (p1 > HW) p1 = HW;
+  const int p0 = blockIdx.x * pix_per_chunk, p1 = gn_chunk_end(p0, pix_per_chunk, HW);
   if (p0 >= p1) return;
   if (silu) gn_bwd_apply_body<NS, true>(s, m, b, HW, C, cpg, p0, p1, mr_lds, gs_lds, inv_n, dy, gamma, beta, add1, add2, dx1, dx2, silu);
   else gn_bwd_apply_body<NS, false>(s, m, b, HW, C, cpg, p0, p1, mr_lds, gs_lds, inv_n, dy, gamma, beta, add1, add2, dx1, dx2, silu);
@@ -616,37 +605,10 @@ double gn_inv_n(int C, int G, int HW) { return 1.0 / ((double)(C / G) * (double)
 
 // quads per thread of the slab kernels for this shape, 0 = not eligible
 int gn_slab_ni(int C1, int C2, int HW, int G) {
-  const bool off = false;
   const int C = C1 + C2, cpg = C / G;
-  if (off || cpg % 4 != 0 || (C2 > 0 && C1 % cpg != 0) || (long long)HW * cpg > GN_SLAB_MAX) return 0;
+  if (cpg % 4 != 0 || (C2 > 0 && C1 % cpg != 0) || (long long)HW * cpg > GN_SLAB_MAX) return 0;
   const int ni = cdiv(HW * (cpg / 4), 256);
   return ni <= 3 ? 3 : ni <= 5 ? 5 : 10;
-}
-
-
-template <int NI>
-void gn_slab_fwd_launch(const GNSrc& s, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd, int Bn, int HW, int G, float eps,
-                        int silu, hipStream_t st) {
-  const double inv_n = gn_inv_n(s.C1 + s.C2, G, HW);
-  if (silu) hipLaunchKernelGGL((gn_slab_fwd_kernel<NI, true>), dim3(G, Bn), dim3(256), 0, st, s, gamma, beta, y, mean_rstd, HW, G, inv_n, eps);
-  else hipLaunchKernelGGL((gn_slab_fwd_kernel<NI, false>), dim3(G, Bn), dim3(256), 0, st, s, gamma, beta, y, mean_rstd, HW, G, inv_n, eps);
-}
-int gn_slab_fwd(int ni, const GNSrc& s, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd, int Bn, int HW, int G, float eps,
-                int silu, hipStream_t st) {
-  E4T_LOG_LAUNCH("gn_slab_fwd_kernel<%d, %s>|B%d HW%d C%d G%d|%.0f|0", ni, silu ? "true" : "false", Bn, HW, s.C1 + s.C2, G,
-                 4.0 * Bn * (double)HW * (s.C1 + s.C2));
-  if (ni == 3) gn_slab_fwd_launch<3>(s, gamma, beta, y, mean_rstd, Bn, HW, G, eps, silu, st);
-  else if (ni == 5) gn_slab_fwd_launch<5>(s, gamma, beta, y, mean_rstd, Bn, HW, G, eps, silu, st);
-  else gn_slab_fwd_launch<10>(s, gamma, beta, y, mean_rstd, Bn, HW, G, eps, silu, st);
-  E4T_CHECK_LAUNCH("gn_slab_fwd_kernel");
-  return 0;
-}
-template <int NI>
-void gn_slab_bwd_launch(const GNSrc& s, const bf16_t* dy, const float* mean_rstd, const float* gamma, const float* beta, const bf16_t* add1,
-                        const bf16_t* add2, bf16_t* dx1, bf16_t* dx2, int Bn, int HW, int G, int silu, hipStream_t st) {
-  const float inv_n = 1.f / ((float)((s.C1 + s.C2) / G) * (float)HW);
-  if (silu) hipLaunchKernelGGL((gn_slab_bwd_kernel<NI, true>), dim3(G, Bn), dim3(256), 0, st, s, dy, mean_rstd, gamma, beta, add1, add2, dx1, dx2, HW, G, inv_n);
-  else hipLaunchKernelGGL((gn_slab_bwd_kernel<NI, false>), dim3(G, Bn), dim3(256), 0, st, s, dy, mean_rstd, gamma, beta, add1, add2, dx1, dx2, HW, G, inv_n);
 }
 
 size_t gn_lds_bytes(int C) {
@@ -802,8 +764,6 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* x, const bf16
   }
 }
 
-// column sums for norm parameter gradients: out[c] (+)= sum_r f(r, c); one thread per column, rows split over grid.y
-// mode 0: dbeta = sum dy ; mode 1: dgamma = sum dy * (x - mean_r) * rstd_r
 // ------------------------------------------------------------------------------------------------
 // Column reductions over the rows of a (M, C) bf16 matrix — bias gradients and LayerNorm parameter gradients:
 //   MODE 0:  out0[c] = sum_r x[r][c]
@@ -870,68 +830,11 @@ int gn_chunks(int Bn, int HW) {
   return ch;
 }
 
-}  // namespace
-
-// one 16-byte chunk per thread up to C = 2048, two above (GNMap): the kernels are instantiated per slot count
-#define GN_TWO_SLOTS ((C1 + C2) / 8 > 256)
-
-extern "C" int e4t_groupnorm_num_chunks(int Bn, int HW) { return gn_chunks(Bn, HW); }
-
-extern "C" size_t e4t_groupnorm_workspace_bytes(int Bn, int HW, int C, int G, int with_param_grads) {
-  const size_t ch = (size_t)gn_chunks(Bn, HW);
-  size_t b = (size_t)Bn * ch * G * 2 * sizeof(float);
-  if (with_param_grads) b += (size_t)Bn * ch * C * 2 * sizeof(float);
-  return b;
-}
-
-static int gn_check(const void* x1, int C1, const void* x2, int C2, int Bn, int HW, int G) {
-  const int C = C1 + C2;
-  E4T_REQUIRE(x1 && C1 > 0 && Bn > 0 && HW > 0 && G > 0, "groupnorm: bad arguments");
-  E4T_REQUIRE((x2 != nullptr) == (C2 > 0), "groupnorm: x2/C2 mismatch");
-  E4T_REQUIRE(C % G == 0 && C1 % 8 == 0 && C2 % 8 == 0, "groupnorm: C=%d must divide into G=%d groups, C1/C2 %% 8 == 0", C, G);
-  E4T_REQUIRE(C <= GN_MAXS * 256 * 8 && G <= 256, "groupnorm: C=%d too large", C);
-  return 0;
-}
-
-extern "C" int e4t_groupnorm_stats(const void* x1, int C1, const void* x2, int C2, int Bn, int HW, int G, float eps,
-                                   float* mean_rstd, void* workspace, size_t ws_bytes, e4t_stream stream) {
-  if (int e = gn_check(x1, C1, x2, C2, Bn, HW, G)) return e;
-  const int C = C1 + C2, ch = gn_chunks(Bn, HW), ppc = cdiv(HW, ch);
-  E4T_REQUIRE(workspace && ws_bytes >= (size_t)Bn * ch * G * 2 * sizeof(float), "groupnorm_stats: workspace too small");
-  GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-  hipStream_t st = (hipStream_t)stream;
-  E4T_LOG_LAUNCH("gn_stats_kernel<%d>|B%d HW%d C%d G%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, 2.0 * Bn * (double)HW * C);
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_stats_kernel<2>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, HW, G, ppc, (float*)workspace);
-  else hipLaunchKernelGGL((gn_stats_kernel<1>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, HW, G, ppc, (float*)workspace);
-  E4T_CHECK_LAUNCH("gn_stats_kernel");
-  const int BG = Bn * G;
-  hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(BG, 4)), dim3(256), 0, st, (const float*)workspace, ch, G, BG,
-                     gn_inv_n(C, G, HW), eps, mean_rstd);
-  E4T_CHECK_LAUNCH("gn_finalize_kernel");
-  return 0;
-}
-
-extern "C" int e4t_groupnorm_apply(const void* x1, int C1, const void* x2, int C2, const float* mean_rstd, const float* gamma,
-                                   const float* beta, void* y, int Bn, int HW, int G, int silu, e4t_stream stream) {
-  if (int e = gn_check(x1, C1, x2, C2, Bn, HW, G)) return e;
-  E4T_REQUIRE(mean_rstd && gamma && beta && y, "groupnorm_apply: null argument");
-  const int ch = gn_chunks(Bn, HW), ppc = cdiv(HW, ch);
-  GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-  E4T_LOG_LAUNCH("gn_apply_kernel<false, %d>|B%d HW%d C%d G%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C1 + C2, G, 4.0 * Bn * (double)HW * (C1 + C2));
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<false, 2>), dim3(ch, Bn), dim3(256), 0, (hipStream_t)stream, s, mean_rstd, gamma, beta, (bf16_t*)y, HW, G, ppc,
-                     silu, (const float*)nullptr, 0, 0.0, 0.f, (float*)nullptr, 0.0);
-  else hipLaunchKernelGGL((gn_apply_kernel<false, 1>), dim3(ch, Bn), dim3(256), 0, (hipStream_t)stream, s, mean_rstd, gamma, beta, (bf16_t*)y, HW, G, ppc,
-                     silu, (const float*)nullptr, 0, 0.0, 0.f, (float*)nullptr, 0.0);
-  E4T_CHECK_LAUNCH("gn_apply_kernel");
-  return 0;
-}
-
 // Chunk partials (the format gn_stats_kernel writes: partial[b][chunk][g][2]) from the column statistics the producing GEMM /
 // conv epilogue left behind (gemm.hip, write_tile): cs[blk][c][2] = (sum, sum of squares) of channel c over the 32 pixels of
 // block blk.  One workgroup per (chunk of 32-pixel blocks, batch entry): thread t owns columns t, t+256, ...; a few KB .. MB of
 // statistics are read instead of a pass over the whole activation.  Deterministic (fixed summation order).  The second entry of a
 // partial is CENTRED here (see below): only gn_apply_kernel<true, *> with centred_nc > 0 consumes these partials.
-namespace {
 __global__ __launch_bounds__(256) void gn_stats_cols_kernel(const float* cs1, int C1, const float* cs2, int C2, int nblk_img, int blk_per_chunk,
                                                             int G, float* partial) {
   extern __shared__ float lds[];            // [C][2] column totals of this chunk
@@ -961,147 +864,245 @@ __global__ __launch_bounds__(256) void gn_stats_cols_kernel(const float* cs1, in
     o[0] = sf; o[1] = (float)m2;
   }
 }
+
+// ------------------------------------------------------------------------------------------------
+// Host side: one plan per GroupNorm call and ONE launch statement per kernel template, with its launch-log line (the key
+// tools/roofline_report.py joins traces on) and its launch check beside it.  A template that several entry points launch has a
+// launch_* function; the others are launched where their one entry point needs them.
+// ------------------------------------------------------------------------------------------------
+// Run-time value -> template argument: f(std::integral_constant<.., V>), which launches, for the V among Vs that equals v, then the launch
+// check; a value that is not in the list is an error, not a skipped launch.  Two template arguments travel as the decimal digits of one
+// value.  (E4T_REQUIRE and E4T_CHECK_LAUNCH return from the function they stand in: here, not in the lambdas.)
+template <auto... Vs, typename T, typename F>
+int pick(const char* kernel, T v, F&& f) {
+  const bool hit = ((v == Vs ? (f(std::integral_constant<decltype(Vs), Vs>{}), true) : false) || ...);
+  E4T_REQUIRE(hit, "%s: no instantiation for %d", kernel, (int)v);
+  E4T_CHECK_LAUNCH(kernel);
+  return 0;
+}
+
+// What the GroupNorm entry points need to know about a call's shape, worked out once.
+struct GNPlan {
+  GNSrc s;
+  int Bn, HW, G, C, cpg;
+  int ns;                 // 16-byte chunks per thread: one up to C = 2048, two above (GNMap); the chunked kernels are instantiated per count
+  int ni;                 // quads per thread of the slab kernels (gn_slab_ni), 0 = the chunked path
+  int ch, ppc;            // chunked path: chunks of pixels (workgroups) per batch entry, pixels per chunk
+  double inv_n;           // gn_inv_n, for the forward statistics
+  size_t partial_bytes;   // partial[Bn][ch][G][2]: what the chunked path needs of the workspace
+};
+// the part of the plan that (Bn, HW, G) decide: all that e4t_groupnorm_workspace_bytes, which validates nothing, asks for
+GNPlan gn_plan_chunks(int Bn, int HW, int G) {
+  GNPlan p{};
+  p.Bn = Bn; p.HW = HW; p.G = G;
+  p.ch = gn_chunks(Bn, HW); p.ppc = cdiv(HW, p.ch);
+  p.partial_bytes = (size_t)Bn * p.ch * G * 2 * sizeof(float);
+  return p;
+}
+int gn_plan(GNPlan& p, const void* x1, int C1, const void* x2, int C2, int Bn, int HW, int G) {
+  const int C = C1 + C2;
+  E4T_REQUIRE(x1 && C1 > 0 && Bn > 0 && HW > 0 && G > 0, "groupnorm: bad arguments");
+  E4T_REQUIRE((x2 != nullptr) == (C2 > 0), "groupnorm: x2/C2 mismatch");
+  E4T_REQUIRE(C % G == 0 && C1 % 8 == 0 && C2 % 8 == 0, "groupnorm: C=%d must divide into G=%d groups, C1/C2 %% 8 == 0", C, G);
+  E4T_REQUIRE(C <= GN_MAXS * 256 * 8 && G <= 256, "groupnorm: C=%d too large", C);
+  p = gn_plan_chunks(Bn, HW, G);
+  p.s = GNSrc{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
+  p.C = C; p.cpg = C / G;
+  p.ns = C / 8 > 256 ? 2 : 1;
+  p.ni = gn_slab_ni(C1, C2, HW, G);
+  p.inv_n = gn_inv_n(C, G, HW);
+  return 0;
+}
+int launch_gn_stats(const GNPlan& p, float* partial, hipStream_t st) {
+  E4T_LOG_LAUNCH("gn_stats_kernel<%d>|B%d HW%d C%d G%d|%.0f|0", p.ns, p.Bn, p.HW, p.C, p.G, 2.0 * p.Bn * (double)p.HW * p.C);
+  return pick<1, 2>("gn_stats_kernel", p.ns, [&](auto NS) {
+    hipLaunchKernelGGL((gn_stats_kernel<NS.value>), dim3(p.ch, p.Bn), dim3(256), gn_lds_bytes(p.C), st, p.s, p.HW, p.G, p.ppc, partial);
+  });
+}
+// FUSED: the npart chunk partials per batch entry are finalised in the prologue (centred_nc > 0: centred ones, over chunks of that many
+// values) and the statistics written to mean_rstd_out; otherwise mean_rstd holds them already and those five arguments are 0.
+template <bool FUSED>
+int launch_gn_apply(const GNPlan& p, const float* mean_rstd, const float* partial, int npart, float eps, float* mean_rstd_out, double centred_nc,
+                    const float* gamma, const float* beta, bf16_t* y, int silu, hipStream_t st) {
+  const double bytes = 4.0 * p.Bn * (double)p.HW * p.C;
+  if (FUSED) E4T_LOG_LAUNCH("gn_apply_kernel<true, %d>|B%d HW%d C%d G%d silu%d|%.0f|0", p.ns, p.Bn, p.HW, p.C, p.G, silu, bytes);
+  else E4T_LOG_LAUNCH("gn_apply_kernel<false, %d>|B%d HW%d C%d G%d|%.0f|0", p.ns, p.Bn, p.HW, p.C, p.G, bytes);
+  return pick<1, 2>("gn_apply_kernel", p.ns, [&](auto NS) {
+    hipLaunchKernelGGL((gn_apply_kernel<FUSED, NS.value>), dim3(p.ch, p.Bn), dim3(256), 0, st, p.s, mean_rstd, gamma, beta, y, p.HW, p.G, p.ppc, silu,
+                       partial, npart, FUSED ? p.inv_n : 0.0, eps, mean_rstd_out, centred_nc);
+  });
+}
+// the slab kernels' <NI, SILU> as the key NI * 10 + SILU
+template <typename F>
+int pick_slab(const char* kernel, const GNPlan& p, int silu, F&& f) {
+  return pick<30, 31, 50, 51, 100, 101>(kernel, p.ni * 10 + (silu != 0), f);
+}
+int launch_gn_slab_fwd(const GNPlan& p, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd, float eps, int silu, hipStream_t st) {
+  E4T_LOG_LAUNCH("gn_slab_fwd_kernel<%d, %s>|B%d HW%d C%d G%d|%.0f|0", p.ni, silu ? "true" : "false", p.Bn, p.HW, p.C, p.G,
+                 4.0 * p.Bn * (double)p.HW * p.C);
+  return pick_slab("gn_slab_fwd_kernel", p, silu, [&](auto K) {
+    hipLaunchKernelGGL((gn_slab_fwd_kernel<K.value / 10, K.value % 10 != 0>), dim3(p.G, p.Bn), dim3(256), 0, st, p.s, gamma, beta, y, mean_rstd, p.HW,
+                       p.G, p.inv_n, eps);
+  });
+}
+// the check every LayerNorm entry point makes (args_ok: its own pointers and M)
+int ln_check(bool args_ok, const char* entry, int D) {
+  E4T_REQUIRE(args_ok, "%s: null argument", entry);
+  E4T_REQUIRE(D % 8 == 0 && D <= LN_MAXC * 64 * 8, "layernorm: D=%d must be a multiple of 8 and <= 1536", D);
+  return 0;
+}
+int launch_ln_fwd(const void* x, bool xf32, const float* gamma, const float* beta, bf16_t* y, float* mean_rstd, int M, int D, float eps, hipStream_t st) {
+  if (int e = ln_check(x && gamma && beta && y && M > 0, "layernorm_fwd", D)) return e;
+  const int ncl = cdiv(D / 8, 64);      // 16-byte chunks per lane: the kernels are instantiated per count (no dead loads)
+  // rows per wave: 4 / 2 / 2 for 1 / 2 / 3 chunks per lane; small M keeps one row per wave (enough blocks to fill the chip first)
+  const int rpw = ((long long)M * ncl < 256 * 4 * 8 || xf32) ? 1 : ncl == 1 ? 4 : 2;
+  E4T_LOG_LAUNCH("ln_fwd_kernel<%d, %d, %s>|M%d D%d|%.0f|0", ncl, rpw, xf32 ? "true" : "false", M, D, (xf32 ? 6.0 : 4.0) * (double)M * D);
+  // the nine instantiations, as the key ncl * 100 + rpw * 10 + xf32
+  return pick<110, 210, 310, 140, 220, 320, 111, 211, 311>("ln_fwd_kernel", ncl * 100 + rpw * 10 + xf32, [&](auto K) {
+    constexpr int NC = K.value / 100, R = K.value / 10 % 10;
+    hipLaunchKernelGGL((ln_fwd_kernel<NC, R, K.value % 10 != 0>), dim3(cdiv(M, 4 * R)), dim3(256), 0, st, x, gamma, beta, y, mean_rstd, M, D, eps);
+  });
+}
+// stage 1 of a column reduction over ns row splits
+template <int MODE>
+int launch_colreduce(const bf16_t* x, int ldx, const bf16_t* dy, const float* mean_rstd, int M, int C, int ns, float* part0, float* part1,
+                     hipStream_t st) {
+  hipLaunchKernelGGL(colreduce_kernel<MODE>, dim3(cdiv(C, 64), ns), dim3(256), 0, st, x, ldx, dy, mean_rstd, M, C, cdiv(M, ns), part0, part1);
+  E4T_CHECK_LAUNCH("colreduce_kernel");
+  return 0;
+}
+int launch_colreduce_final(const float* part, int ns, int C, float* out, int accumulate, hipStream_t st) {
+  hipLaunchKernelGGL(colreduce_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, part, ns, C, out, accumulate);
+  E4T_CHECK_LAUNCH("colreduce_final_kernel");
+  return 0;
+}
+
 }  // namespace
 
-extern "C" int e4t_groupnorm_fwd_cs(const void* x1, int C1, const float* cs1, const void* x2, int C2, const float* cs2, const float* gamma,
-                                    const float* beta, void* y, float* mean_rstd, int Bn, int HW, int G, float eps, int silu,
-                                    void* workspace, size_t ws_bytes, e4t_stream stream) {
-  if (int e = gn_check(x1, C1, x2, C2, Bn, HW, G)) return e;
-  E4T_REQUIRE(cs1 && ((cs2 != nullptr) == (C2 > 0)) && gamma && beta && y && mean_rstd && HW % 32 == 0, "groupnorm_fwd_cs: bad arguments");
-  if (const int ni = gn_slab_ni(C1, C2, HW, G)) {      // small map: one launch, the column statistics are not needed
-    GNSrc ss{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-    return gn_slab_fwd(ni, ss, gamma, beta, (bf16_t*)y, mean_rstd, Bn, HW, G, eps, silu, (hipStream_t)stream);
-  }
-  const int C = C1 + C2, ch = gn_chunks(Bn, HW), ppc = cdiv(HW, ch), nblk = HW / 32;
-  const int npart = ch < nblk ? ch : nblk;                   // chunks of whole 32-pixel blocks
-  E4T_REQUIRE(nblk % npart == 0, "groupnorm_fwd_cs: %d blocks do not split into %d chunks", nblk, npart);
-  E4T_REQUIRE(workspace && ws_bytes >= (size_t)Bn * npart * G * 2 * sizeof(float), "groupnorm_fwd_cs: workspace too small");
-  GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
+extern "C" int e4t_groupnorm_num_chunks(int Bn, int HW) { return gn_chunks(Bn, HW); }
+
+extern "C" size_t e4t_groupnorm_workspace_bytes(int Bn, int HW, int C, int G, int with_param_grads) {
+  const GNPlan p = gn_plan_chunks(Bn, HW, G);
+  return p.partial_bytes + (with_param_grads ? (size_t)Bn * p.ch * C * 2 * sizeof(float) : 0);
+}
+
+extern "C" int e4t_groupnorm_stats(const void* x1, int C1, const void* x2, int C2, int Bn, int HW, int G, float eps,
+                                   float* mean_rstd, void* workspace, size_t ws_bytes, e4t_stream stream) {
+  GNPlan p;
+  if (int e = gn_plan(p, x1, C1, x2, C2, Bn, HW, G)) return e;
+  E4T_REQUIRE(workspace && ws_bytes >= p.partial_bytes, "groupnorm_stats: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  E4T_LOG_LAUNCH("gn_stats_cols_kernel|B%d HW%d C%d G%d|%.0f|0", Bn, HW, C, G, 8.0 * Bn * (double)nblk * C);
-  hipLaunchKernelGGL(gn_stats_cols_kernel, dim3(npart, Bn), dim3(256), (size_t)C * 2 * sizeof(float), st, cs1, C1, cs2, C2, nblk, nblk / npart, G,
-                     (float*)workspace);
-  E4T_CHECK_LAUNCH("gn_stats_cols_kernel");
-  E4T_LOG_LAUNCH("gn_apply_kernel<true, %d>|B%d HW%d C%d G%d silu%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, silu, 4.0 * Bn * (double)HW * C);
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<true, 2>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, npart, gn_inv_n(C, G, HW), eps, mean_rstd, (double)(nblk / npart) * 32.0 * (double)(C / G));
-  else hipLaunchKernelGGL((gn_apply_kernel<true, 1>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, npart, gn_inv_n(C, G, HW), eps, mean_rstd, (double)(nblk / npart) * 32.0 * (double)(C / G));
-  E4T_CHECK_LAUNCH("gn_apply_kernel");
+  if (int e = launch_gn_stats(p, (float*)workspace, st)) return e;
+  const int BG = p.Bn * p.G;
+  hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(BG, 4)), dim3(256), 0, st, (const float*)workspace, p.ch, p.G, BG, p.inv_n, eps, mean_rstd);
+  E4T_CHECK_LAUNCH("gn_finalize_kernel");
   return 0;
+}
+
+extern "C" int e4t_groupnorm_apply(const void* x1, int C1, const void* x2, int C2, const float* mean_rstd, const float* gamma,
+                                   const float* beta, void* y, int Bn, int HW, int G, int silu, e4t_stream stream) {
+  GNPlan p;
+  if (int e = gn_plan(p, x1, C1, x2, C2, Bn, HW, G)) return e;
+  E4T_REQUIRE(mean_rstd && gamma && beta && y, "groupnorm_apply: null argument");
+  return launch_gn_apply<false>(p, mean_rstd, nullptr, 0, 0.f, nullptr, 0.0, gamma, beta, (bf16_t*)y, silu, (hipStream_t)stream);
 }
 
 extern "C" int e4t_groupnorm_fwd(const void* x1, int C1, const void* x2, int C2, const float* gamma, const float* beta, void* y,
                                  float* mean_rstd, int Bn, int HW, int G, float eps, int silu, void* workspace, size_t ws_bytes,
                                  e4t_stream stream) {
-  if (int e = gn_check(x1, C1, x2, C2, Bn, HW, G)) return e;
+  GNPlan p;
+  if (int e = gn_plan(p, x1, C1, x2, C2, Bn, HW, G)) return e;
   E4T_REQUIRE(gamma && beta && y && mean_rstd, "groupnorm_fwd: null argument");
-  if (const int ni = gn_slab_ni(C1, C2, HW, G)) {
-    GNSrc ss{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-    return gn_slab_fwd(ni, ss, gamma, beta, (bf16_t*)y, mean_rstd, Bn, HW, G, eps, silu, (hipStream_t)stream);
-  }
-  const int C = C1 + C2, ch = gn_chunks(Bn, HW), ppc = cdiv(HW, ch);
-  E4T_REQUIRE(workspace && ws_bytes >= (size_t)Bn * ch * G * 2 * sizeof(float), "groupnorm_fwd: workspace too small");
-  GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
   hipStream_t st = (hipStream_t)stream;
-  E4T_LOG_LAUNCH("gn_stats_kernel<%d>|B%d HW%d C%d G%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, 2.0 * Bn * (double)HW * C);
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_stats_kernel<2>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, HW, G, ppc, (float*)workspace);
-  else hipLaunchKernelGGL((gn_stats_kernel<1>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, HW, G, ppc, (float*)workspace);
-  E4T_CHECK_LAUNCH("gn_stats_kernel");
-  E4T_LOG_LAUNCH("gn_apply_kernel<true, %d>|B%d HW%d C%d G%d silu%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, silu, 4.0 * Bn * (double)HW * C);
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_apply_kernel<true, 2>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, ch, gn_inv_n(C, G, HW), eps, mean_rstd, 0.0);
-  else hipLaunchKernelGGL((gn_apply_kernel<true, 1>), dim3(ch, Bn), dim3(256), 0, st, s, (const float*)nullptr, gamma, beta, (bf16_t*)y, HW, G, ppc, silu,
-                     (const float*)workspace, ch, gn_inv_n(C, G, HW), eps, mean_rstd, 0.0);
-  E4T_CHECK_LAUNCH("gn_apply_kernel");
-  return 0;
+  if (p.ni) return launch_gn_slab_fwd(p, gamma, beta, (bf16_t*)y, mean_rstd, eps, silu, st);      // small map: one launch, no workspace
+  E4T_REQUIRE(workspace && ws_bytes >= p.partial_bytes, "groupnorm_fwd: workspace too small");
+  if (int e = launch_gn_stats(p, (float*)workspace, st)) return e;
+  return launch_gn_apply<true>(p, nullptr, (const float*)workspace, p.ch, eps, mean_rstd, 0.0, gamma, beta, (bf16_t*)y, silu, st);
+}
+
+// The forward from the column statistics the producing GEMM / conv epilogue left behind (gn_stats_cols_kernel) instead of a pass over x.
+extern "C" int e4t_groupnorm_fwd_cs(const void* x1, int C1, const float* cs1, const void* x2, int C2, const float* cs2, const float* gamma,
+                                    const float* beta, void* y, float* mean_rstd, int Bn, int HW, int G, float eps, int silu,
+                                    void* workspace, size_t ws_bytes, e4t_stream stream) {
+  GNPlan p;
+  if (int e = gn_plan(p, x1, C1, x2, C2, Bn, HW, G)) return e;
+  E4T_REQUIRE(cs1 && ((cs2 != nullptr) == (C2 > 0)) && gamma && beta && y && mean_rstd && HW % 32 == 0, "groupnorm_fwd_cs: bad arguments");
+  hipStream_t st = (hipStream_t)stream;
+  if (p.ni) return launch_gn_slab_fwd(p, gamma, beta, (bf16_t*)y, mean_rstd, eps, silu, st);      // small map: the column statistics are not needed
+  const int nblk = p.HW / 32, npart = p.ch < nblk ? p.ch : nblk;      // chunks of whole 32-pixel blocks
+  E4T_REQUIRE(nblk % npart == 0, "groupnorm_fwd_cs: %d blocks do not split into %d chunks", nblk, npart);
+  E4T_REQUIRE(workspace && ws_bytes >= (size_t)p.Bn * npart * p.G * 2 * sizeof(float), "groupnorm_fwd_cs: workspace too small");      // npart <= ch partials
+  E4T_LOG_LAUNCH("gn_stats_cols_kernel|B%d HW%d C%d G%d|%.0f|0", p.Bn, p.HW, p.C, p.G, 8.0 * p.Bn * (double)nblk * p.C);
+  float* partial = (float*)workspace;
+  hipLaunchKernelGGL(gn_stats_cols_kernel, dim3(npart, p.Bn), dim3(256), (size_t)p.C * 2 * sizeof(float), st, cs1, p.s.C1, cs2, p.s.C2, nblk,
+                     nblk / npart, p.G, partial);
+  E4T_CHECK_LAUNCH("gn_stats_cols_kernel");
+  const double centred_nc = (double)(nblk / npart) * 32.0 * (double)p.cpg;      // values per chunk: the partials are centred
+  return launch_gn_apply<true>(p, nullptr, partial, npart, eps, mean_rstd, centred_nc, gamma, beta, (bf16_t*)y, silu, st);
 }
 
 extern "C" int e4t_groupnorm_bwd(const void* x1, int C1, const void* x2, int C2, const void* dy, const float* mean_rstd,
                                  const float* gamma, const float* beta, const void* add1, const void* add2, void* dx1, void* dx2,
                                  float* dgamma_dbeta_partial, int Bn, int HW, int G, int silu, void* workspace,
                                  size_t ws_bytes, e4t_stream stream) {
-  if (int e = gn_check(x1, C1, x2, C2, Bn, HW, G)) return e;
+  GNPlan p;
+  if (int e = gn_plan(p, x1, C1, x2, C2, Bn, HW, G)) return e;
   E4T_REQUIRE(dy && mean_rstd && gamma && beta && dx1 && ((dx2 != nullptr) == (C2 > 0)) && (!add2 || C2 > 0), "groupnorm_bwd: null argument");
-  if (const int ni = dgamma_dbeta_partial ? 0 : gn_slab_ni(C1, C2, HW, G)) {      // (per-channel parameter gradients: chunked path)
-    GNSrc ss{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-    E4T_LOG_LAUNCH("gn_slab_bwd_kernel<%d, %s>|B%d HW%d C%d G%d add%d|%.0f|0", ni, silu ? "true" : "false", Bn, HW, C1 + C2, G,
-                   (add1 != nullptr) + (add2 != nullptr), 2.0 * Bn * (double)HW * (3.0 * (C1 + C2) + (add1 ? C1 : 0) + (add2 ? C2 : 0)));
-    if (ni == 3) gn_slab_bwd_launch<3>(ss, (const bf16_t*)dy, mean_rstd, gamma, beta, (const bf16_t*)add1, (const bf16_t*)add2, (bf16_t*)dx1, (bf16_t*)dx2, Bn, HW, G, silu, (hipStream_t)stream);
-    else if (ni == 5) gn_slab_bwd_launch<5>(ss, (const bf16_t*)dy, mean_rstd, gamma, beta, (const bf16_t*)add1, (const bf16_t*)add2, (bf16_t*)dx1, (bf16_t*)dx2, Bn, HW, G, silu, (hipStream_t)stream);
-    else gn_slab_bwd_launch<10>(ss, (const bf16_t*)dy, mean_rstd, gamma, beta, (const bf16_t*)add1, (const bf16_t*)add2, (bf16_t*)dx1, (bf16_t*)dx2, Bn, HW, G, silu, (hipStream_t)stream);
-    E4T_CHECK_LAUNCH("gn_slab_bwd_kernel");
-    return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const bf16_t *dyb = (const bf16_t*)dy, *a1 = (const bf16_t*)add1, *a2 = (const bf16_t*)add2;
+  bf16_t *d1 = (bf16_t*)dx1, *d2 = (bf16_t*)dx2;
+  const float inv_n = 1.f / ((float)p.cpg * (float)p.HW);
+  const int nadd = (add1 != nullptr) + (add2 != nullptr);
+  // bytes of x, dy, dx and the shortcut gradients given
+  const double bytes = 2.0 * p.Bn * (double)p.HW * (3.0 * p.C + (add1 ? p.s.C1 : 0) + (add2 ? p.s.C2 : 0));
+  if (p.ni && !dgamma_dbeta_partial) {      // (per-channel parameter gradients: chunked path)
+    E4T_LOG_LAUNCH("gn_slab_bwd_kernel<%d, %s>|B%d HW%d C%d G%d add%d|%.0f|0", p.ni, silu ? "true" : "false", p.Bn, p.HW, p.C, p.G, nadd, bytes);
+    return pick_slab("gn_slab_bwd_kernel", p, silu, [&](auto K) {
+      hipLaunchKernelGGL((gn_slab_bwd_kernel<K.value / 10, K.value % 10 != 0>), dim3(p.G, p.Bn), dim3(256), 0, st, p.s, dyb, mean_rstd, gamma, beta, a1,
+                         a2, d1, d2, p.HW, p.G, inv_n);
+    });
   }
-  const int C = C1 + C2, ch = gn_chunks(Bn, HW), ppc = cdiv(HW, ch), BG = Bn * G;
-  const size_t need = ((size_t)Bn * ch * G * 2 + (size_t)BG * 2) * sizeof(float);
+  // The workspace contract is the partials plus Bn * G * 2 floats.  Nothing reads those floats any more (they held the finalised (S1, S2)
+  // before gn_bwd_apply_kernel reduced the partials itself), but callers allocate to this size and it is what they are checked against.
+  const size_t need = p.partial_bytes + (size_t)p.Bn * p.G * 2 * sizeof(float);
   E4T_REQUIRE(workspace && ws_bytes >= need, "groupnorm_bwd: workspace too small (%zu < %zu)", ws_bytes, need);
   float* partial = (float*)workspace;
-  float* gsum = partial + (size_t)Bn * ch * G * 2;
-  GNSrc s{(const bf16_t*)x1, (const bf16_t*)x2, C1, C2};
-  hipStream_t st = (hipStream_t)stream;
-  E4T_LOG_LAUNCH("gn_bwd_stats_kernel<%d>|B%d HW%d C%d G%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, 4.0 * Bn * (double)HW * C);
-  E4T_LOG_LAUNCH("gn_bwd_apply_kernel<%d>|B%d HW%d C%d G%d add%d|%.0f|0", GN_TWO_SLOTS ? 2 : 1, Bn, HW, C, G, (add1 != nullptr) + (add2 != nullptr),
-                 2.0 * Bn * (double)HW * (3.0 * C + (add1 ? C1 : 0) + (add2 ? C2 : 0)));
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_bwd_stats_kernel<2>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, (const bf16_t*)dy, mean_rstd,
-                     gamma, beta, HW, G, ppc, silu, partial, dgamma_dbeta_partial);
-  else hipLaunchKernelGGL((gn_bwd_stats_kernel<1>), dim3(ch, Bn), dim3(256), gn_lds_bytes(C), st, s, (const bf16_t*)dy, mean_rstd,
-                     gamma, beta, HW, G, ppc, silu, partial, dgamma_dbeta_partial);
-  E4T_CHECK_LAUNCH("gn_bwd_stats_kernel");
-  (void)gsum;     // (S1, S2) are reduced from the partials inside gn_bwd_apply_kernel: no finalize launch
-  if (GN_TWO_SLOTS) hipLaunchKernelGGL((gn_bwd_apply_kernel<2>), dim3(ch, Bn), dim3(256), 0, st, s, (const bf16_t*)dy, mean_rstd, (const float*)nullptr, gamma, beta,
-                     (const bf16_t*)add1, (const bf16_t*)add2, (bf16_t*)dx1, (bf16_t*)dx2, HW, G, ppc, silu, 1.f / ((float)(C / G) * (float)HW),
-                     (const float*)partial);
-  else hipLaunchKernelGGL((gn_bwd_apply_kernel<1>), dim3(ch, Bn), dim3(256), 0, st, s, (const bf16_t*)dy, mean_rstd, (const float*)nullptr, gamma, beta,
-                     (const bf16_t*)add1, (const bf16_t*)add2, (bf16_t*)dx1, (bf16_t*)dx2, HW, G, ppc, silu, 1.f / ((float)(C / G) * (float)HW),
-                     (const float*)partial);
-  E4T_CHECK_LAUNCH("gn_bwd_apply_kernel");
-  return 0;
+  E4T_LOG_LAUNCH("gn_bwd_stats_kernel<%d>|B%d HW%d C%d G%d|%.0f|0", p.ns, p.Bn, p.HW, p.C, p.G, 4.0 * p.Bn * (double)p.HW * p.C);
+  const int e = pick<1, 2>("gn_bwd_stats_kernel", p.ns, [&](auto NS) {
+    hipLaunchKernelGGL((gn_bwd_stats_kernel<NS.value>), dim3(p.ch, p.Bn), dim3(256), gn_lds_bytes(p.C), st, p.s, dyb, mean_rstd, gamma, beta, p.HW, p.G,
+                       p.ppc, silu, partial, dgamma_dbeta_partial);
+  });
+  if (e) return e;
+  // (S1, S2) are reduced from the partials in gn_bwd_apply_kernel's prologue (its gsum argument is null): no finalize launch
+  E4T_LOG_LAUNCH("gn_bwd_apply_kernel<%d>|B%d HW%d C%d G%d add%d|%.0f|0", p.ns, p.Bn, p.HW, p.C, p.G, nadd, bytes);
+  return pick<1, 2>("gn_bwd_apply_kernel", p.ns, [&](auto NS) {
+    hipLaunchKernelGGL((gn_bwd_apply_kernel<NS.value>), dim3(p.ch, p.Bn), dim3(256), 0, st, p.s, dyb, mean_rstd, (const float*)nullptr, gamma, beta, a1,
+                       a2, d1, d2, p.HW, p.G, p.ppc, silu, inv_n, (const float*)partial);
+  });
 }
-
-namespace {
-int launch_ln_fwd(const void* x, bool xf32, const float* gamma, const float* beta, void* y, float* mean_rstd, int M, int D, float eps, e4t_stream stream) {
-  E4T_REQUIRE(x && gamma && beta && y && M > 0, "layernorm_fwd: null argument");
-  E4T_REQUIRE(D % 8 == 0 && D <= LN_MAXC * 64 * 8, "layernorm: D=%d must be a multiple of 8 and <= 1536", D);
-  const int ncl = cdiv(D / 8, 64);      // 16-byte chunks per lane: the kernels are instantiated per count (no dead loads)
-  // rows per wave: 4 / 2 / 2 for 1 / 2 / 3 chunks per lane; small M keeps one row per wave (enough blocks to fill the chip first)
-  const int rpw = ((long long)M * ncl < 256 * 4 * 8 || xf32) ? 1 : ncl == 1 ? 4 : 2;
-  E4T_LOG_LAUNCH("ln_fwd_kernel<%d, %d, %s>|M%d D%d|%.0f|0", ncl < 3 ? ncl : 3, rpw, xf32 ? "true" : "false", M, D, (xf32 ? 6.0 : 4.0) * (double)M * D);
-#define E4T_LN_FWD(NC_, R_, F_) hipLaunchKernelGGL((ln_fwd_kernel<NC_, R_, F_>), dim3(cdiv(M, 4 * R_)), dim3(256), 0, (hipStream_t)stream, x, gamma, beta, (bf16_t*)y, mean_rstd, M, D, eps)
-  if (xf32) { if (ncl == 1) E4T_LN_FWD(1, 1, true); else if (ncl == 2) E4T_LN_FWD(2, 1, true); else E4T_LN_FWD(3, 1, true); }
-  else if (rpw == 1) { if (ncl == 1) E4T_LN_FWD(1, 1, false); else if (ncl == 2) E4T_LN_FWD(2, 1, false); else E4T_LN_FWD(3, 1, false); }
-  else if (ncl == 1) E4T_LN_FWD(1, 4, false); else if (ncl == 2) E4T_LN_FWD(2, 2, false); else E4T_LN_FWD(3, 2, false);
-#undef E4T_LN_FWD
-  E4T_CHECK_LAUNCH("ln_fwd_kernel");
-  return 0;
-}
-}  // namespace
 
 extern "C" int e4t_layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean_rstd, int M, int D, float eps,
                                  e4t_stream stream) {
-  return launch_ln_fwd(x, false, gamma, beta, y, mean_rstd, M, D, eps, stream);
+  return launch_ln_fwd(x, false, gamma, beta, (bf16_t*)y, mean_rstd, M, D, eps, (hipStream_t)stream);
 }
 
 extern "C" int e4t_layernorm_fwd_f32(const float* x, const float* gamma, const float* beta, void* y, float* mean_rstd, int M, int D, float eps,
                                      e4t_stream stream) {
   E4T_REQUIRE(((uintptr_t)x & 15) == 0, "layernorm_fwd_f32: x must be 16-byte aligned");
-  return launch_ln_fwd(x, true, gamma, beta, y, mean_rstd, M, D, eps, stream);
+  return launch_ln_fwd(x, true, gamma, beta, (bf16_t*)y, mean_rstd, M, D, eps, (hipStream_t)stream);
 }
 
 extern "C" int e4t_layernorm_bwd(const void* x, const void* dy, const float* gamma, const float* mean_rstd, const void* add, void* dx,
                                  int M, int D, e4t_stream stream) {
-  E4T_REQUIRE(x && dy && gamma && mean_rstd && dx && M > 0, "layernorm_bwd: null argument");
-  E4T_REQUIRE(D % 8 == 0 && D <= LN_MAXC * 64 * 8, "layernorm: D=%d must be a multiple of 8 and <= 1536", D);
+  if (int e = ln_check(x && dy && gamma && mean_rstd && dx && M > 0, "layernorm_bwd", D)) return e;
   const int ncl = cdiv(D / 8, 64);
-  E4T_LOG_LAUNCH("ln_bwd_kernel<%d>|M%d D%d add%d|%.0f|0", ncl < 3 ? ncl : 3, M, D, add != nullptr, 2.0 * (double)M * D * (add ? 4 : 3));
-#define E4T_LN_BWD(NC_) hipLaunchKernelGGL((ln_bwd_kernel<NC_>), dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, gamma, mean_rstd, (const bf16_t*)add, (bf16_t*)dx, M, D)
-  if (ncl == 1) E4T_LN_BWD(1); else if (ncl == 2) E4T_LN_BWD(2); else E4T_LN_BWD(3);
-#undef E4T_LN_BWD
-  E4T_CHECK_LAUNCH("ln_bwd_kernel");
-  return 0;
+  E4T_LOG_LAUNCH("ln_bwd_kernel<%d>|M%d D%d add%d|%.0f|0", ncl, M, D, add != nullptr, 2.0 * (double)M * D * (add ? 4 : 3));
+  return pick<1, 2, 3>("ln_bwd_kernel", ncl, [&](auto NC) {
+    hipLaunchKernelGGL((ln_bwd_kernel<NC.value>), dim3(cdiv(M, 4)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, (const bf16_t*)dy, gamma,
+                       mean_rstd, (const bf16_t*)add, (bf16_t*)dx, M, D);
+  });
 }
 
-// part_dgamma / part_dbeta: [nblk][D] fp32 with nblk = e4t_layernorm_param_grad_blocks(M); caller sums over dim 0.
 extern "C" int e4t_colreduce_splits(int M) { return colreduce_splits(M); }
 
 extern "C" int e4t_colsum(const void* x, int ldx, int M, int C, float* out, int accumulate, void* workspace, size_t ws_bytes,
@@ -1110,12 +1111,8 @@ extern "C" int e4t_colsum(const void* x, int ldx, int M, int C, float* out, int 
   const int ns = colreduce_splits(M);
   E4T_REQUIRE(workspace && ws_bytes >= (size_t)ns * C * sizeof(float), "colsum: workspace too small");
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(colreduce_kernel<0>, dim3(cdiv(C, 64), ns), dim3(256), 0, st, (const bf16_t*)x, ldx, (const bf16_t*)nullptr,
-                     (const float*)nullptr, M, C, cdiv(M, ns), (float*)workspace, (float*)nullptr);
-  E4T_CHECK_LAUNCH("colreduce_kernel");
-  hipLaunchKernelGGL(colreduce_final_kernel, dim3(cdiv(C, 256)), dim3(256), 0, st, (const float*)workspace, ns, C, out, accumulate);
-  E4T_CHECK_LAUNCH("colreduce_final_kernel");
-  return 0;
+  if (int e = launch_colreduce<0>((const bf16_t*)x, ldx, nullptr, nullptr, M, C, ns, (float*)workspace, nullptr, st)) return e;
+  return launch_colreduce_final((const float*)workspace, ns, C, out, accumulate, st);
 }
 
 extern "C" int e4t_layernorm_param_grad(const void* x, const void* dy, const float* mean_rstd, int M, int D, float* dgamma, float* dbeta,
@@ -1123,14 +1120,10 @@ extern "C" int e4t_layernorm_param_grad(const void* x, const void* dy, const flo
   E4T_REQUIRE(x && dy && mean_rstd && dgamma && dbeta && D % 8 == 0, "layernorm_param_grad: bad arguments");
   const int ns = colreduce_splits(M);
   E4T_REQUIRE(workspace && ws_bytes >= (size_t)2 * ns * D * sizeof(float), "layernorm_param_grad: workspace too small");
-  float* p0 = (float*)workspace;
+  float* p0 = (float*)workspace;      // [ns][D] dgamma partials, then as many of dbeta
   float* p1 = p0 + (size_t)ns * D;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(colreduce_kernel<1>, dim3(cdiv(D, 64), ns), dim3(256), 0, st, (const bf16_t*)x, D, (const bf16_t*)dy, mean_rstd, M, D,
-                     cdiv(M, ns), p0, p1);
-  E4T_CHECK_LAUNCH("colreduce_kernel");
-  hipLaunchKernelGGL(colreduce_final_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, (const float*)p0, ns, D, dgamma, accumulate);
-  hipLaunchKernelGGL(colreduce_final_kernel, dim3(cdiv(D, 256)), dim3(256), 0, st, (const float*)p1, ns, D, dbeta, accumulate);
-  E4T_CHECK_LAUNCH("colreduce_final_kernel");
-  return 0;
+  if (int e = launch_colreduce<1>((const bf16_t*)x, D, (const bf16_t*)dy, mean_rstd, M, D, ns, p0, p1, st)) return e;
+  if (int e = launch_colreduce_final(p0, ns, D, dgamma, accumulate, st)) return e;
+  return launch_colreduce_final(p1, ns, D, dbeta, accumulate, st);
 }
