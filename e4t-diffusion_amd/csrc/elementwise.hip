@@ -55,7 +55,11 @@ __global__ __launch_bounds__(256) void unary_kernel(const bf16_t* x, const bf16_
         case 4: f[k] = f[k] > 0.f ? f[k] : 0.01f * f[k]; break;
         case 5: f[k] = f[k] > 0.f ? d[k] : 0.01f * d[k]; break;
         case 6: f[k] = f[k] / (1.f + __expf(-1.702f * f[k])); break;
-        default: { const float sg = 1.f / (1.f + __expf(-1.702f * f[k])); f[k] = d[k] * sg * (1.f + 1.702f * f[k] * (1.f - sg)); } break;
+        default: {
+          // 1.702 x overflows for |x| > 2e38 where sg or 1 - sg is 0: inf * 0.  Clamped to a finite value the product is the 0 it stands for; below the clamp the bits are unchanged
+          const float sg = 1.f / (1.f + __expf(-1.702f * f[k])), ax = fminf(fmaxf(1.702f * f[k], -3.0e38f), 3.0e38f);
+          f[k] = d[k] * sg * (1.f + ax * (1.f - sg));
+        } break;
       }
     }
     *(uint4*)(y + i * 8) = pack8(f);
@@ -660,6 +664,7 @@ extern "C" int e4t_sampler_step_guided(const float* pred, const float* x, float*
 }
 extern "C" int e4t_transpose(const void* in, void* out, int batch, int R, int C, int ldi, int ldo, long long bsi, long long bso, e4t_stream s) {
   E4T_REQUIRE(in && out && batch > 0 && R > 0 && C > 0 && ldi >= C && ldo >= R, "transpose: bad arguments");
+  E4T_REQUIRE(batch <= 65535 && cdiv(R, 64) <= 65535, "transpose: batch = %d, R = %d (at most 65535 batches and 65535 row tiles of 64: grid.z, grid.y)", batch, R);
   hipLaunchKernelGGL(transpose_kernel, dim3(cdiv(C, 64), cdiv(R, 64), batch), dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, R, C, ldi, ldo, bsi, bso);
   E4T_CHECK_LAUNCH("transpose_kernel");
   return 0;
@@ -672,19 +677,25 @@ extern "C" int e4t_conv_weight_prepare(const float* w_oihw, void* w_fwd, void* w
   return 0;
 }
 extern "C" int e4t_sumpool2(const void* in, void* out, int Bn, int H, int W, int C, e4t_stream s) {
-  E4T_REQUIRE(in && out && Bn > 0 && H > 0 && W > 0 && C % 8 == 0, "sumpool2: bad arguments");
+  E4T_REQUIRE(in && out && Bn > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "sumpool2: bad arguments (C > 0, C %% 8 == 0)");
   hipLaunchKernelGGL(sumpool2_kernel, dim3(grid_for((long long)Bn * H * W * (C / 8))), dim3(256), 0, (hipStream_t)s, (const bf16_t*)in, (bf16_t*)out, Bn, H, W, C);
   E4T_CHECK_LAUNCH("sumpool2_kernel");
   return 0;
 }
 extern "C" int e4t_spatial_mean(const void* x, float* out, int Bn, int HW, int C, int ldo, int coff, e4t_stream s) {
   E4T_REQUIRE(x && out && Bn > 0 && HW > 0 && C > 0 && C % 4 == 0, "spatial_mean: bad arguments (C %% 4 == 0)");
+  E4T_REQUIRE(coff >= 0 && (long long)ldo >= (long long)coff + C, "spatial_mean: coff = %d, ldo = %d (coff >= 0 and ldo >= coff + C = %lld: the slice lies inside a row of out)",
+              coff, ldo, (long long)coff + C);
+  E4T_REQUIRE(Bn <= 65535, "spatial_mean: B = %d (at most 65535 images: grid.y)", Bn);
   hipLaunchKernelGGL(spatial_mean_kernel, dim3(cdiv(C, 64), Bn), dim3(1024), 0, (hipStream_t)s, (const bf16_t*)x, out, HW, C, ldo, coff);
   E4T_CHECK_LAUNCH("spatial_mean_kernel");
   return 0;
 }
 extern "C" int e4t_spatial_mean_bwd(const float* g, const void* base, void* dx, int Bn, int HW, int C, int ldg, int coff, e4t_stream s) {
-  E4T_REQUIRE(g && dx && Bn > 0 && HW > 0 && C % 8 == 0, "spatial_mean_bwd: bad arguments");
+  E4T_REQUIRE(g && dx && Bn > 0 && HW > 0 && C > 0 && C % 8 == 0, "spatial_mean_bwd: bad arguments (C > 0, C %% 8 == 0)");
+  E4T_REQUIRE(coff >= 0 && (long long)ldg >= (long long)coff + C, "spatial_mean_bwd: coff = %d, ldg = %d (coff >= 0 and ldg >= coff + C = %lld: the slice lies inside a row of g)",
+              coff, ldg, (long long)coff + C);
+  E4T_REQUIRE(Bn <= 65535, "spatial_mean_bwd: B = %d (at most 65535 images, as e4t_spatial_mean)", Bn);
   hipLaunchKernelGGL(spatial_mean_bwd_kernel, dim3(grid_for((long long)Bn * HW * (C / 8))), dim3(256), 0, (hipStream_t)s, g, (const bf16_t*)base, (bf16_t*)dx, Bn, HW, C, ldg, coff);
   E4T_CHECK_LAUNCH("spatial_mean_bwd_kernel");
   return 0;
@@ -696,7 +707,9 @@ extern "C" int e4t_timestep_embedding(const long long* t, void* out, int Bn, int
   return 0;
 }
 extern "C" int e4t_clip_preprocess(const float* pixels_nchw, void* patches, int Bn, int Hin, int Win, int S, int P, int Kpad, e4t_stream s) {
-  E4T_REQUIRE(pixels_nchw && patches && Bn > 0 && S % P == 0 && Kpad >= 3 * P * P, "clip_preprocess: bad arguments");
+  E4T_REQUIRE(pixels_nchw && patches && Bn > 0, "clip_preprocess: bad arguments");
+  E4T_REQUIRE(P > 0 && S > 0 && Hin > 0 && Win > 0, "clip_preprocess: P = %d, S = %d, Hin = %d, Win = %d must be positive", P, S, Hin, Win);      // before the modulo: P = 0 would trap on the host
+  E4T_REQUIRE(S % P == 0 && (long long)Kpad >= 3LL * P * P, "clip_preprocess: bad arguments (S %% P == 0, Kpad >= 3 * P * P)");
   hipLaunchKernelGGL(clip_preprocess_kernel, dim3(grid_for((long long)Bn * 3 * S * S)), dim3(256), 0, (hipStream_t)s, pixels_nchw, (bf16_t*)patches, Bn, Hin, Win, S, P, Kpad);
   E4T_CHECK_LAUNCH("clip_preprocess_kernel");
   return 0;
@@ -979,7 +992,7 @@ extern "C" int e4t_im2col(const void* x, void* out, int Bn, int Hin, int Win, in
 
 extern "C" int e4t_im2col_T(const void* x, void* out, int Bn, int Hin, int Win, int C, int Hout, int Wout, int ldo, int mode, e4t_stream s) {
   E4T_REQUIRE(x && out && Bn > 0 && Hin > 0 && Win > 0 && Hout > 0 && Wout > 0, "im2col_T: bad arguments");
-  E4T_REQUIRE(C % 4 == 0 && ldo % 4 == 0 && (long long)ldo >= (long long)Bn * Hout * Wout, "im2col_T: C, ldo must be multiples of 4, ldo >= B*Hout*Wout");
+  E4T_REQUIRE(C > 0 && C % 4 == 0 && ldo % 4 == 0 && (long long)ldo >= (long long)Bn * Hout * Wout, "im2col_T: C, ldo must be multiples of 4, C > 0, ldo >= B*Hout*Wout");
   E4T_REQUIRE(mode == E4T_CONV_S1 || mode == E4T_CONV_S2 || mode == E4T_CONV_UP2, "im2col_T: mode must be S1, S2 or UP2");
   const long long Mpix = (long long)Bn * Hout * Wout;
   hipLaunchKernelGGL(im2col_T_kernel, dim3(cdiv(C, 64), (unsigned)((ldo + 63) / 64), 9), dim3(256), 0, (hipStream_t)s, (const bf16_t*)x, (bf16_t*)out,

@@ -319,11 +319,18 @@ int e4t_geglu_bwd(const void* u, const void* dh, void* du, long long M, int H, e
 #define E4T_OP_QGELU_BWD 7
 int e4t_unary(const void* x, const void* dy, void* y, long long n, int op, e4t_stream stream);
 int e4t_add(const void* a, const void* b, void* y, long long n, e4t_stream stream);
+/* in[b][R][C] (row stride ldi >= C, batch stride bsi) -> out[b][C][R] (row stride ldo >= R, batch stride bso); columns [R, ldo) of out are left alone.
+ * batch <= 65535 and R <= 65535 * 64 (grid.z, grid.y). */
 int e4t_transpose(const void* in, void* out, int batch, int R, int C, int ldi, int ldo, long long bsi, long long bso, e4t_stream stream);
+/* C > 0, C % 8 == 0 */
 int e4t_sumpool2(const void* in /* [B][2H][2W][C] */, void* out /* [B][H][W][C] */, int B, int H, int W, int C, e4t_stream stream);
+/* out[b][coff + c] = mean over the HW pixels of x[b][.][c]; only columns [coff, coff + C) of each row of out (row stride ldo) are written.
+ * C % 4 == 0, coff >= 0, ldo >= coff + C, B <= 65535 (grid.y).  The backward reads the same slice of g (row stride ldg): C % 8 == 0, coff >= 0,
+ * ldg >= coff + C, B <= 65535. */
 int e4t_spatial_mean(const void* x, float* out, int B, int HW, int C, int ldo, int coff, e4t_stream stream);            /* encoder.py:147 */
 int e4t_spatial_mean_bwd(const float* g, const void* base, void* dx, int B, int HW, int C, int ldg, int coff, e4t_stream stream);
 int e4t_timestep_embedding(const long long* t, void* out /* bf16 [B][dim] = [cos|sin] */, int B, int dim, e4t_stream stream); /* unet_2d_condition.py:461 */
+/* B, Hin, Win, S, P > 0, S % P == 0, Kpad >= 3 * P * P.  Columns [3 * P * P, Kpad) of patches are NOT written: the caller zeroes them (ops.clip_preprocess). */
 int e4t_clip_preprocess(const float* pixels_nchw, void* patches /* bf16 [B*g*g][Kpad] */, int B, int Hin, int Win, int S, int P, int Kpad, e4t_stream stream); /* encoder.py:131-139 + patchify */
 /* Sampling loop glue (pipeline_stable_diffusion_e4t.py:209-214): classifier-free guidance eps = u + g*(c-u) over
  * pred = [uncond | cond] (cfg = 1; cfg = 0: pred is eps) fused with a linear scheduler update
@@ -454,6 +461,7 @@ int e4t_softmax_rows(void* x, long long rows, int L, int ld, e4t_stream stream);
 /* 3x3/pad-1 im2col of a 3-channel NCHW fp32 image -> bf16 [B*H*W][32], column (ky*3+kx)*3+c, columns 27..31 zero */
 int e4t_im2col3_rgb(const float* pixels_nchw, void* out, int B, int H, int W, e4t_stream stream);
 /* out[(tap*C + c)][m] = gathered X (3x3 taps, zero outside), m over OUTPUT pixels: B operand of the conv weight-gradient GEMM */
+/* C > 0, C % 4 == 0, ldo % 4 == 0, ldo >= B * Hout * Wout; columns [B * Hout * Wout, ldo) of out are written as zeros */
 int e4t_im2col_T(const void* x, void* out, int B, int Hin, int Win, int C, int Hout, int Wout, int ldo, int mode, e4t_stream stream);
 /* out[m][tap*C + c] (bf16 [B*Hout*Wout][9*C]): with e4t_gemm_tn, dW[co][tap][ci] = dY^T . im2col(X) needs no transposes. */
 int e4t_im2col(const void* x, void* out, int B, int Hin, int Win, int C, int Hout, int Wout, int mode, e4t_stream stream);

@@ -8,7 +8,8 @@ bf16 inputs is bounded by ~eps/sqrt(3) per output rounding (~2.3e-3) plus accumu
 we allow 6e-3 for single-rounding kernels, 1.5e-2 where an intermediate (P, dS) is also rounded to
 bf16 inside the kernel, 1e-5 for fp32-only kernels.
 
-Importable without a GPU: the attention, conv, norm, GEMM and weight-offset case lists, slices(), conv_slices(), norm_slices(), gemm_slices() and
+Importable without a GPU: the attention, conv, norm, GEMM, weight-offset and streaming case lists (stream_value_cases, stream_layout_cases),
+the stream_ref64_* definitions, stream_slices() (tests/test_streaming_slices_cpu.py), slices(), conv_slices(), norm_slices(), gemm_slices() and
 wo_slices(), norm_plan() and the fp64 norm, GEMM and weight-offset references are shared with CPU tests (test_gemm_dispatch.py,
 test_attention_slices_cpu.py, test_conv_slices_cpu.py, test_norm_slices_cpu.py, test_norm_plan_cpu.py, test_gemm_slices_cpu.py, test_wo_slices_cpu.py).
 """
@@ -2837,6 +2838,700 @@ def check_gemm_guards(hip, emu, dev):
     return out + _gemm_rejection_rows(hip, dev)
 
 
+# ---- streaming_values / streaming_layout / streaming_guards: elementwise.hip against fp64 definitions, per slice --------------------
+# A value row is  max |got - ref| / (rel * |ref| + floor * scale + STREAM_TINY)  over a region, and passes at <= 1.  rel is one bf16 rounding
+# (2^-8, the format's) for a bf16 output and 0 for an fp32 one; `scale` is what the op's fp32 arithmetic error is proportional to (|x| / 2 for a
+# GELU value, |dy| for a derivative, sum |terms| for a sum, ...) and `floor` the class's bound on that error in units of the scale: twice the
+# worst the fp32 model of tests/test_streaming_slices_cpu.py shows before its output rounding, rounded up (measured there, printed there).
+# STREAM_TINY = 2^-126: fp32 arithmetic on the fast paths (v_exp_f32, v_rcp_f32) takes subnormals as zero.  Permutation rows count unequal elements.
+STREAM_REL, STREAM_TINY = 2.0 ** -8, 2.0 ** -126
+BF16_MAX = (2.0 - 2.0 ** -7) * 2.0 ** 127
+STREAM_TOL = {      # class -> (rel, floor)
+    "gelu": (STREAM_REL, 1.0e-6),        # of |x| / 2 (times |a| or |dh|): erf by Abramowitz & Stegun 7.1.26, 1.5e-7 absolute, and five roundings
+    "dgelu": (STREAM_REL, 5.0e-7),       # of |dy| (|dh a|)
+    "sigmoid": (STREAM_REL, 2.2e-7),     # x * sigmoid(x), x * sigmoid(1.702 x) and their derivatives
+    "round": (STREAM_REL, 1.5e-7),       # one fp32 operation, one rounding: leaky ReLU, add
+    "sum": (STREAM_REL, 2.0e-7),         # sumpool2, spatial_mean_bwd: against the sum of the absolute terms
+    "softmax": (STREAM_REL, 6.6e-6),     # against p itself: exp(v - max) at v - max down to -87, the sum
+    "embed": (STREAM_REL, 1.3e-4),       # absolute, on [-1, 1]: the angle is fp32 at up to 1000 rad
+    "clip": (STREAM_REL, 4.8e-5),        # absolute, in units of 1 / std: fy = oy * sy in fp32 at up to 511
+    "mean32": (0.0, 7.6e-8),             # fp32 output, against the mean of |x|
+    "sumsq32": (0.0, 2.0e-7),            # fp32 output, against the sum itself
+}
+StreamCase = namedtuple("StreamCase", "op tag a")      # a: dict of CPU tensors and ints
+_STREAM_CACHE = {}
+CLIP_MEAN, CLIP_STD = (0.48145466, 0.4578275, 0.40821073), (0.26862954, 0.26130258, 0.27577711)
+
+
+def _cg(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _cr(g, *shape, scale=1.0, dtype=bf16):
+    return (torch.randn(*shape, generator=g, dtype=f32) * scale).to(dtype)
+
+
+def bf16_patterns():
+    """all 65536 bf16 bit patterns (one tensor, a multiple of 8)"""
+    return (torch.arange(65536, dtype=torch.int32) - 32768).to(torch.int16).view(bf16)
+
+
+def _Phi64(x):
+    return 0.5 * torch.special.erfc(-x / math.sqrt(2.0))
+
+
+def _phi64(x):
+    return torch.exp(-0.5 * x * x) / math.sqrt(2.0 * math.pi)
+
+
+def stream_ref64_unary(op, x, dy=None):
+    x = x.to(f64)
+    d = dy.to(f64) if dy is not None else None
+    k = 1.702 if op >= 6 else 1.0
+    if op in (0, 6):
+        return x * torch.sigmoid(k * x)
+    if op in (1, 7):
+        s, ns = torch.sigmoid(k * x), torch.sigmoid(-k * x)      # 1 - s without the cancellation
+        return d * s * (1.0 + k * x * ns)
+    if op == 2:
+        return x * _Phi64(x)
+    if op == 3:
+        return d * (_Phi64(x) + x * _phi64(x))
+    if op == 4:
+        return torch.where(x > 0, x, 0.01 * x)
+    return torch.where(x > 0, d, 0.01 * d)
+
+
+def stream_ref64_geglu(u, dh=None):
+    H = u.shape[1] // 2
+    a, g = u[:, :H].to(f64), u[:, H:].to(f64)
+    out = {"h": a * g * _Phi64(g)}
+    if dh is not None:
+        d = dh.to(f64)
+        out.update(da=d * g * _Phi64(g), dg=d * a * (_Phi64(g) + g * _phi64(g)))
+    return out
+
+
+def stream_ref64_softmax(x):
+    x = x.to(f64)
+    e = torch.exp(x - x.max(-1, keepdim=True).values)
+    return e / e.sum(-1, keepdim=True)
+
+
+def stream_ref64_timestep(t, dim):
+    half = dim // 2
+    ang = t.to(f64)[:, None] * torch.pow(torch.tensor(10000.0, dtype=f64), -torch.arange(half, dtype=f64) / half)[None, :]
+    return torch.cat([torch.cos(ang), torch.sin(ang)], 1)
+
+
+def _cubic64(d):
+    """the cubic convolution kernel, A = -0.75, at distance d >= 0"""
+    A = -0.75
+    return torch.where(d <= 1, ((A + 2) * d - (A + 3)) * d * d + 1, ((A * d - 5 * A) * d + 8 * A) * d - 4 * A)
+
+
+def stream_ref64_clip(px, S, P, Kpad):
+    """bicubic (A = -0.75, align corners, clamped indices) to S x S, (x + 1) / 2, CLIP mean / std, patches [B * g * g][Kpad], k = (c * P + py) * P + px"""
+    B, _, Hin, Win = px.shape
+    x = px.to(f64)
+
+    def taps(n_in):
+        f = torch.arange(S, dtype=f64) * ((n_in - 1) / (S - 1) if S > 1 else 0.0)
+        i0 = torch.floor(f)
+        t = f - i0
+        w = torch.stack([_cubic64(t + 1), _cubic64(t), _cubic64(1 - t), _cubic64(2 - t)], 1)
+        idx = (i0.long()[:, None] + torch.arange(-1, 3)[None, :]).clamp(0, n_in - 1)
+        return w, idx
+    wy, iy = taps(Hin)
+    wx, ix = taps(Win)
+    rows = (x[:, :, iy, :] * wy[None, None, :, :, None]).sum(3)                 # [B][3][S][Win]
+    img = (rows[:, :, :, ix] * wx[None, None, None, :, :]).sum(4)               # [B][3][S][S]
+    mean, std = torch.tensor(CLIP_MEAN, dtype=f64), torch.tensor(CLIP_STD, dtype=f64)
+    img = ((img + 1.0) * 0.5 - mean[None, :, None, None]) / std[None, :, None, None]
+    return clip_patchify(img, P, Kpad)
+
+
+def clip_patchify(img, P, Kpad):
+    """[B][3][S][S] -> [B * g * g][Kpad], k = (c * P + py) * P + px, zero pad columns"""
+    B, S = img.shape[0], img.shape[2]
+    g = S // P
+    pat = img.reshape(B, 3, g, P, g, P).permute(0, 2, 4, 1, 3, 5).reshape(B * g * g, 3 * P * P)
+    return torch.nn.functional.pad(pat, (0, Kpad - 3 * P * P))
+
+
+def stream_ref_conv_weight(w, Ipad, Opad):
+    """fwd[o][tap][i], dgrad[i][8 - tap][o], zero in the pads; one RNE rounding"""
+    O, I = w.shape[:2]
+    w9 = w.reshape(O, I, 9).to(bf16)
+    fwd = torch.zeros(O, 9, Ipad, dtype=bf16)
+    fwd[:, :, :I] = w9.permute(0, 2, 1)
+    dg = torch.zeros(I, 9, Opad, dtype=bf16)
+    dg[:, :, :O] = w9.flip(2).permute(1, 2, 0)
+    return fwd.reshape(O, 9 * Ipad), dg.reshape(I, 9 * Opad)
+
+
+def _conv_src(Hin, Win, Hout, Wout, mode):
+    """per output pixel and tap: source row, column and validity, written out plainly"""
+    oy, ox = torch.arange(Hout)[:, None, None, None], torch.arange(Wout)[None, :, None, None]
+    ky, kx = torch.arange(3)[None, None, :, None], torch.arange(3)[None, None, None, :]
+    if mode == CONV_S1:
+        iy, ix = oy + ky - 1 + 0 * ox + 0 * kx, ox + kx - 1 + 0 * oy + 0 * ky
+        ok = (iy >= 0) & (iy < Hin) & (ix >= 0) & (ix < Win)
+    elif mode == CONV_S2:
+        iy, ix = 2 * oy + ky - 1 + 0 * ox + 0 * kx, 2 * ox + kx - 1 + 0 * oy + 0 * ky
+        ok = (iy >= 0) & (iy < Hin) & (ix >= 0) & (ix < Win)
+    else:      # UP2: the 3x3 window on the nearest-neighbour upsampled image
+        uy, ux = oy + ky - 1 + 0 * ox + 0 * kx, ox + kx - 1 + 0 * oy + 0 * ky
+        ok = (uy >= 0) & (uy < 2 * Hin) & (ux >= 0) & (ux < 2 * Win)
+        iy, ix = torch.div(uy, 2, rounding_mode="floor"), torch.div(ux, 2, rounding_mode="floor")
+    return iy.clamp(0, Hin - 1), ix.clamp(0, Win - 1), ok      # [Hout][Wout][3][3]
+
+
+def stream_ref_im2col(x, B, Hin, Win, Hout, Wout, mode):
+    """out[(b, oy, ox)][tap * C + c] = x[b][iy][ix][c], zero outside"""
+    C = x.shape[1]
+    iy, ix, ok = _conv_src(Hin, Win, Hout, Wout, mode)
+    v = x.reshape(B, Hin, Win, C)[:, iy, ix, :]                                         # [B][Hout][Wout][3][3][C]
+    v = torch.where(ok[None, ..., None], v, torch.zeros_like(v))
+    return v.reshape(B * Hout * Wout, 9 * C)
+
+
+def stream_ref_im2col_T(x, B, Hin, Win, Hout, Wout, mode, ld):
+    m = stream_ref_im2col(x, B, Hin, Win, Hout, Wout, mode)
+    return torch.nn.functional.pad(m.t(), (0, ld - m.shape[0])).contiguous()
+
+
+def stream_ref_im2col3(px):
+    """out[(b, y, x)][(ky * 3 + kx) * 3 + c] = px[b][c][y + ky - 1][x + kx - 1], zero outside, columns 27..31 zero; one RNE rounding"""
+    B, _, H, W = px.shape
+    iy, ix, ok = _conv_src(H, W, H, W, CONV_S1)
+    v = px.to(bf16).permute(0, 2, 3, 1)[:, iy, ix, :]
+    v = torch.where(ok[None, ..., None], v, torch.zeros_like(v))
+    return torch.nn.functional.pad(v.reshape(B * H * W, 27), (0, 5))
+
+
+def _padb(m, pads):
+    return torch.nn.functional.pad(m.to(torch.uint8), pads).bool()
+
+
+def _ring(H, W):
+    m = torch.zeros(H, W, dtype=torch.bool)
+    m[0], m[-1], m[:, 0], m[:, -1] = True, True, True, True
+    return m
+
+
+def _default_regions(shape):
+    if len(shape) != 2:
+        return []
+    R, C = shape
+    reg = []
+    if R > 1:
+        reg += [("first row", (slice(0, 1), slice(None))), ("last row", (slice(R - 1, R), slice(None)))]
+    if C > 8:
+        reg += [("first 8 columns", (slice(None), slice(0, 8))), ("last 8 columns", (slice(None), slice(C - 8, C)))]
+    return reg
+
+
+def stream_slices(tag, got, ref, cls, scale=None, regions=None):
+    """(label, error, tolerance) for the whole output and per region.  cls "exact": the number of unequal elements against 0; else the elementwise
+    measure of STREAM_TOL[cls] against 1.  regions: [(label, index)] with index a boolean mask or a tuple of slices; default first / last row and
+    8-wide column chunk.  A non-finite output where the reference is finite is an infinite error."""
+    if got is None or tuple(got.shape) != tuple(ref.shape):
+        return [(f"{tag}: output missing or shaped {None if got is None else tuple(got.shape)}, not {tuple(ref.shape)}", float("inf"), 0.0)]
+    if cls == "exact":
+        r = (got != ref.to(got.dtype)).to(f64)
+        tol = 0.0
+    else:
+        rel_, floor = STREAM_TOL[cls]
+        g, rf = got.to(f64), ref.to(f64)
+        den = rel_ * rf.abs() + STREAM_TINY + (floor * scale.to(f64) if scale is not None else 0.0)
+        r = (g - rf).abs() / den
+        # equal, both NaN, or an infinity where the reference lies beyond the largest bf16: no error; any other non-finite value: an infinite one
+        same = (g == rf) | (torch.isnan(g) & torch.isnan(rf)) | (torch.isinf(g) & (rf.abs() >= BF16_MAX) & (torch.sign(g) == torch.sign(rf)) & (got.dtype == bf16))
+        r = torch.where(same, torch.zeros_like(r), torch.where(torch.isfinite(g) & torch.isfinite(rf), r, torch.full_like(r, float("inf"))))
+        tol = 1.0
+    red = (lambda t: float(t.sum())) if cls == "exact" else (lambda t: float(t.max()) if t.numel() else 0.0)
+    rows = [(f"{tag}: whole {tuple(ref.shape)}", red(r), tol)]
+    for label, idx in (_default_regions(ref.shape) if regions is None else regions):
+        rows.append((f"{tag}: {label}", red(r[idx]), tol))
+    return rows
+
+
+def stream_excess(pre, ref, scale):
+    """the fp32 arithmetic error of an unrounded output in units of its scale: what a class's floor bounds"""
+    p, rf, s = pre.to(f64), ref.to(f64), scale.to(f64)
+    ok = torch.isfinite(p) & torch.isfinite(rf) & (s > 0)
+    d = torch.where(ok, ((p - rf).abs() - STREAM_TINY).clamp(min=0.0) / torch.where(ok, s, torch.ones_like(s)), torch.zeros_like(rf))      # (a subnormal fp32 result has no relative precision: STREAM_TINY is its bound)
+    return float(d.max()) if d.numel() else 0.0
+
+
+# ---- the cases: inputs drawn on the CPU, once -------------------------------------------------------------------------------------------
+SOFTMAX_ROWS = {8: ("seeded", "peaked", "some -inf"), 64: ("seeded", "constant", "offset 3e4"), 2056: ("seeded", "peaked", "some -inf"),
+                16384: ("seeded", "constant", "offset 3e4")}
+TIMESTEPS, TIMESTEP_DIMS = (0, 1, 17, 500, 999, 1000), (2, 6, 320, 322, 1280)
+SUMSQ_N, SUMSQ_BLOCKS = (1, 255, 257, 100003), (1, 1024)
+GEGLU_SHAPES = [(1, 8), (3, 72), (300, 640)]
+TRANSPOSE_CASES = [(1, 1, 0), (3, 65, 1), (63, 64, 0), (64, 63, 1), (65, 130, 0), (130, 72, 0)]      # R, C, ldi - C
+CONV_WEIGHT_CASES = [(4, 320, None, None), (320, 4, None, None), (72, 200, 256, 128), (8, 8, 8, 8)]      # O, I, Ipad, Opad
+SUMPOOL_CASES = [(3, 1, 1, 8), (2, 5, 3, 72), (1, 8, 8, 64)]
+IM2COL_GEOM = [(CONV_S1, 2, 6, 10, 6, 10), (CONV_S2, 2, 7, 9, 4, 5), (CONV_UP2, 1, 3, 5, 6, 10),
+               (CONV_S1, 2, 12, 12, 12, 12), (CONV_S2, 3, 9, 9, 5, 5), (CONV_UP2, 2, 6, 6, 12, 12)]      # mode, B, Hin, Win, Hout, Wout; the last three: check_streaming's
+IM2COL3_CASES = [(1, 1, 1), (2, 5, 3)]
+SPATIAL_MEAN_CASES = [(1, 1, 4, 4, 0, 0.0), (2, 63, 68, 68, 0, 0.0), (3, 65, 132, 200, 60, 0.0), (2, 4096, 320, 320, 0, 0.0), (2, 63, 68, 68, 0, 100.0)]      # B, HW, C, ldo, coff, mean
+SPATIAL_BWD_CASES = [(2, 5, 8, 8, 0, False), (2, 5, 8, 8, 0, True), (2, 5, 8, 24, 8, True), (3, 7, 16, 40, 16, False)]      # B, HW, C, ldg, coff, base
+CLIP_CASES = [("identity 28->28", 1, 28, 28, 28, 14, 588, "rand"), ("enlarging 20x20->28", 2, 20, 20, 28, 14, 640, "rand"), ("48x80->28", 1, 48, 80, 28, 14, 640, "rand"),
+              ("64->28 S == P", 1, 64, 64, 28, 28, 3 * 28 * 28, "rand"), ("512->224", 1, 512, 512, 224, 14, 640, "rand"),
+              ("constant 48x80->28", 1, 48, 80, 28, 14, 588, "constant"), ("ramp 48x80->28", 1, 48, 80, 28, 14, 640, "ramp")]
+
+
+def softmax_rows_input(L, kinds, g):
+    x = _cr(g, len(kinds), L, scale=2.0).float()
+    for r, kind in enumerate(kinds):
+        if kind == "peaked":
+            x[r, (7 * L) // 11] += 40.0
+        elif kind == "constant":
+            x[r] = 1.25
+        elif kind == "offset 3e4":
+            x[r] += 3.0e4
+        elif kind == "some -inf":
+            x[r, ::3] = float("-inf")
+    return x.to(bf16)
+
+
+def stream_value_cases():
+    if "values" in _STREAM_CACHE:
+        return _STREAM_CACHE["values"]
+    cases, g = [], _cg(3100)
+    pat = bf16_patterns()
+    fin = pat[torch.isfinite(pat.float())]      # 65280 = 8160 * 8
+    for op in range(8):
+        cases.append(StreamCase("unary", f"unary op{op}, every bf16 pattern" + (", dy = 1" if op & 1 else ""), dict(op=op, x=pat, dy=torch.ones_like(pat) if op & 1 else None)))
+        if op & 1:
+            cases.append(StreamCase("unary", f"unary op{op}, every bf16 pattern, seeded dy", dict(op=op, x=pat, dy=_cr(g, pat.numel()))))
+    u = torch.cat([_cr(g, fin.numel() // 8, 8), fin.reshape(-1, 8)], 1)
+    cases.append(StreamCase("geglu", "geglu gate = every finite bf16 pattern, H8", dict(u=u, dh=_cr(g, fin.numel() // 8, 8))))
+    for M, H in GEGLU_SHAPES:
+        cases.append(StreamCase("geglu", f"geglu {M}x{H}", dict(u=_cr(g, M, 2 * H, scale=2.0), dh=_cr(g, M, H))))
+    a = _cr(g, 37, 72)
+    cases.append(StreamCase("add", "add seeded", dict(a=a, b=_cr(g, 37, 72))))
+    cases.append(StreamCase("add", "add a = -b", dict(a=a, b=-a)))
+    cases.append(StreamCase("add", "add magnitudes 2^16 apart", dict(a=a, b=(_cr(g, 37, 72).float() * 2.0 ** -16).to(bf16))))
+    for L, kinds in SOFTMAX_ROWS.items():
+        cases.append(StreamCase("softmax", f"softmax_rows L{L}", dict(x=softmax_rows_input(L, kinds, g), kinds=kinds)))
+    for dim in TIMESTEP_DIMS:
+        cases.append(StreamCase("timestep", f"timestep_embedding dim{dim}", dict(t=torch.tensor(TIMESTEPS), dim=dim)))
+    for n in SUMSQ_N:
+        cases.append(StreamCase("sumsq", f"sumsq n{n}", dict(g=_cr(g, n, dtype=f32))))
+    _STREAM_CACHE["values"] = cases
+    return cases
+
+
+def clip_input(kind, B, Hin, Win, g):
+    if kind == "constant":
+        return torch.full((B, 3, Hin, Win), 0.3125)
+    if kind == "ramp":      # linear in y and x, another slope per channel: cubic convolution reproduces degree 1 away from the clamped border
+        y, x = torch.arange(Hin, dtype=f32)[:, None] / Hin, torch.arange(Win, dtype=f32)[None, :] / Win
+        return torch.stack([0.9 * y - 0.7 * x, x - 0.5 * y - 0.2, 0.3 * y + 0.4 * x - 0.6], 0)[None].repeat(B, 1, 1, 1).contiguous()
+    return torch.rand(B, 3, Hin, Win, generator=g) * 2 - 1
+
+
+def stream_layout_cases():
+    if "layout" in _STREAM_CACHE:
+        return _STREAM_CACHE["layout"]
+    cases, g = [], _cg(3200)
+    for R, C, pad in TRANSPOSE_CASES:
+        cases.append(StreamCase("transpose", f"transpose {R}x{C}" + (f" ldi {C + pad}" if pad else ""), dict(x=_cr(g, R, C + pad)[:, :C])))
+    for O, I, Ipad, Opad in CONV_WEIGHT_CASES:
+        w = _cr(g, O, I, 3, 3, scale=0.05, dtype=f32)
+        for form, (wf, wd) in (("fwd only", (True, False)), ("dgrad only", (False, True)), ("both", (True, True))):
+            cases.append(StreamCase("conv_weight", f"conv_weight_prepare {I}->{O} pads {Ipad}/{Opad} {form}", dict(w=w, Ipad=Ipad, Opad=Opad, fwd=wf, dgrad=wd)))
+    for B, H, W, C in SUMPOOL_CASES:
+        cases.append(StreamCase("sumpool2", f"sumpool2 B{B} {H}x{W} C{C}", dict(x=_cr(g, B * 2 * H * 2 * W, C), B=B, H=H, W=W)))
+    for i, (mode, B, Hin, Win, Hout, Wout) in enumerate(IM2COL_GEOM):
+        for C in ((8, 72, 4) if i < 3 else (72,)):
+            geo = dict(x=_cr(g, B * Hin * Win, C), B=B, Hin=Hin, Win=Win, Hout=Hout, Wout=Wout, mode=mode)
+            tag = f"mode{mode} B{B} {Hin}x{Win}->{Hout}x{Wout} C{C}"
+            if C % 8 == 0:
+                cases.append(StreamCase("im2col", "im2col " + tag, geo))
+            cases.append(StreamCase("im2col_T", "im2col_T " + tag, geo))
+    for B, H, W in IM2COL3_CASES:
+        cases.append(StreamCase("im2col3", f"im2col3_rgb B{B} {H}x{W}", dict(px=torch.rand(B, 3, H, W, generator=g) * 2 - 1)))
+    for B, HW, C, ldo, coff, mean in SPATIAL_MEAN_CASES:
+        cases.append(StreamCase("spatial_mean", f"spatial_mean B{B} HW{HW} C{C} ldo{ldo} coff{coff}" + (f" mean {mean:g}" if mean else ""),
+                                dict(x=(torch.randn(B * HW, C, generator=g) + mean).to(bf16), B=B, HW=HW, ldo=ldo, coff=coff)))
+    for B, HW, C, ldg, coff, base in SPATIAL_BWD_CASES:
+        cases.append(StreamCase("spatial_mean_bwd", f"spatial_mean_bwd B{B} HW{HW} C{C} ldg{ldg} coff{coff}" + (" + base" if base else ""),
+                                dict(g=_cr(g, B, ldg, dtype=f32), base=_cr(g, B * HW, C) if base else None, B=B, HW=HW, C=C, coff=coff)))
+    for name, B, Hin, Win, S, P, Kpad, kind in CLIP_CASES:
+        cases.append(StreamCase("clip", f"clip_preprocess {name} P{P} Kpad{Kpad}", dict(px=clip_input(kind, B, Hin, Win, g), S=S, P=P, Kpad=Kpad, kind=kind)))
+    _STREAM_CACHE["layout"] = cases
+    return cases
+
+
+def _pixel_regions(mask_hw, expand):
+    """border ring / interior of the output pixels; expand: [H][W] mask -> mask of the output's shape"""
+    reg = [("border ring", expand(mask_hw))]
+    if bool((~mask_hw).any()):
+        reg.append(("interior", expand(~mask_hw)))
+    return reg
+
+
+def stream_ref64(case):
+    """{output name: (class, fp64 reference or the exact expected tensor, scale or None, regions or None)} of a case, from the definition"""
+    if case.tag in _STREAM_CACHE:
+        return _STREAM_CACHE[case.tag]
+    a, op = case.a, case.op
+    if op == "unary":
+        x, dy, o = a["x"], a["dy"], a["op"]
+        fin = torch.isfinite(x.float())
+        ref = stream_ref64_unary(o, x, dy)
+        xa, da = x.to(f64).abs(), (dy.to(f64).abs() if dy is not None else None)
+        if dy is not None:
+            dx = da * (1.0 + xa)      # s * (1 + x * (1 - s)): the rounding of 1 - s is multiplied by x
+        cls, scale = {0: ("sigmoid", xa), 1: ("sigmoid", dx if o == 1 else None), 2: ("gelu", xa / 2), 3: ("dgelu", da), 4: ("round", ref.abs()), 5: ("round", ref.abs()),
+                      6: ("sigmoid", xa), 7: ("sigmoid", dx if o == 7 else None)}[o]
+        xf = x.float()[fin]      # the rows are over the finite patterns; stream_rows() looks at the others
+        out = {"y": (cls, ref[fin], scale[fin], [("x < -4", xf < -4), ("x > 4", xf > 4), ("|x| <= 4", xf.abs() <= 4), ("|x| < 2^-100", xf.abs() < 2.0 ** -100)])}
+    elif op == "geglu":
+        H = a["u"].shape[1] // 2
+        r = stream_ref64_geglu(a["u"], a["dh"])
+        A, G, D = a["u"][:, :H].to(f64).abs(), a["u"][:, H:].to(f64).abs(), a["dh"].to(f64).abs()
+        out = {"h": ("gelu", r["h"], A * G / 2, None), "da": ("gelu", r["da"], D * G / 2, None), "dg": ("dgelu", r["dg"], D * A, None)}
+    elif op == "add":
+        s = a["a"].to(f64) + a["b"].to(f64)
+        out = {"y": ("round", s, s.abs(), None)}
+    elif op == "softmax":
+        p = stream_ref64_softmax(a["x"])
+        out = {"p": ("softmax", p, p, [(f"row {r} ({k})", (slice(r, r + 1), slice(None))) for r, k in enumerate(a["kinds"])])}
+    elif op == "timestep":
+        e, half = stream_ref64_timestep(a["t"], a["dim"]), a["dim"] // 2
+        reg = [("cos half", (slice(None), slice(0, half))), ("sin half", (slice(None), slice(half, None)))]
+        reg += [(f"t = {int(t)}", (slice(b, b + 1), slice(None))) for b, t in enumerate(a["t"])]
+        out = {"emb": ("embed", e, torch.ones_like(e), reg)}
+    elif op == "sumsq":
+        s = (a["g"].to(f64) ** 2).sum().reshape(1)
+        out = {"sum": ("sumsq32", s, s, [])}
+    elif op == "transpose":
+        out = {"y": ("exact", a["x"].t().contiguous(), None, None)}
+    elif op == "conv_weight":
+        O, I = a["w"].shape[:2]
+        f, d = stream_ref_conv_weight(a["w"], a["Ipad"] or (I + 63) // 64 * 64, a["Opad"] or (O + 63) // 64 * 64)
+        out = {}
+        if a["fwd"]:
+            out["fwd"] = ("exact", f, None, None)
+        if a["dgrad"]:
+            out["dgrad"] = ("exact", d, None, None)
+    elif op == "sumpool2":
+        B, H, W, C = a["B"], a["H"], a["W"], a["x"].shape[1]
+        x = a["x"].to(f64).reshape(B, H, 2, W, 2, C)
+        ex = lambda m: m[None, :, :, None].expand(B, H, W, C).reshape(B * H * W, C)
+        out = {"y": ("sum", x.sum((2, 4)).reshape(B * H * W, C), x.abs().sum((2, 4)).reshape(B * H * W, C), _pixel_regions(_ring(H, W), ex))}
+    elif op in ("im2col", "im2col_T"):
+        B, Ho, Wo, C = a["B"], a["Hout"], a["Wout"], a["x"].shape[1]
+        ring = _ring(Ho, Wo)
+        if op == "im2col":
+            ref = stream_ref_im2col(a["x"], B, a["Hin"], a["Win"], Ho, Wo, a["mode"])
+            ex = lambda m: m[None, :, :, None].expand(B, Ho, Wo, 9 * C).reshape(B * Ho * Wo, 9 * C)
+        else:
+            ld = (B * Ho * Wo + 7) // 8 * 8
+            ref = stream_ref_im2col_T(a["x"], B, a["Hin"], a["Win"], Ho, Wo, a["mode"], ld)
+            ex = lambda m: _padb(m[None].expand(B, Ho, Wo).reshape(1, -1).expand(9 * C, -1), (0, ld - B * Ho * Wo))
+        out = {"y": ("exact", ref, None, _pixel_regions(ring, ex))}
+    elif op == "im2col3":
+        B, _, H, W = a["px"].shape
+        ex = lambda m: m[None, :, :, None].expand(B, H, W, 32).reshape(B * H * W, 32)
+        out = {"y": ("exact", stream_ref_im2col3(a["px"]), None, _pixel_regions(_ring(H, W), ex))}
+    elif op == "spatial_mean":
+        B, HW, C = a["B"], a["HW"], a["x"].shape[1]
+        x = a["x"].to(f64).reshape(B, HW, C)
+        reg = [(f"image {b}", (slice(b, b + 1), slice(None))) for b in range(B)] + [(f"channels {c}-{min(c + 64, C) - 1}", (slice(None), slice(c, c + 64))) for c in range(0, C, 64)]
+        out = {"mean": ("mean32", x.mean(1), x.abs().mean(1), reg)}
+    elif op == "spatial_mean_bwd":
+        B, HW, C, coff = a["B"], a["HW"], a["C"], a["coff"]
+        gs = (a["g"].to(f64)[:, coff:coff + C] / HW)[:, None, :].expand(B, HW, C).reshape(B * HW, C)
+        bs = a["base"].to(f64) if a["base"] is not None else torch.zeros_like(gs)
+        out = {"dx": ("sum", bs + gs, bs.abs() + gs.abs(), None)}
+    elif op == "clip":
+        B, _, Hin, Win = a["px"].shape
+        S, P, Kpad = a["S"], a["P"], a["Kpad"]
+        gp, k3 = S // P, 3 * P * P
+        ref = stream_ref64_clip(a["px"], S, P, Kpad)
+
+        def ex(m):      # [S][S] pixel mask -> [B * g * g][Kpad]
+            mm = m[None, None].expand(B, 3, S, S).reshape(B, 3, gp, P, gp, P).permute(0, 2, 4, 1, 3, 5).reshape(B * gp * gp, k3)
+            return _padb(mm, (0, Kpad - k3))
+        ring = ~_padb(torch.ones(S - 4, S - 4, dtype=torch.bool), (2, 2, 2, 2))      # two pixels wide: the rows and columns whose window can reach past the image
+        reg = _pixel_regions(ring, ex)
+        if Kpad > k3:
+            reg.append(("pad columns (zero)", (slice(None), slice(k3, Kpad))))
+        out = {"patches": ("clip", ref, torch.full_like(ref, 1.0 / min(CLIP_STD)), reg)}
+    _STREAM_CACHE[case.tag] = out
+    return out
+
+
+def stream_rows(case, got, ref=None):
+    """the rows of one case: got = {output name: tensor on the CPU}"""
+    rows = []
+    for name, (cls, rf, scale, reg) in (ref or stream_ref64(case)).items():
+        g = got.get(name)
+        if case.op == "unary" and g is not None:
+            g = g[torch.isfinite(case.a["x"].float())]
+        rows += stream_slices(f"{case.tag} {name}", g, rf, cls, scale, reg)
+    if case.op == "unary":      # the non-finite patterns: NaN gives NaN (leaky ReLU backward: what `x > 0` false gives), no finite x a non-finite y
+        x, y, o = case.a["x"].float(), got["y"].float(), case.a["op"]
+        want_nan = torch.isnan(stream_ref64_unary(o, case.a["x"], case.a["dy"]))
+        rows.append((f"{case.tag}: NaN patterns that do not give NaN", float((torch.isnan(x) & want_nan & ~torch.isnan(y)).sum()), 0.0))
+        rows.append((f"{case.tag}: finite patterns that give a non-finite value", float((torch.isfinite(x) & ~torch.isfinite(y)).sum()), 0.0))
+    if case.op == "clip" and case.a["kind"] == "rand" and case.tag.startswith("clip_preprocess identity"):
+        px = case.a["px"]      # the identity resize: the normalised input, rounded once (the fp32 expression of the kernel: every step is one IEEE operation)
+        img = ((px + 1.0) * 0.5 - torch.tensor(CLIP_MEAN)[None, :, None, None]) / torch.tensor(CLIP_STD)[None, :, None, None]
+        B, S, P = px.shape[0], case.a["S"], case.a["P"]
+        want = img.reshape(B, 3, S // P, P, S // P, P).permute(0, 2, 4, 1, 3, 5).reshape(-1, 3 * P * P).to(bf16)
+        rows.append((f"{case.tag}: elements that are not the normalised input rounded once", float((got["patches"][:, :3 * P * P] != want).sum()), 0.0))
+    return rows
+
+
+def stream_run(hip, case, dev):
+    """the case through e4t.ops on the GPU -> {output name: CPU tensor}"""
+    a, op = case.a, case.op
+    d = lambda t: None if t is None else t.to(dev)
+    if op == "unary":
+        return {"y": hip.unary(d(a["x"]), a["op"], d(a["dy"])).cpu()}
+    if op == "geglu":
+        u, H = d(a["u"]), a["u"].shape[1] // 2
+        du = hip.geglu_bwd(u, d(a["dh"])).cpu()
+        return {"h": hip.geglu_fwd(u).cpu(), "da": du[:, :H], "dg": du[:, H:]}
+    if op == "add":
+        return {"y": hip.add(d(a["a"]), d(a["b"])).cpu()}
+    if op == "softmax":
+        return {"p": hip.softmax_rows_(d(a["x"]).clone()).cpu()}
+    if op == "timestep":
+        return {"emb": hip.timestep_embedding(d(a["t"]), a["dim"]).cpu()}
+    if op == "sumsq":
+        return {"sum": hip.sumsq(d(a["g"])).reshape(1).cpu()}
+    if op == "transpose":
+        R, C = a["x"].shape
+        xb = torch.zeros(R, a["x"].stride(0), dtype=bf16, device=dev)      # the case's row stride (ldi = C + 1 for two of them)
+        xb[:, :C] = d(a["x"])
+        return {"y": hip.transpose(xb[:, :C]).cpu()}
+    if op == "conv_weight":
+        f, g = hip.conv_weight_prepare(d(a["w"]), a["Ipad"], a["Opad"], want_fwd=a["fwd"], want_dgrad=a["dgrad"])
+        return {k: v.cpu() for k, v in (("fwd", f), ("dgrad", g)) if v is not None}
+    if op == "sumpool2":
+        return {"y": hip.sumpool2(d(a["x"]), a["B"], a["H"], a["W"]).cpu()}
+    if op in ("im2col", "im2col_T"):
+        fn = hip.im2col if op == "im2col" else hip.im2col_T
+        return {"y": fn(d(a["x"]), a["B"], a["Hin"], a["Win"], a["Hout"], a["Wout"], a["mode"]).cpu()}
+    if op == "im2col3":
+        return {"y": hip.im2col3_rgb(d(a["px"])).cpu()}
+    if op == "spatial_mean":
+        C = a["x"].shape[1]
+        out = torch.full((a["B"], a["ldo"]), float("nan"), dtype=f32, device=dev)
+        hip.spatial_mean(d(a["x"]), a["B"], a["HW"], out, a["coff"])
+        return {"mean": out[:, a["coff"]:a["coff"] + C].cpu()}
+    if op == "spatial_mean_bwd":
+        return {"dx": hip.spatial_mean_bwd(d(a["g"]), d(a["base"]), a["B"], a["HW"], a["C"], a["coff"]).cpu()}
+    if op == "clip":
+        return {"patches": hip.clip_preprocess(d(a["px"]), a["S"], a["P"], a["Kpad"]).cpu()}
+    raise KeyError(op)
+
+
+def _sumsq_raw_rows(hip, case, dev):
+    """e4t_sumsq_partial through the ABI: partial NaN-filled first, nblocks = 1 and 1024 (n = 1: 1023 blocks without an element must still write 0)"""
+    from e4t.ops import _stream, _ptr
+    rows = []
+    g = case.a["g"].to(dev)
+    cls, ref, scale, _ = stream_ref64(case)["sum"]
+    for nb in SUMSQ_BLOCKS:
+        part = torch.full((nb,), float("nan"), dtype=f32, device=dev)
+        code = hip.lib.e4t_sumsq_partial(_ptr(g), g.numel(), _ptr(part), nb, _stream())
+        torch.cuda.synchronize()
+        rows.append((f"{case.tag} nblocks {nb}: return code", float(code), 0.0))
+        rows.append((f"{case.tag} nblocks {nb}: NaN left in partial", float(torch.isnan(part).sum()), 0.0))
+        rows += stream_slices(f"{case.tag} nblocks {nb}: sum of the partials", part.to(f64).sum().reshape(1).cpu(), ref, cls, scale, [])
+    return rows
+
+
+def check_streaming_values(hip, emu, dev):
+    """the activation, softmax, embedding and sum-of-squares kernels against their fp64 definitions on CPU-drawn inputs: every bf16 bit pattern
+    through the eight unary ops and the GEGLU gate, saturating and cancelling rows, per-region elementwise errors (stream_slices)"""
+    out = []
+    for case in stream_value_cases():
+        out += stream_rows(case, stream_run(hip, case, dev))
+        if case.op == "sumsq":
+            out += _sumsq_raw_rows(hip, case, dev)
+    return out
+
+
+def check_streaming_layout(hip, emu, dev):
+    """the layout, pooling and preprocessing kernels on non-square and ragged shapes: permutations exact against plainly written index
+    arithmetic, sums and the bicubic resize against fp64, border ring and interior apart"""
+    out = []
+    for case in stream_layout_cases():
+        out += stream_rows(case, stream_run(hip, case, dev))
+    return out
+
+
+# ---- streaming_guards: the raw ABI, exactly sized buffers between sentinel bands; no out-of-range argument anywhere ---------------------
+def _left(view):
+    """16-bit words of an output region that still hold the sentinel (poison the kernel should have overwritten)"""
+    if view.dtype == bf16:
+        return int((view.contiguous().view(torch.int16) == SENT16).sum())
+    return int((view.contiguous().view(torch.int32) == SENT16 * 0x10001).sum())      # an fp32 word of a _Guarded buffer: the 16-bit sentinel twice
+
+
+def _guard_rows(tag, code, outs, values):
+    """outs: [(a _Guarded, the view of what the kernel owns or None = all of it)]; values: rows"""
+    torch.cuda.synchronize()
+    rows = [(f"{tag}: return code", float(code), 0.0),
+            (f"{tag}: sentinel words changed around the outputs", float(sum(o.outside() for o, _ in outs)), 0.0),
+            (f"{tag}: poison left in what the kernel owns", float(sum(_left(o.view if own is None else own) for o, own in outs)), 0.0)]
+    return rows + values
+
+
+def check_streaming_guards(hip, emu, dev):
+    """every entry point of the family through the C ABI: outputs exactly sized inside sentinel bands and poisoned, inputs between rows of NaN;
+    per kernel the return code, sentinel words changed (0), poison left in what the kernel owns (0), and the values against fp64.  Strides,
+    offsets and pads no e4t.ops call passes: transpose batches with gaps and ldo > R, softmax ld > L, spatial_mean coff / ldo, clip_preprocess
+    Kpad > 3 P^2 (the kernel leaves the pad alone; ops.clip_preprocess zeroes it), im2col_T ldo rounded up (zero fill)."""
+    from e4t.ops import _stream, _ptr
+    lib, out, st = hip.lib, [], _stream()
+    g = _cg(3300)
+    keep = []      # every device input stays referenced until the rows are read: a temporary's memory would be handed to the next allocation
+
+    def d(t):
+        keep.append(t.to(dev))
+        return keep[-1]
+
+    def wrapped(t):
+        keep.append(_nan_wrapped(d(t)))
+        return keep[-1]
+    val = lambda tag, got, ref, cls, scale=None: stream_slices(tag, got.cpu(), ref, cls, scale, [])
+    # geglu, unary, add: exactly sized outputs
+    M, H = 37, 72
+    u, dh = _cr(g, M, 2 * H), _cr(g, M, H)
+    r = stream_ref64_geglu(u, dh)
+    A, G, D = u[:, :H].to(f64).abs(), u[:, H:].to(f64).abs(), dh.to(f64).abs()
+    ug, dhg = wrapped(u), wrapped(dh)
+    h = _Guarded(M, H, bf16, dev)
+    code = lib.e4t_geglu_fwd(_ptr(ug), h.ptr, M, H, st)
+    out += _guard_rows("geglu_fwd 37x72 guarded", code, [(h, None)], val("geglu_fwd guarded h", h.view, r["h"], "gelu", A * G / 2))
+    du = _Guarded(M, 2 * H, bf16, dev)
+    code = lib.e4t_geglu_bwd(_ptr(ug), _ptr(dhg), du.ptr, M, H, st)
+    out += _guard_rows("geglu_bwd 37x72 guarded", code, [(du, None)],
+                       val("geglu_bwd guarded da", du.view[:, :H], r["da"], "gelu", D * G / 2) + val("geglu_bwd guarded dg", du.view[:, H:], r["dg"], "dgelu", D * A))
+    x, dy = _cr(g, M, H), _cr(g, M, H)
+    xg, dyg = wrapped(x), wrapped(dy)
+    for op, cls, scale in ((0, "sigmoid", x.to(f64).abs()), (3, "dgelu", dy.to(f64).abs())):
+        y = _Guarded(M, H, bf16, dev)
+        code = lib.e4t_unary(_ptr(xg), _ptr(dyg) if op & 1 else None, y.ptr, M * H, op, st)
+        out += _guard_rows(f"unary op{op} 37x72 guarded", code, [(y, None)], val(f"unary op{op} guarded y", y.view, stream_ref64_unary(op, x, dy), cls, scale))
+    y = _Guarded(M, H, bf16, dev)
+    code = lib.e4t_add(_ptr(xg), _ptr(dyg), y.ptr, M * H, st)
+    s = x.to(f64) + dy.to(f64)
+    out += _guard_rows("add 37x72 guarded", code, [(y, None)], val("add guarded y", y.view, s, "round", s.abs()))
+    # transpose: three images with sentinel gaps between them, ldo = R + 8
+    nb, R, C, gap = 3, 37, 70, 5
+    xs = _cr(g, nb, R, C)
+    xin = torch.full((nb * (R + gap), C + 2), float("nan"), dtype=bf16, device=dev)
+    for b in range(nb):
+        xin[b * (R + gap):b * (R + gap) + R, :C] = d(xs[b])
+    y = _Guarded(nb * (C + gap), R + 8, bf16, dev)
+    code = lib.e4t_transpose(_ptr(xin), y.ptr, nb, R, C, C + 2, R + 8, (R + gap) * (C + 2), (C + gap) * (R + 8), st)
+    torch.cuda.synchronize()
+    yb = y.view.reshape(nb, C + gap, R + 8)
+    own = yb[:, :C, :R]
+    rest = yb.contiguous().view(torch.int16).clone()
+    rest[:, :C, :R] = SENT16
+    out += _guard_rows(f"transpose batch {nb} {R}x{C} ldo {R + 8}, gaps of {gap} rows, guarded", code, [(y, own)],
+                       [("transpose guarded: pad columns and gap rows changed", float((rest != SENT16).sum()), 0.0)] + val("transpose guarded y", own, xs.transpose(1, 2), "exact"))
+    # softmax_rows in place with ld = L + 8: the gap columns bitwise unchanged
+    rows_, L = 3, 2056
+    xs = softmax_rows_input(L, SOFTMAX_ROWS[L], g)
+    y = _Guarded(rows_, L + 8, bf16, dev)
+    y.view[:, :L] = d(xs)
+    code = lib.e4t_softmax_rows(y.ptr, rows_, L, L + 8, st)
+    p = stream_ref64_softmax(xs)
+    out += _guard_rows(f"softmax_rows {rows_}x{L} ld {L + 8} guarded", code, [(y, y.view[:, :L])],
+                       [("softmax_rows guarded: gap columns changed", float((y.view[:, L:].contiguous().view(torch.int16) != SENT16).sum()), 0.0)] + val("softmax_rows guarded p", y.view[:, :L], p, "softmax", p))
+    # spatial_mean into a column slice; spatial_mean_bwd out of one
+    B, HW, C, ldo, coff = 3, 65, 132, 200, 60
+    xs = _cr(g, B * HW, C)
+    o = _Guarded(B, ldo, f32, dev)
+    code = lib.e4t_spatial_mean(_ptr(wrapped(xs)), o.ptr, B, HW, C, ldo, coff, st)
+    torch.cuda.synchronize()
+    side = torch.cat([o.view[:, :coff], o.view[:, coff + C:]], 1).contiguous().view(torch.int16)
+    x64 = xs.to(f64).reshape(B, HW, C)
+    out += _guard_rows(f"spatial_mean B{B} HW{HW} C{C} ldo{ldo} coff{coff} guarded", code, [(o, o.view[:, coff:coff + C])],
+                       [("spatial_mean guarded: columns left and right changed", float((side != SENT16).sum()), 0.0)] + val("spatial_mean guarded mean", o.view[:, coff:coff + C], x64.mean(1), "mean32", x64.abs().mean(1)))
+    B, HW, C, ldg, coff = 2, 5, 8, 24, 8
+    gs = torch.full((B, ldg), float("nan"), dtype=f32)
+    gs[:, coff:coff + C] = _cr(g, B, C, dtype=f32)
+    base = _cr(g, B * HW, C)
+    dx = _Guarded(B * HW, C, bf16, dev)
+    code = lib.e4t_spatial_mean_bwd(_ptr(d(gs)), _ptr(wrapped(base)), dx.ptr, B, HW, C, ldg, coff, st)
+    gq = (gs.to(f64)[:, coff:coff + C] / HW)[:, None, :].expand(B, HW, C).reshape(B * HW, C)
+    out += _guard_rows(f"spatial_mean_bwd B{B} HW{HW} C{C} ldg{ldg} coff{coff} guarded (NaN beside the slice of g)", code, [(dx, None)],
+                       val("spatial_mean_bwd guarded dx", dx.view, base.to(f64) + gq, "sum", base.to(f64).abs() + gq.abs()))
+    # sumpool2, im2col, im2col_T (ldo rounded up: zero fill), im2col3_rgb, conv_weight_prepare
+    B, H, W, C = 2, 5, 3, 72
+    xs = _cr(g, B * 2 * H * 2 * W, C)
+    y = _Guarded(B * H * W, C, bf16, dev)
+    code = lib.e4t_sumpool2(_ptr(wrapped(xs)), y.ptr, B, H, W, C, st)
+    x6 = xs.to(f64).reshape(B, H, 2, W, 2, C)
+    out += _guard_rows(f"sumpool2 B{B} {H}x{W} C{C} guarded", code, [(y, None)], val("sumpool2 guarded y", y.view, x6.sum((2, 4)).reshape(-1, C), "sum", x6.abs().sum((2, 4)).reshape(-1, C)))
+    mode, B, Hin, Win, Hout, Wout, C = CONV_S2, 1, 7, 9, 4, 5, 72      # 20 output pixels: ldo = 24 leaves four pad columns
+    xs = _cr(g, B * Hin * Win, C)
+    xg = wrapped(xs)
+    Mpix, ld = B * Hout * Wout, (B * Hout * Wout + 7) // 8 * 8
+    y = _Guarded(Mpix, 9 * C, bf16, dev)
+    code = lib.e4t_im2col(_ptr(xg), y.ptr, B, Hin, Win, C, Hout, Wout, mode, st)
+    out += _guard_rows(f"im2col mode{mode} {Hin}x{Win}->{Hout}x{Wout} C{C} guarded", code, [(y, None)], val("im2col guarded y", y.view, stream_ref_im2col(xs, B, Hin, Win, Hout, Wout, mode), "exact"))
+    y = _Guarded(9 * C, ld, bf16, dev)
+    code = lib.e4t_im2col_T(_ptr(xg), y.ptr, B, Hin, Win, C, Hout, Wout, ld, mode, st)
+    out += _guard_rows(f"im2col_T mode{mode} {Hin}x{Win}->{Hout}x{Wout} C{C} ldo {ld} (Mpix {Mpix}) guarded", code, [(y, None)],
+                       val("im2col_T guarded y, columns [Mpix, ldo) zero", y.view, stream_ref_im2col_T(xs, B, Hin, Win, Hout, Wout, mode, ld), "exact"))
+    B, H, W = 2, 5, 3
+    px = torch.rand(B, 3, H, W, generator=g) * 2 - 1
+    y = _Guarded(B * H * W, 32, bf16, dev)
+    code = lib.e4t_im2col3_rgb(_ptr(wrapped(px)), y.ptr, B, H, W, st)
+    out += _guard_rows(f"im2col3_rgb B{B} {H}x{W} guarded", code, [(y, None)], val("im2col3_rgb guarded y", y.view, stream_ref_im2col3(px), "exact"))
+    O, I, Ipad, Opad = 72, 200, 256, 128
+    w = _cr(g, O, I, 3, 3, scale=0.05, dtype=f32)
+    f_ref, d_ref = stream_ref_conv_weight(w, Ipad, Opad)
+    wg = wrapped(w)
+    for form in ("fwd only", "dgrad only", "both"):
+        wf = _Guarded(O, 9 * Ipad, bf16, dev) if form != "dgrad only" else None
+        wd = _Guarded(I, 9 * Opad, bf16, dev) if form != "fwd only" else None
+        code = lib.e4t_conv_weight_prepare(_ptr(wg), wf.ptr if wf else None, wd.ptr if wd else None, O, I, Ipad, Opad, st)
+        vals = (val("conv_weight_prepare guarded fwd", wf.view, f_ref, "exact") if wf else []) + (val("conv_weight_prepare guarded dgrad", wd.view, d_ref, "exact") if wd else [])
+        out += _guard_rows(f"conv_weight_prepare {I}->{O} pads {Ipad}/{Opad} {form} guarded", code, [(b, None) for b in (wf, wd) if b], vals)
+    # clip_preprocess, Kpad > 3 P^2: through the ABI the pad columns keep the sentinel; through e4t.ops they are zero
+    B, Hin, Win, S, P, Kpad = 1, 48, 80, 28, 14, 640
+    px = torch.rand(B, 3, Hin, Win, generator=g) * 2 - 1
+    ref = stream_ref64_clip(px, S, P, Kpad)
+    k3, gp = 3 * P * P, S // P
+    y = _Guarded(B * gp * gp, Kpad, bf16, dev)
+    code = lib.e4t_clip_preprocess(_ptr(wrapped(px)), y.ptr, B, Hin, Win, S, P, Kpad, st)
+    out += _guard_rows(f"clip_preprocess {Hin}x{Win}->{S} P{P} Kpad{Kpad} guarded", code, [(y, y.view[:, :k3])],
+                       [("clip_preprocess guarded: pad columns changed by the kernel", float((y.view[:, k3:].contiguous().view(torch.int16) != SENT16).sum()), 0.0)]
+                       + val("clip_preprocess guarded patches", y.view[:, :k3], ref[:, :k3], "clip", torch.full_like(ref[:, :k3], 1.0 / min(CLIP_STD))))
+    got = hip.clip_preprocess(d(px), S, P, Kpad)
+    out.append(("clip_preprocess through e4t.ops: nonzero words in the pad columns", float((got[:, k3:].contiguous().view(torch.int16) != 0).sum()), 0.0))
+    # timestep_embedding and sumsq_partial: exactly sized
+    t = torch.tensor(TIMESTEPS)
+    e = _Guarded(len(TIMESTEPS), 322, bf16, dev)
+    code = lib.e4t_timestep_embedding(_ptr(d(t)), e.ptr, len(TIMESTEPS), 322, st)
+    e64 = stream_ref64_timestep(t, 322)
+    out += _guard_rows("timestep_embedding B6 dim322 guarded", code, [(e, None)], val("timestep_embedding guarded emb", e.view, e64, "embed", torch.ones_like(e64)))
+    gv = _cr(g, 257, dtype=f32)
+    part = _Guarded(1, 1024, f32, dev)
+    code = lib.e4t_sumsq_partial(_ptr(wrapped(gv.reshape(1, -1))), 257, part.ptr, 1024, st)
+    s = (gv.to(f64) ** 2).sum().reshape(1)
+    out += _guard_rows("sumsq_partial n257 nblocks 1024 guarded", code, [(part, None)], val("sumsq_partial guarded sum", part.view.to(f64).sum().reshape(1), s, "sumsq32", s))
+    return out
+
+
 def all_checks(hip, emu, dev, ops_mod):
     yield "gemm_races", lambda: check_gemm_races(hip, emu, dev)
     yield "probe", lambda: check_probe(hip, emu, dev)
@@ -2852,6 +3547,9 @@ def all_checks(hip, emu, dev, ops_mod):
     yield "norms", lambda: check_norms(hip, emu, dev)
     yield "norm_guards", lambda: check_norm_guards(hip, emu, dev)
     yield "streaming", lambda: check_streaming(hip, emu, dev)
+    yield "streaming_values", lambda: check_streaming_values(hip, emu, dev)
+    yield "streaming_layout", lambda: check_streaming_layout(hip, emu, dev)
+    yield "streaming_guards", lambda: check_streaming_guards(hip, emu, dev)
     yield "wo", lambda: check_wo(hip, emu, dev, ops_mod)
     yield "wo_forms", lambda: check_wo_forms(hip, emu, dev, ops_mod)
     yield "wo_guards", lambda: check_wo_guards(hip, emu, dev, ops_mod)

@@ -5,7 +5,7 @@ import kernel_checks as kc
 
 pytestmark = pytest.mark.gpu
 
-FAMILIES = ["probe", "gemm", "gemm_races", "gemm_kloop", "gemm_edges", "gemm_forms", "gemm_guards", "conv", "conv_forms", "conv_guards", "attention", "norms", "norm_guards", "streaming", "wo", "wo_forms", "wo_guards", "image_prep"]
+FAMILIES = ["probe", "gemm", "gemm_races", "gemm_kloop", "gemm_edges", "gemm_forms", "gemm_guards", "conv", "conv_forms", "conv_guards", "attention", "norms", "norm_guards", "streaming", "streaming_values", "streaming_layout", "streaming_guards", "wo", "wo_forms", "wo_guards", "image_prep"]
 
 
 @pytest.mark.parametrize("family", FAMILIES)
