@@ -1,4 +1,4 @@
-// Body of adamw_kernel / adamw_ema_kernel (elementwise.hip), included once into each: the two __global__ kernels differ only in what they bind to
+// Body of adamw_kernel / adamw_ema_kernel (optim.hip), included once into each: the two __global__ kernels differ only in what they bind to
 // EMA, ema and ema_w, so the plain kernel keeps its symbol and, not being routed through a shared device function, its code (DESIGN §2.1, §2.3c).
 // EMA: the average `ema` of the weights moves in the same pass, e' = ema_f(e, p', w) with p' the value this thread stores; hyper is then float[8], [4] = w.
   if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; gscale = hyper[3]; if constexpr (EMA) ema_w = hyper[4]; }

@@ -1,4 +1,4 @@
-// Body of adamw_rank_kernel<RB> / adamw_rank_ema_kernel<RB> (elementwise.hip), included once into each, as adamw_kernel.inc is: the plain kernel keeps
+// Body of adamw_rank_kernel<RB> / adamw_rank_ema_kernel<RB> (optim.hip), included once into each, as adamw_kernel.inc is: the plain kernel keeps
 // its symbol and its code.  EMA: the average of the stack moves in the same pass (32 B per parameter); hyper is then float[8], [4] = w.
   if (hyper) { lr = hyper[0]; bc1 = hyper[1]; bc2_sqrt = hyper[2]; gscale = hyper[3]; if constexpr (EMA) ema_w = hyper[4]; }
   __shared__ float gs[16 * RB];                      // G[k0 + k][r0 + rr] as fp32, [rr][k]

@@ -166,8 +166,14 @@ __device__ __forceinline__ float geglu_da_f(float d, float g) { return d * gelu_
 __device__ __forceinline__ float geglu_dg_f(float d, float a, float g) { return d * a * dgelu_f(g); }
 
 // EMA of a weight per element: e' = e - w * (e - p) with w = 1 - decay and p the value just stored (fp32).  The ONE statement of this arithmetic, used by
-// adamw_ema_kernel, adamw_rank_ema_kernel and ema_update_kernel (elementwise.hip); the fused multiply-add is spelled out so that no context contracts it differently
+// adamw_ema_kernel, adamw_rank_ema_kernel and ema_update_kernel (optim.hip); the fused multiply-add is spelled out so that no context contracts it differently
 __device__ __forceinline__ float ema_f(float e, float p, float w) { return fmaf(-w, e - p, e); }
 
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long long cdivl(long long a, long long b) { return (a + b - 1) / b; }
+// grid of a grid-stride kernel over `work` items, 256 per block: at least 1 block, at most cap
+static inline int grid_for(long long work, int cap = 2048) {
+  long long b = (work + 255) / 256;
+  if (b < 1) b = 1;
+  return (int)(b > cap ? cap : b);
+}

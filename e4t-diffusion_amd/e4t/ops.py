@@ -708,22 +708,32 @@ class HipBackend:
         _C.check(self.lib.e4t_mask_prep(_ptr(pool), _ptr(table), _ptr(mask_off), _ptr(out), B, S, _stream()), "e4t_mask_prep")
         return out
 
+    @staticmethod
+    def _loss_operands(pred, target, w, lam, save):
+        """what the loss entry points share -> (B, C, HW, pred, target, w, lam, nhwc, wd, stats): fp32 pred / target [B, C, h, w], the mask
+        w [B, h, w] and the per-image weight lam [B] (either may be None), made contiguous.  pred may be an NCHW view of NHWC storage (the
+        native UNet's output) and is then read in place (nhwc); wd (None unless save) has pred's layout, stats is the device {loss, den, workspace}."""
+        B, Cn = pred.shape[0], pred.shape[1]
+        HW = pred.numel() // (B * Cn)
+        assert pred.dtype == f32 and target.dtype == f32 and pred.dim() == 4 and target.shape == pred.shape
+        assert w is None or (w.dtype == f32 and w.numel() == B * HW)
+        assert lam is None or (lam.dtype == f32 and lam.numel() == B)
+        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
+        if not nhwc:
+            pred = pred.contiguous()
+        w = None if w is None else w.contiguous()
+        lam = None if lam is None else lam.contiguous()
+        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
+        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
+        return B, Cn, HW, pred, target.contiguous(), w, lam, int(nhwc), wd, stats
+
     def masked_mse(self, pred, target, w, save=True):
         """sum w (pred - target)^2 / (C max(sum w, 1)) for fp32 pred / target [B, C, h, w] and w [B, h, w] -> (loss (0-dim), wd, stats).
         pred may be an NCHW view of NHWC storage (the native UNet's output) and is read in place; wd = w * (pred - target) in pred's
         layout and stats (device {loss, den, workspace}) are what masked_mse_bwd needs; save=False skips wd."""
-        B, Cn = pred.shape[0], pred.shape[1]
-        HW = pred.numel() // (B * Cn)
-        assert pred.dtype == f32 and target.dtype == f32 and w.dtype == f32 and pred.dim() == 4
-        assert target.shape == pred.shape and w.numel() == B * HW
-        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
-        if not nhwc:
-            pred = pred.contiguous()
-        target, w = target.contiguous(), w.contiguous()
-        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
-        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
-        _C.check(self.lib.e4t_masked_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(wd), _ptr(stats), B, Cn, HW, int(nhwc), _stream()),
-                 "e4t_masked_mse_fwd")
+        assert w is not None
+        B, Cn, HW, pred, target, w, _, nhwc, wd, stats = self._loss_operands(pred, target, w, None, save)
+        _C.check(self.lib.e4t_masked_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(wd), _ptr(stats), B, Cn, HW, nhwc, _stream()), "e4t_masked_mse_fwd")
         return stats[0], wd, stats
 
     def masked_mse_bwd(self, wd, stats, g):
@@ -736,20 +746,8 @@ class HipBackend:
     def weighted_mse(self, pred, target, lam=None, w=None, save=True):
         """sum lam[b] w (pred - target)^2 / (C max(sum w, 1)) -> (loss (0-dim), wd, stats): masked_mse with a per-image weight lam [B]
         (None = ones) and an optional mask w [B, h, w] (None = ones); wd = lam * w * (pred - target) in pred's layout."""
-        B, Cn = pred.shape[0], pred.shape[1]
-        HW = pred.numel() // (B * Cn)
-        assert pred.dtype == f32 and target.dtype == f32 and pred.dim() == 4 and target.shape == pred.shape
-        assert w is None or (w.dtype == f32 and w.numel() == B * HW)
-        assert lam is None or (lam.dtype == f32 and lam.numel() == B)
-        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
-        if not nhwc:
-            pred = pred.contiguous()
-        target = target.contiguous()
-        w = None if w is None else w.contiguous()
-        lam = None if lam is None else lam.contiguous()
-        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
-        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
-        _C.check(self.lib.e4t_weighted_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(lam), _ptr(wd), _ptr(stats), B, Cn, HW, int(nhwc), _stream()),
+        B, Cn, HW, pred, target, w, lam, nhwc, wd, stats = self._loss_operands(pred, target, w, lam, save)
+        _C.check(self.lib.e4t_weighted_mse_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(lam), _ptr(wd), _ptr(stats), B, Cn, HW, nhwc, _stream()),
                  "e4t_weighted_mse_fwd")
         return stats[0], wd, stats
 
@@ -761,25 +759,14 @@ class HipBackend:
         """The scheduled pseudo-Huber (kind "huber" / 1) or smooth-L1 ("smooth_l1" / 2) loss of functional.robust_loss ->
         (loss (0-dim), wd, stats): weighted_mse's operands and layouts plus ctab fp32 [T] and timesteps int64 [B] (None = ctab[0] for
         every image), both read on the device.  wd = lam * w * (k / 2) * d / sqrt(d^2 + c^2) in pred's layout is what robust_loss_bwd needs."""
-        B, Cn = pred.shape[0], pred.shape[1]
-        HW = pred.numel() // (B * Cn)
         kind = {"huber": _C.LOSS_HUBER, "smooth_l1": _C.LOSS_SMOOTH_L1}.get(kind, kind)
-        assert pred.dtype == f32 and target.dtype == f32 and pred.dim() == 4 and target.shape == pred.shape
+        B, Cn, HW, pred, target, w, lam, nhwc, wd, stats = self._loss_operands(pred, target, w, lam, save)
         assert ctab.dtype == f32 and ctab.dim() == 1 and ctab.device == pred.device
         assert timesteps is None or (timesteps.dtype == torch.int64 and timesteps.numel() == B and timesteps.device == pred.device)
-        assert w is None or (w.dtype == f32 and w.numel() == B * HW)
-        assert lam is None or (lam.dtype == f32 and lam.numel() == B)
-        nhwc = not pred.is_contiguous() and pred.permute(0, 2, 3, 1).is_contiguous()
-        if not nhwc:
-            pred = pred.contiguous()
-        target, ctab = target.contiguous(), ctab.contiguous()
+        ctab = ctab.contiguous()
         timesteps = None if timesteps is None else timesteps.contiguous()
-        w = None if w is None else w.contiguous()
-        lam = None if lam is None else lam.contiguous()
-        wd = torch.empty_like(pred) if save else None          # (preserve_format: pred's own strides)
-        stats = torch.empty(_C.MASKED_MSE_STATS, dtype=f32, device=pred.device)
         _C.check(self.lib.e4t_robust_loss_fwd(_ptr(pred), _ptr(target), _ptr(w), _ptr(lam), _ptr(ctab), _ptr(timesteps), _ptr(wd), _ptr(stats), B, Cn, HW,
-                                              ctab.numel(), int(kind), int(nhwc), _stream()), "e4t_robust_loss_fwd")
+                                              ctab.numel(), int(kind), nhwc, _stream()), "e4t_robust_loss_fwd")
         return stats[0], wd, stats
 
     def robust_loss_bwd(self, wd, stats, g):
@@ -811,13 +798,19 @@ class HipBackend:
         self._timed("adamw", 0.0, lambda: _C.check(self.lib.e4t_adamw_hyper(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(hyper), beta1, beta2, eps, wd,
                                                                             _stream()), "e4t_adamw_hyper"), 28.0 * p.numel())
 
-    def adamw_rank(self, p, m, v, G, Z, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, hyper=None):
-        """AdamW of the stack p [n, rows, cols] (fp32, with its moments) under the never-materialised gradient
-        dW_i = grad_scale * G^T Z[:, i*cols:(i+1)*cols]   (G [K, rows], Z [K, n*cols], bf16).  hyper: device scalars as in adamw_hyper."""
+    @staticmethod
+    def _rank_operands(p, m, v, G, Z):
+        """the checks adamw_rank and adamw_rank_ema share -> (n, rows, cols, K): p, m, v [n, rows, cols], G [K, rows], Z [K, n*cols] (bf16, unit column stride)"""
         n, rows, cols = p.shape
         K = G.shape[0]
         assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and G.dtype == bf16 and Z.dtype == bf16
         assert G.shape[1] == rows and Z.shape == (K, n * cols) and G.stride(1) == 1 and Z.stride(1) == 1
+        return n, rows, cols, K
+
+    def adamw_rank(self, p, m, v, G, Z, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, hyper=None):
+        """AdamW of the stack p [n, rows, cols] (fp32, with its moments) under the never-materialised gradient
+        dW_i = grad_scale * G^T Z[:, i*cols:(i+1)*cols]   (G [K, rows], Z [K, n*cols], bf16).  hyper: device scalars as in adamw_hyper."""
+        n, rows, cols, K = self._rank_operands(p, m, v, G, Z)
         self._timed("adamw", 2.0 * p.numel() * K, lambda: _C.check(self.lib.e4t_adamw_rank(
             _ptr(p), _ptr(m), _ptr(v), _ptr(G), _ptr(Z), n, rows, cols, K, G.stride(0), Z.stride(0), lr, beta1, beta2, eps, wd, int(step), grad_scale,
             _ptr(hyper), _stream()), "e4t_adamw_rank"), 24.0 * p.numel())
@@ -833,11 +826,8 @@ class HipBackend:
 
     def adamw_rank_ema(self, p, m, v, ema, G, Z, lr, beta1, beta2, eps, wd, step, grad_scale=1.0, ema_w=0.0, hyper=None):
         """adamw_rank plus the EMA of the stack (ema [n, rows, cols], fp32) in the same pass; hyper as in adamw_ema"""
-        n, rows, cols = p.shape
-        K = G.shape[0]
-        assert p.is_contiguous() and m.is_contiguous() and v.is_contiguous() and G.dtype == bf16 and Z.dtype == bf16
+        n, rows, cols, K = self._rank_operands(p, m, v, G, Z)
         assert ema.is_contiguous() and ema.dtype == f32 and ema.shape == p.shape and (hyper is None or hyper.numel() == 8)
-        assert G.shape[1] == rows and Z.shape == (K, n * cols) and G.stride(1) == 1 and Z.stride(1) == 1
         self._timed("adamw", 2.0 * p.numel() * K, lambda: _C.check(self.lib.e4t_adamw_rank_ema(
             _ptr(p), _ptr(m), _ptr(v), _ptr(ema), _ptr(G), _ptr(Z), n, rows, cols, K, G.stride(0), Z.stride(0), lr, beta1, beta2, eps, wd, int(step), grad_scale,
             ema_w, _ptr(hyper), _stream()), "e4t_adamw_rank_ema"), 32.0 * p.numel())

@@ -86,7 +86,7 @@ def ema_weight(decay: float, t: int) -> float:
 
 # ---- block-wise 8-bit AdamW moments (E4TTrainer(optimizer_state_bits=8)) ---------------------------------------------------
 # The fp32 torch composition below is the DEFINITION of the format: the codebooks and the rounding rule are stated here and nowhere else;
-# adamw8_kernel (csrc/elementwise.hip) receives the codebooks as device arrays and restates the rule, the tests take both from here.
+# adamw8_kernel (csrc/optim.hip) receives the codebooks as device arrays and restates the rule, the tests take both from here.
 ADAM8_BLOCK = 256
 
 

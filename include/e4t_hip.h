@@ -306,7 +306,7 @@ int e4t_weight_prepare(const e4t_wo_desc* descs_dev, int n, int max_row, int max
 /* OIHW fp32 3x3 weights -> [O][ky][kx][Ipad] (forward) and [I][2-ky][2-kx][Opad] (dgrad), bf16, zero padded */
 int e4t_conv_weight_prepare(const float* w_oihw, void* w_fwd, void* w_dgrad, int O, int I, int Ipad, int Opad, e4t_stream stream);
 
-/* ---------------------------------------------------------------- streaming ops (elementwise.hip) */
+/* ---------------------------------------------------------------- streaming ops (elementwise.hip) -- */
 int e4t_geglu_fwd(const void* u /* [M][2H] */, void* h /* [M][H] */, long long M, int H, e4t_stream stream);  /* attention.py:428-430 */
 int e4t_geglu_bwd(const void* u, const void* dh, void* du, long long M, int H, e4t_stream stream);
 #define E4T_OP_SILU 0
@@ -332,6 +332,7 @@ int e4t_spatial_mean_bwd(const float* g, const void* base, void* dx, int B, int 
 int e4t_timestep_embedding(const long long* t, void* out /* bf16 [B][dim] = [cos|sin] */, int B, int dim, e4t_stream stream); /* unet_2d_condition.py:461 */
 /* B, Hin, Win, S, P > 0, S % P == 0, Kpad >= 3 * P * P.  Columns [3 * P * P, Kpad) of patches are NOT written: the caller zeroes them (ops.clip_preprocess). */
 int e4t_clip_preprocess(const float* pixels_nchw, void* patches /* bf16 [B*g*g][Kpad] */, int B, int Hin, int Win, int S, int P, int Kpad, e4t_stream stream); /* encoder.py:131-139 + patchify */
+/* ---------------------------------------------------------------- sampling step (sampler.hip) -- */
 /* Sampling loop glue (pipeline_stable_diffusion_e4t.py:209-214): classifier-free guidance eps = u + g*(c-u) over
  * pred = [uncond | cond] (cfg = 1; cfg = 0: pred is eps) fused with a linear scheduler update
  * out = c_sample*sample + c_pred*eps (+ c_noise*noise, noise may be NULL) — DDIM for epsilon and v prediction is of this
@@ -397,6 +398,7 @@ int e4t_sampler_step_guided(const float* pred, const float* x, float* out, float
                             const float* gstat, const float* keep, const float* x0, const float* n0,
                             int B, int C, int HW, int K, int branches, int pred_nhwc, int x_in_copies,
                             int keep_per_image, int x0_per_image, e4t_stream stream);
+/* ---------------------------------------------------------------- image data path (image.hip) -- */
 /* Data path (pretrain_e4t.py:137-144 make_transforms = SmallestMaxSize(interpolation=3: cv2.INTER_AREA) -> RandomCrop ->
  * HorizontalFlip, and :174-177 image/127.5-1, HWC->CHW): a batch of raw decoded uint8 RGB images in one device pool ->
  * out fp32 [B][3][S][S].  table: int64 [B][8] (device) = {byte offset of the image in pool, H, W, newH, newW (the
@@ -409,6 +411,7 @@ int e4t_image_prep(const void* pool, const long long* table, float* out, int B, 
  * out[b][i][j] = (float)((double)s / 16320.0) with s the integer sum of the 64 resized bytes of latent pixel (i, j)'s 8 x 8 block
  * (16320 = 64 * 255).  The S x S mask is never written.  S % 8 == 0, B <= 65535. */
 int e4t_mask_prep(const void* pool, const long long* table, const long long* mask_off, float* out /* fp32 [B][S/8][S/8] */, int B, int S, e4t_stream stream);
+/* ---------------------------------------------------------------- training objective (objective.hip) -- */
 /* Masked mean-squared error replacing F.mse_loss at pretrain_e4t.py:645-647 when a loss mask is given (README.md:112-115): with d = pred - target
  * and w fp32 [B][HW] broadcast over the C channels, den = C * max(sum(w), 1) and loss = sum w * d^2 / den; dpred = g * 2 * w * d / den.
  * pred is [B][C][HW], or [B][HW][C] when pred_nhwc (the UNet's native output, as in e4t_guided_step); target is [B][C][HW]; wd (may be
@@ -456,6 +459,7 @@ int e4t_robust_loss_fwd(const float* pred, const float* target, const float* w, 
  * new timesteps gathers new coefficients.  z == NULL with s != 0 is an error (-22). */
 int e4t_diffuse(const float* x0, const float* noise, const float* z, const long long* timesteps, const float* coef, float* noisy, float* target,
                 float* lam, int B, int C, int HW, int T, float s, int v_prediction, e4t_stream stream);
+/* ---------------------------------------------------------------- streaming ops, continued (elementwise.hip) -- */
 /* in-place row softmax of a bf16 matrix [rows][ld] over the first L columns (fp32 math); L % 8 == 0, L <= 16384 */
 int e4t_softmax_rows(void* x, long long rows, int L, int ld, e4t_stream stream);
 /* 3x3/pad-1 im2col of a 3-channel NCHW fp32 image -> bf16 [B*H*W][32], column (ky*3+kx)*3+c, columns 27..31 zero */
@@ -465,6 +469,7 @@ int e4t_im2col3_rgb(const float* pixels_nchw, void* out, int B, int H, int W, e4
 int e4t_im2col_T(const void* x, void* out, int B, int Hin, int Win, int C, int Hout, int Wout, int ldo, int mode, e4t_stream stream);
 /* out[m][tap*C + c] (bf16 [B*Hout*Wout][9*C]): with e4t_gemm_tn, dW[co][tap][ci] = dY^T . im2col(X) needs no transposes. */
 int e4t_im2col(const void* x, void* out, int B, int Hin, int Win, int C, int Hout, int Wout, int mode, e4t_stream stream);
+/* ---------------------------------------------------------------- optimiser (optim.hip) -- */
 int e4t_adamw(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
               float weight_decay, int step, float grad_scale, e4t_stream stream);                                        /* pretrain_e4t.py:387-392,652 */
 /* The same update with the step-dependent scalars in DEVICE memory: hyper_dev = float[4] {lr, 1 - beta1^t, sqrt(1 - beta2^t), grad_scale}

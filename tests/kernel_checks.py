@@ -1690,7 +1690,7 @@ STRIDE_ITEMS, STRIDE_TAIL = 2048 * 256 + 333, 333      # = 107 * 4903 work items
 
 
 def _check_grid_stride(hip, emu, dev):
-    """Every kernel of elementwise.hip launched through grid_for() caps its grid (2048 blocks of 256; 4096 for the weight relayout and AdamW) and
+    """Every kernel of elementwise.hip, optim.hip and objective.hip launched through grid_for() caps its grid (2048 blocks of 256; 4096 for the weight relayout and AdamW) and
     walks the rest with a grid-stride loop: one case per kernel whose work is one full grid plus a ragged second trip, with the existing tolerance,
     and the items of the second trip once more on their own (333 of 524621 items move a whole-tensor relative L2 by 2.5 % when they are garbage;
     a subtler error in them would drown)."""

@@ -5,19 +5,20 @@
 # offset the compiler could not prove uniform).  usage: tools/check_isa.sh [out]   (default profiles/rNN_isa_resources.txt)
 cd "$(dirname "$0")/../e4t-diffusion_amd/csrc"
 OUT=${1:-../../profiles/r04_isa_resources.txt}
-FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=fast -Wno-unused-result -w"
+. ./units.sh      # UNITS, UNIT_FLAGS, unit_extra_flags
+FLAGS="$UNIT_FLAGS -w"
 echo "# $(git -C ../.. rev-parse --short HEAD)  hipcc $FLAGS" > $OUT
-for f in gemm attention norm wo elementwise image core tome; do
-  EXTRA=""; [ $f = image ] && EXTRA="-ffp-contract=off"
+for f in $UNITS; do
+  EXTRA=$(unit_extra_flags $f)
   hipcc $FLAGS $EXTRA -Rpass-analysis=kernel-resource-usage -c $f.hip -o /tmp/isa_$f.o 2> /tmp/isa_$f.rpt &
   hipcc $FLAGS $EXTRA -S --cuda-device-only $f.hip -o /tmp/isa_$f.s 2> /dev/null &
 done
 wait
-python3 - "$OUT" <<'PY'
+python3 - "$OUT" $UNITS <<'PY'
 import re, subprocess, sys
 out = open(sys.argv[1], "a")
 out.write("file,kernel,vgprs,agprs,scratch_bytes_per_lane,occupancy_waves_per_simd,lds_bytes_per_block,waterfall_loops_around_lds_dma\n")
-for f in "gemm attention norm wo elementwise image core tome".split():
+for f in sys.argv[2:]:
     rpt = open(f"/tmp/isa_{f}.rpt").read()
     asm = open(f"/tmp/isa_{f}.s").read().split("\n")
     # waterfall loops per kernel symbol
